@@ -18,6 +18,14 @@ table over RCCL; per-GPU work shrinks with N at fixed total graph.
 Run:  python bench.py [--gpus N --steps K --warmup W]
       python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
              --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run builds the graph, warms up, times the K passes (the aggregation launches'
+HIP events ride in them: `roofline`) and prints the line.  `--full` adds everything that
+takes time of its own after the timed passes: the output digest (and, at P > 1, its
+comparison with the committed one-GPU digest and the multi-GPU diagnostics), the CPU
+baseline and the C2 minibatch training step with its kernel rooflines.
+`--dump-outputs DIR` writes the last timed pass's output tables, a fixed seeded row sample
+of each, as DIR/<node type>.npy (fp32).
 """
 from __future__ import annotations
 
@@ -64,9 +72,19 @@ def parse(argv=None):
     ap.add_argument("--concurrency", default="auto",
                     help="row-kernel schedule: 'auto' (static at one rank; 16 CUs reserved + "
                          "work queue beside RCCL at several) or 'R,Q' (R reserved CUs, Q=1 queue)")
-    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed passes also run what the headline figure does not "
+                         "need: the output digest (P > 1: its comparison with the one-GPU "
+                         "digest, the multi-GPU diagnostics), the CPU baseline, the C2 "
+                         "minibatch step and its kernel rooflines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed pass's output tables as DIR/<node type>.npy "
+                         "(fp32; a fixed seeded row sample of each table, rows ascending)")
+    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto",
+                    help="(with --full) the CPU baseline")
     ap.add_argument("--minibatch", choices=["auto", "off"], default="auto",
-                    help="also time the C2 training step (one GPU; a secondary field)")
+                    help="(with --full) also time the C2 training step (one GPU; a secondary "
+                         "field)")
     ap.add_argument("--cpu-sample", type=float, default=1 / 32,
                     help="fraction of each relation's destination rows the bounded CPU "
                          "baseline aggregates (over the full-size tables and edge stream)")
@@ -284,6 +302,45 @@ def output_digest(args, shard, out, rank, world, dev):
         du = digest_add(*[p[:2] for p in parts])
         di = digest_add(*[p[2:] for p in parts])
     return {"user": f"{du[0]:016x}{du[1]:016x}", "item": f"{di[0]:016x}{di[1]:016x}"}
+
+
+DUMP_BYTES = {"user": 32 << 20, "item": 16 << 20}  # --dump-outputs: 48 MB of fp32 rows at most
+
+
+def dump_rows(n, d, budget, seed):
+    """The global rows of an n x d fp32 table that --dump-outputs keeps: every row if the
+    table fits `budget` bytes, else a fixed sample of budget / 4d rows (numpy default_rng(seed),
+    without replacement), ascending — the same rows in every run of the same workload."""
+    import numpy as np
+    k = max(1, budget // (4 * d))
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, args, shard, out, rank, world, dev):
+    """--dump-outputs: what the last timed pass returned, as `path`/user.npy and item.npy
+    (fp32, the rows dump_rows() names, in that order).  At P > 1 every rank fills in the
+    sampled rows of the user range and item block it owns (the others stay zero, so the sum
+    over the ranks is exact) and rank 0 writes the files: the same rows at any P."""
+    import numpy as np
+    S = shard.shard_rows["item"]
+    own = {"user": (shard.p_lo, shard.p_hi),
+           "item": (rank * S, min((rank + 1) * S, args.items))}
+    total = {"user": args.users, "item": args.items}
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+    for seed, nt in enumerate(("user", "item")):
+        t = out[nt]
+        rows = torch.from_numpy(dump_rows(total[nt], t.shape[1], DUMP_BYTES[nt], seed)).to(dev)
+        lo, hi = own[nt]
+        mine = (rows >= lo) & (rows < hi)
+        buf = torch.zeros((rows.numel(), t.shape[1]), dtype=torch.float32, device=dev)
+        buf[mine] = t[rows[mine] - lo].float()
+        if world > 1:
+            dist.all_reduce(buf)
+        if rank == 0:
+            np.save(os.path.join(path, nt + ".npy"), buf.cpu().numpy())
 
 
 def p1_digest_lookup(path, args):
@@ -537,6 +594,8 @@ def spawn_ranks(n: int, argv) -> int:
 
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit(f"bench.py: --steps {args.steps}: need at least one timed step")
     world, spawn = resolve_world(args)
     if spawn is not None:
         sys.exit(spawn_ranks(spawn, sys.argv[1:]))
@@ -648,11 +707,16 @@ def main():
               f"{torch.cuda.memory_stats().get('num_alloc_retries', 0)}", file=sys.stderr,
               flush=True)
     elapsed = ex.max_scalar(elapsed, dev)
-    hb.enter("output digest")
-    digest = output_digest(args, shard, out, rank, world, dev)
+    if args.dump_outputs:
+        hb.enter("output dump")
+        dump_outputs(args.dump_outputs, args, shard, out, rank, world, dev)
+    digest = None
+    if args.full or args.record_digest:
+        hb.enter("output digest")
+        digest = output_digest(args, shard, out, rank, world, dev)
     del out
     bitwise, digest_src = None, None
-    if world > 1:
+    if world > 1 and digest is not None:
         if det:
             ref, digest_src = p1_digest_lookup(args.p1_digests, args)
             if ref is not None:
@@ -710,13 +774,13 @@ def main():
                          f"traffic_{t}": traffic.get(t)})
 
     diag = None
-    if world > 1:
+    if world > 1 and args.full:
         hb.enter("multi-GPU diagnostics (collective replay, per-rank compute)")
         diag = multi_gpu_diagnostics(args, runner, ex, feats, model, shard, det, conc, dev,
                                      ms_step)
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_baseline == "auto":
+    if rank == 0 and world == 1 and args.full and args.cpu_baseline == "auto":
         hb.enter("CPU baseline")
         try:
             cpu = cpu_baseline(args, d)
@@ -725,7 +789,7 @@ def main():
                    "sample": f"failed: {exc!r}"}
 
     mb = None
-    if world == 1 and args.minibatch == "auto":
+    if world == 1 and args.full and args.minibatch == "auto":
         hb.enter("minibatch (C2 training step)")
         try:
             mb = minibatch_step(dev)
@@ -749,9 +813,10 @@ def main():
                                 not runner.concurrency[1] else "queue")
                                + (f", {runner.concurrency[0]} CUs reserved"
                                   if runner.concurrency and runner.concurrency[0] else "")}
-        cfg["output_digest"] = digest  # P-independent in deterministic mode
+        if digest is not None:
+            cfg["output_digest"] = digest  # P-independent in deterministic mode
         cfg["bits_sources"] = bits_digest()
-        if world > 1:
+        if world > 1 and digest is not None:
             cfg["bitwise_vs_p1"] = bitwise
             cfg["bitwise_vs_p1_src"] = digest_src
         if ag_choice is not None:
@@ -762,7 +827,7 @@ def main():
             "metric": "edges aggregated/sec, full-graph embed pass, d=128",
             "value": value, "unit": "edges/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "fp32",
+            "scaling": "strong", "vs_baseline": None, "dtype": "fp32", "full": args.full,
             "data": "synthetic (counter-hash graph seed 11, N(0,1) features, xavier weights)",
             "config": cfg, "roofline": roof, "cpu_baseline": cpu,
         }
