@@ -14,82 +14,16 @@
 //   sddmm_cos                       <- CosinePrediction.forward src/model.py:317-327
 //   edge_mlp                        <- PredictingModule.forward src/model.py:290-305
 //   edge_mlp_grouped                <- the same over negative_sampler.Uniform's pair graphs
-//   sample_*, scan, relabel ops     <- dgl samplers / to_block, src/sampling.py:153-161
-#include <ATen/ATen.h>
-#include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <torch/library.h>
-
+// The sampler and loader ops (sample_*, scan, relabel, gathers) are in torch_sampler.cpp.
 #include <algorithm>
 #include <utility>
-#include <map>
 #include <vector>
 
-#include "gnnrec.h"
+#include "torch_common.hpp"
 
 namespace {
 
-using at::Tensor;
-using c10::optional;
-
-void ck(int rc, const char* what) {
-  if (rc == GNNREC_OK) return;
-  const char* msg = gnnrec_last_error();
-  TORCH_CHECK_VALUE(rc != GNNREC_EINVAL, what, ": ", msg);
-  TORCH_CHECK(false, what, ": ", msg, " (status ", rc, ")");
-}
-
-void* stream_of(const Tensor& t) {
-  return c10::hip::getCurrentHIPStream(t.device().index()).stream();
-}
-
-// Every device operand of one op must sit on ONE device: the guard and the stream come from
-// one of them, and a pointer into another GPU's memory would fault in the kernel instead of
-// raising.  Each op opens a OneDevice scope; dev()/same_dev() compare every operand with
-// the first one seen in it.
-thread_local bool g_op_dev_set = false;
-thread_local c10::Device g_op_device{c10::DeviceType::CPU};
-struct OneDevice {
-  OneDevice() { g_op_dev_set = false; }
-  ~OneDevice() { g_op_dev_set = false; }
-};
-void same_dev(const Tensor& t, const char* name) {
-  if (!t.defined() || !t.is_cuda()) return;
-  if (!g_op_dev_set) {
-    g_op_device = t.device();
-    g_op_dev_set = true;
-    return;
-  }
-  TORCH_CHECK_VALUE(t.device() == g_op_device, name, " is on ", t.device(),
-                    " but the op's other operands are on ", g_op_device);
-}
-
-// device operand (or meta/fake during tracing) of the given dtype
-void dev(const Tensor& t, const char* name, c10::ScalarType dt) {
-  TORCH_CHECK_VALUE(t.is_cuda() || t.is_meta(), name,
-                    " must be a HIP device tensor (gnnrec has no CPU path), got ", t.device());
-  TORCH_CHECK_VALUE(t.scalar_type() == dt, name, " must be ", dt, ", got ", t.scalar_type());
-  same_dev(t, name);
-}
-void dev(const optional<Tensor>& t, const char* name, c10::ScalarType dt) {
-  if (t.has_value() && t->defined()) dev(*t, name, dt);
-}
-
-bool has(const optional<Tensor>& t) { return t.has_value() && t->defined(); }
-
-template <typename T>
-T* p(const Tensor& t) { return reinterpret_cast<T*>(t.data_ptr()); }
-template <typename T>
-T* p(const optional<Tensor>& t) { return has(t) ? reinterpret_cast<T*>(t->data_ptr()) : nullptr; }
-
-// leading dimension of a 2-D row-major operand (unit column stride)
-int64_t ld(const Tensor& t, const char* name) {
-  TORCH_CHECK_VALUE(t.dim() == 2, name, " must be 2-D, got ", t.sizes());
-  TORCH_CHECK_VALUE(t.stride(1) == 1 || t.size(1) <= 1, name, " must have unit column stride");
-  return std::max<int64_t>({t.stride(0), t.size(1), 1});
-}
-
-bool meta(const Tensor& t) { return t.is_meta(); }
+using namespace gnnrec_torch;
 
 // ---------------------------------------------------------------- a1 aggregation
 // live (nullable, one device int64): rows from it on are empty rows (gnnrec_spmm_csr_live_f32)
@@ -577,146 +511,6 @@ void edge_mlp_grouped(const Tensor& src_g, const optional<Tensor>& first, int64_
                                  p<float>(W2), p<float>(b2), p<float>(w3), p<float>(b3),
                                  stream_of(P)),
      "gnnrec_edge_mlp_grouped_f32");
-}
-
-// ---------------------------------------------------------------- a9 sampler / relabel
-// excluded_rows flags one byte per destination row (the kernels index it by the seed's global
-// id) and only narrows the exclusion: it means nothing without the eid mask
-void check_excluded_rows(const Tensor& indptr, const optional<Tensor>& excluded,
-                         const optional<Tensor>& excluded_rows) {
-  if (!has(excluded_rows)) return;
-  TORCH_CHECK_VALUE(has(excluded), "excluded_rows given without the excluded eid mask");
-  TORCH_CHECK_VALUE(excluded_rows->numel() >= indptr.numel() - 1,
-                    "excluded_rows must hold one flag per destination row (",
-                    indptr.numel() - 1, "), got ", excluded_rows->numel());
-}
-
-void sample_count(const Tensor& indptr, const Tensor& eids, const optional<Tensor>& excluded,
-                  const Tensor& seeds, int64_t fanout, int64_t seed_key, Tensor& counts,
-                  const optional<Tensor>& excluded_rows) {
-  const OneDevice one_device_;
-  dev(indptr, "indptr", at::kLong);
-  dev(eids, "eids", at::kLong);
-  dev(excluded, "excluded", at::kByte);
-  dev(excluded_rows, "excluded_rows", at::kByte);
-  dev(seeds, "seeds", at::kLong);
-  dev(counts, "counts", at::kLong);
-  TORCH_CHECK_VALUE(counts.numel() >= seeds.numel(), "counts shorter than seeds");
-  check_excluded_rows(indptr, excluded, excluded_rows);
-  if (meta(seeds)) return;
-  const c10::DeviceGuard g(seeds.device());
-  ck(gnnrec_sample_count(p<int64_t>(indptr), p<int64_t>(eids), p<uint8_t>(excluded),
-                         p<uint8_t>(excluded_rows), p<int64_t>(seeds), seeds.numel(), fanout,
-                         (uint64_t)seed_key,
-                         p<int64_t>(counts), stream_of(seeds)),
-     "gnnrec_sample_count");
-}
-
-void sample_fill(const Tensor& indptr, const Tensor& indices, const Tensor& eids,
-                 const optional<Tensor>& excluded, const Tensor& seeds, int64_t fanout,
-                 int64_t seed_key, const Tensor& out_indptr, Tensor& out_src, Tensor& out_eid,
-                 const optional<Tensor>& excluded_rows) {
-  const OneDevice one_device_;
-  dev(indptr, "indptr", at::kLong);
-  dev(indices, "indices", at::kInt);
-  dev(eids, "eids", at::kLong);
-  dev(excluded, "excluded", at::kByte);
-  dev(excluded_rows, "excluded_rows", at::kByte);
-  dev(seeds, "seeds", at::kLong);
-  dev(out_indptr, "out_indptr", at::kLong);
-  dev(out_src, "out_src", at::kLong);
-  dev(out_eid, "out_eid", at::kLong);
-  TORCH_CHECK_VALUE(out_indptr.numel() >= seeds.numel() + 1, "out_indptr shorter than seeds + 1");
-  check_excluded_rows(indptr, excluded, excluded_rows);
-  if (meta(seeds)) return;
-  const c10::DeviceGuard g(seeds.device());
-  ck(gnnrec_sample_fill(p<int64_t>(indptr), p<int32_t>(indices), p<int64_t>(eids),
-                        p<uint8_t>(excluded), p<uint8_t>(excluded_rows), p<int64_t>(seeds),
-                        seeds.numel(), fanout,
-                        (uint64_t)seed_key, p<int64_t>(out_indptr), p<int64_t>(out_src),
-                        p<int64_t>(out_eid), stream_of(seeds)),
-     "gnnrec_sample_fill");
-}
-
-void exclusive_scan(const Tensor& x, Tensor& out, Tensor& ws) {
-  const OneDevice one_device_;
-  dev(out, "out", at::kLong);
-  TORCH_CHECK_VALUE(x.is_cuda() || x.is_meta(), "x must be a HIP device tensor");
-  TORCH_CHECK_VALUE(x.scalar_type() == at::kLong || x.scalar_type() == at::kInt,
-                    "exclusive_scan supports int32/int64");
-  TORCH_CHECK_VALUE(x.is_contiguous() && out.numel() == x.numel() + 1,
-                    "exclusive_scan: contiguous x [n] and out [n+1]");
-  if (meta(x)) return;
-  const c10::DeviceGuard g(x.device());
-  if (x.scalar_type() == at::kLong)
-    ck(gnnrec_exclusive_scan_i64(p<int64_t>(x), x.numel(), p<int64_t>(out), ws.data_ptr(),
-                                 stream_of(x)),
-       "gnnrec_exclusive_scan_i64");
-  else
-    ck(gnnrec_exclusive_scan_i32(p<int32_t>(x), x.numel(), p<int64_t>(out), ws.data_ptr(),
-                                 stream_of(x)),
-       "gnnrec_exclusive_scan_i32");
-}
-
-void mark_ids(const Tensor& ids, const Tensor& prefix_pos, Tensor& mark) {
-  const OneDevice one_device_;
-  dev(ids, "ids", at::kLong);
-  dev(prefix_pos, "prefix_pos", at::kLong);
-  dev(mark, "mark", at::kInt);
-  if (meta(ids)) return;
-  const c10::DeviceGuard g(ids.device());
-  ck(gnnrec_mark_ids(p<int64_t>(ids), ids.numel(), p<int64_t>(prefix_pos), p<int32_t>(mark),
-                     stream_of(ids)),
-     "gnnrec_mark_ids");
-}
-
-void relabel_ids(const Tensor& ids, const Tensor& prefix_pos, const Tensor& rank, int64_t n_prefix,
-                 Tensor& local) {
-  const OneDevice one_device_;
-  dev(ids, "ids", at::kLong);
-  dev(prefix_pos, "prefix_pos", at::kLong);
-  dev(rank, "rank", at::kLong);
-  dev(local, "local", at::kLong);
-  TORCH_CHECK_VALUE(local.numel() >= ids.numel(), "local shorter than ids");
-  if (meta(ids)) return;
-  const c10::DeviceGuard g(ids.device());
-  ck(gnnrec_relabel_ids(p<int64_t>(ids), ids.numel(), p<int64_t>(prefix_pos), p<int64_t>(rank),
-                        n_prefix, p<int64_t>(local), stream_of(ids)),
-     "gnnrec_relabel_ids");
-}
-
-void compact_marked(const Tensor& mark, const Tensor& rank, Tensor& out_ids) {
-  const OneDevice one_device_;
-  dev(mark, "mark", at::kInt);
-  dev(rank, "rank", at::kLong);
-  dev(out_ids, "out_ids", at::kLong);
-  if (meta(mark)) return;
-  const c10::DeviceGuard g(mark.device());
-  ck(gnnrec_compact_marked(p<int32_t>(mark), p<int64_t>(rank), mark.numel(), p<int64_t>(out_ids),
-                           stream_of(mark)),
-     "gnnrec_compact_marked");
-}
-
-void set_prefix_pos(const Tensor& prefix, Tensor& prefix_pos) {
-  const OneDevice one_device_;
-  dev(prefix, "prefix", at::kLong);
-  dev(prefix_pos, "prefix_pos", at::kLong);
-  if (meta(prefix)) return;
-  const c10::DeviceGuard g(prefix.device());
-  ck(gnnrec_set_prefix_pos(p<int64_t>(prefix), prefix.numel(), p<int64_t>(prefix_pos),
-                           stream_of(prefix)),
-     "gnnrec_set_prefix_pos");
-}
-
-void clear_prefix_pos(const Tensor& prefix, Tensor& prefix_pos) {
-  const OneDevice one_device_;
-  dev(prefix, "prefix", at::kLong);
-  dev(prefix_pos, "prefix_pos", at::kLong);
-  if (meta(prefix)) return;
-  const c10::DeviceGuard g(prefix.device());
-  ck(gnnrec_clear_prefix_pos(p<int64_t>(prefix), prefix.numel(), p<int64_t>(prefix_pos),
-                             stream_of(prefix)),
-     "gnnrec_clear_prefix_pos");
 }
 
 // ---------------------------------------------------------------- f1 top-k
@@ -1337,39 +1131,6 @@ void lstm_slots(const Tensor& indptr, const Tensor& indices, const Tensor& order
      "gnnrec_lstm_slots");
 }
 
-// ---------------------------------------------------------------- a10 row gather
-void gather_rows(const Tensor& src, const Tensor& idx, Tensor& out) {
-  const OneDevice one_device_;
-  dev(idx, "idx", at::kLong);
-  TORCH_CHECK_VALUE(src.is_cuda() || src.is_meta(), "src: expected a device tensor (there is no CPU path)");
-  same_dev(src, "src");
-  same_dev(out, "out");
-  TORCH_CHECK_VALUE(src.dim() >= 1 && out.dim() == src.dim() && out.scalar_type() == src.scalar_type(),
-                    "gather_rows: out must match src's dtype and rank");
-  TORCH_CHECK_VALUE(idx.is_contiguous() && out.size(0) == idx.numel() && out.is_contiguous(),
-                    "gather_rows: contiguous idx [n] and out [n, ...]");
-  const int64_t es = src.element_size();
-  int64_t row_elems = 1;
-  for (int64_t k = 1; k < src.dim(); ++k) {
-    TORCH_CHECK_VALUE(out.size(k) == src.size(k), "gather_rows: row shapes differ");
-    row_elems *= src.size(k);
-  }
-  // rows are copied as flat byte runs: within a row the elements must be contiguous
-  int64_t inner = 1;
-  for (int64_t k = src.dim() - 1; k >= 1; --k) {
-    TORCH_CHECK_VALUE(src.size(k) <= 1 || src.stride(k) == inner,
-                      "gather_rows: src rows must be contiguous (stride ", src.stride(k),
-                      " in dim ", k, ")");
-    inner *= src.size(k);
-  }
-  const int64_t row_bytes = es * row_elems;
-  if (meta(src)) return;
-  const c10::DeviceGuard g(src.device());
-  ck(gnnrec_gather_rows(src.data_ptr(), src.stride(0) * es, p<int64_t>(idx), idx.numel(),
-                        row_bytes, out.data_ptr(), row_bytes, stream_of(src)),
-     "gnnrec_gather_rows");
-}
-
 // ---------------------------------------------------------------- f2 loss
 void margin_loss(const Tensor& pos, const Tensor& neg, int64_t K, double delta,
                  const optional<Tensor>& mask, const optional<Tensor>& recency, Tensor& g_pos,
@@ -1432,643 +1193,6 @@ void hold_cus(int64_t blocks, int64_t threads, int64_t lds_bytes, int64_t usec, 
   ck(gnnrec_hold_cus((int)blocks, (int)threads, (int)lds_bytes, usec, p<float>(sink),
                      stream_of(sink)),
      "gnnrec_hold_cus");
-}
-
-// ---------------------------------------------------------------- a9 one sampled layer
-// The whole of one block layer of BlockSampler.sample_blocks (gnnrec/sampling.py) issued
-// from C++: per relation count -> scan; ONE host read of the sampled edge counts; fills;
-// per node type the to_block relabel (prefix map, marks of the new sources, scan); ONE
-// host read of the new-source counts; compaction, relabel of every relation's sources,
-// scratch reset.  The same kernels in the same order with the same keys as the Python
-// form it replaces (bitwise the same blocks), minus ≈ 40 Python-level launches per layer
-// (the C2 step's sampler spent 1.5 ms of host time per batch on them).
-//   relations r: CSR (indptr, indices int32, eids), optional exclusion mask, source / dst
-//   node-type index, fanout (-1 = all), RNG key; node types t: the seeds (dst prefix) and
-//   the Relabeler scratch (prefix_pos int64 [n_t] = -1, mark int32 [n_t] = 0, restored on
-//   exit).  Returns per relation (out indptr, local src int32, eids), per type the src
-//   node ids (prefix first), and the edge counts.
-Tensor exclusive_scan_new(const Tensor& x) {
-  const OneDevice one_device_;
-  const int64_t n = x.numel();
-  Tensor out = at::empty({n + 1}, x.options().dtype(at::kLong));
-  Tensor ws = at::empty({std::max<int64_t>(1, (gnnrec_scan_workspace_bytes(n) + 7) / 8)},
-                        x.options().dtype(at::kLong));
-  exclusive_scan(x, out, ws);
-  return out;
-}
-
-std::tuple<std::vector<Tensor>, std::vector<Tensor>, std::vector<Tensor>, std::vector<Tensor>,
-           std::vector<int64_t>>
-sample_layer(at::TensorList indptrs, at::TensorList indices, at::TensorList eids,
-             const c10::List<optional<Tensor>>& masks,
-             const c10::List<optional<Tensor>>& mask_rows, at::IntArrayRef src_type,
-             at::IntArrayRef dst_type, at::IntArrayRef fanouts, at::IntArrayRef keys,
-             at::TensorList seeds, at::TensorList prefix_pos, at::TensorList marks) {
-  const OneDevice one_device_;
-  const size_t R = indptrs.size(), NT = seeds.size();
-  TORCH_CHECK_VALUE(indices.size() == R && eids.size() == R && masks.size() == R &&
-                        mask_rows.size() == R &&
-                        src_type.size() == R && dst_type.size() == R && fanouts.size() == R &&
-                        keys.size() == R,
-                    "sample_layer: one entry per relation in every relation list");
-  TORCH_CHECK_VALUE(prefix_pos.size() == NT && marks.size() == NT,
-                    "sample_layer: one seed list and one scratch pair per node type");
-  for (size_t r = 0; r < R; ++r)
-    TORCH_CHECK_VALUE(src_type[r] >= 0 && (size_t)src_type[r] < NT && dst_type[r] >= 0 &&
-                          (size_t)dst_type[r] < NT,
-                      "sample_layer: node-type index out of range");
-  TORCH_CHECK_VALUE(NT > 0, "sample_layer: no node types");
-  const c10::DeviceGuard g(seeds[0].device());
-  // Bounded fanouts (every relation samples at most fanout >= 0 in-edges per seed): the
-  // fills write into capacity-sized buffers (seeds x fanout, unused tail = -1, which the
-  // mark / relabel kernels skip) and the new-source scan runs before any size is known,
-  // so the layer's edge counts and new-node counts come back in ONE readback.  Unbounded
-  // (full-neighbour) layers read the edge counts first to size the fills (two readbacks).
-  bool bounded = true;
-  for (size_t r = 0; r < R; ++r) bounded = bounded && fanouts[r] >= 0;
-  // counts -> out indptr per relation
-  std::vector<Tensor> o_ip(R), o_src(R), o_eid(R), src_loc(R), src_nid(NT);
-  for (size_t r = 0; r < R; ++r) {
-    const Tensor& sd = seeds[dst_type[r]];
-    Tensor counts = at::empty({sd.numel()}, sd.options().dtype(at::kLong));
-    const optional<Tensor> m = masks.get(r);
-    sample_count(indptrs[r], eids[r], m, sd, fanouts[r], keys[r], counts, mask_rows.get(r));
-    o_ip[r] = exclusive_scan_new(counts);
-  }
-  std::vector<int64_t> totals(R, 0);
-  auto read_totals = [&](std::vector<Tensor> extra) {  // one device -> host copy
-    std::vector<Tensor> last;
-    for (size_t r = 0; r < R; ++r) last.push_back(o_ip[r].narrow(0, o_ip[r].numel() - 1, 1));
-    for (auto& t : extra) last.push_back(t);
-    const Tensor t = at::cat(last).to(at::kCPU);
-    for (size_t r = 0; r < R; ++r) totals[r] = t.data_ptr<int64_t>()[r];
-    std::vector<int64_t> rest;
-    for (size_t i = R; i < last.size(); ++i) rest.push_back(t.data_ptr<int64_t>()[i]);
-    return rest;
-  };
-  if (R && !bounded) read_totals({});  // the unbounded layer's first readback
-  for (size_t r = 0; r < R; ++r) {
-    const Tensor& sd = seeds[dst_type[r]];
-    const int64_t cap = bounded ? sd.numel() * fanouts[r] : totals[r];
-    o_src[r] = bounded ? at::full({cap}, -1, sd.options().dtype(at::kLong))
-                       : at::empty({cap}, sd.options().dtype(at::kLong));
-    o_eid[r] = at::empty({cap}, sd.options().dtype(at::kLong));
-    const optional<Tensor> m = masks.get(r);
-    sample_fill(indptrs[r], indices[r], eids[r], m, sd, fanouts[r], keys[r], o_ip[r], o_src[r],
-                o_eid[r], mask_rows.get(r));
-  }
-  // relabel: per node type, mark the new sources and scan
-  std::vector<Tensor> rank(NT);
-  for (size_t t = 0; t < NT; ++t) {
-    Tensor pp = prefix_pos[t], mk = marks[t];
-    set_prefix_pos(seeds[t], pp);
-    for (size_t r = 0; r < R; ++r)
-      if ((size_t)src_type[r] == t) mark_ids(o_src[r], pp, mk);
-    rank[t] = exclusive_scan_new(mk);
-  }
-  // local source ids and (bounded) the fresh nodes, before any count is on the host
-  std::vector<Tensor> nodes(NT);
-  auto relabel_all = [&](size_t t) {
-    Tensor pp = prefix_pos[t];
-    const int64_t n_p = seeds[t].numel();
-    for (size_t r = 0; r < R; ++r) {
-      if ((size_t)src_type[r] != t) continue;
-      Tensor loc = at::empty({o_src[r].numel()}, seeds[t].options().dtype(at::kLong));
-      relabel_ids(o_src[r], pp, rank[t], n_p, loc);
-      src_loc[r] = loc;
-    }
-  };
-  std::vector<int64_t> n_new(NT, 0);
-  if (bounded) {
-    for (size_t t = 0; t < NT; ++t) {
-      const Tensor& pre = seeds[t];
-      const int64_t n_p = pre.numel();
-      int64_t cap = 0;  // new sources of type t: at most the sampled edges from it
-      for (size_t r = 0; r < R; ++r)
-        if ((size_t)src_type[r] == t) cap += o_src[r].numel();
-      cap = std::min(cap, marks[t].numel());
-      nodes[t] = at::empty({n_p + cap}, pre.options().dtype(at::kLong));
-      nodes[t].narrow(0, 0, n_p).copy_(pre);
-      if (cap) {
-        Tensor tail = nodes[t].narrow(0, n_p, cap);
-        compact_marked(marks[t], rank[t], tail);
-      }
-      relabel_all(t);
-    }
-    std::vector<Tensor> last;
-    for (size_t t = 0; t < NT; ++t) last.push_back(rank[t].narrow(0, rank[t].numel() - 1, 1));
-    const std::vector<int64_t> nn = read_totals(last);  // the layer's one size readback
-    for (size_t t = 0; t < NT; ++t) n_new[t] = nn[t];
-    for (size_t r = 0; r < R; ++r) {
-      o_src[r] = o_src[r].narrow(0, 0, totals[r]);
-      o_eid[r] = o_eid[r].narrow(0, 0, totals[r]);
-    }
-  } else {
-    std::vector<Tensor> last;
-    for (size_t t = 0; t < NT; ++t) last.push_back(rank[t].narrow(0, rank[t].numel() - 1, 1));
-    const Tensor c = at::cat(last).to(at::kCPU);  // the layer's second size readback
-    for (size_t t = 0; t < NT; ++t) n_new[t] = c.data_ptr<int64_t>()[t];
-    for (size_t t = 0; t < NT; ++t) {
-      const Tensor& pre = seeds[t];
-      const int64_t n_p = pre.numel();
-      nodes[t] = at::empty({n_p + n_new[t]}, pre.options().dtype(at::kLong));
-      nodes[t].narrow(0, 0, n_p).copy_(pre);
-      if (n_new[t]) {
-        Tensor fresh = nodes[t].narrow(0, n_p, n_new[t]);
-        compact_marked(marks[t], rank[t], fresh);
-      }
-      relabel_all(t);
-    }
-  }
-  for (size_t t = 0; t < NT; ++t) {
-    const Tensor& pre = seeds[t];
-    const int64_t n_p = pre.numel();
-    Tensor fresh = nodes[t].narrow(0, n_p, n_new[t]);
-    Tensor pp = prefix_pos[t], mk = marks[t];
-    clear_prefix_pos(pre, pp);
-    if (n_new[t]) mk.index_fill_(0, fresh, 0);
-    src_nid[t] = bounded ? nodes[t].narrow(0, 0, n_p + n_new[t]) : nodes[t];
-  }
-  for (size_t r = 0; r < R; ++r)
-    src_loc[r] = src_loc[r].narrow(0, 0, totals[r]).to(at::kInt);
-  return {o_ip, src_loc, o_eid, src_nid, totals};
-}
-
-// ---------------------------------------------------------------- a9 fused sample_blocks
-// Every block of one bounded-fanout BlockSampler.sample_blocks call (gnnrec_sample_blocks:
-// 1 + 3L launches, include/gnnrec.h) with ONE host read of the sizes at the end: outputs are
-// allocated at their capacities and returned narrowed to the actual sizes.
-//   relations r: global in-CSR, src / dst type index, exclusion (eids, COO dst, flag arrays:
-//   all four or none); types t: node count, step-0 seeds, scratch (pos int64 [2n], bits int64
-//   [2 ceil(n/64)], word_rank int64 [ceil(n/64) + 1]); fanouts / keys flattened [step][r].
-//   -> per step s and relation r (flattened [s][r]): out_indptr [n_dst + 1], local src int32,
-//   eids; per step and type ([s][t]): the source node ids (seeds first); the sizes (node
-//   counts rows -1..L-1 x T, then edge counts L x R).
-std::tuple<std::vector<Tensor>, std::vector<Tensor>, std::vector<Tensor>, std::vector<Tensor>,
-           std::vector<int64_t>, std::vector<Tensor>>
-sample_blocks(at::TensorList indptrs, at::TensorList indices, at::TensorList eids,
-              at::IntArrayRef src_type, at::IntArrayRef dst_type,
-              const c10::List<optional<Tensor>>& excl_eids,
-              const c10::List<optional<Tensor>>& coo_dst,
-              const c10::List<optional<Tensor>>& excl_masks,
-              const c10::List<optional<Tensor>>& excl_rows, at::IntArrayRef n_nodes,
-              at::TensorList seeds, at::TensorList pos, at::TensorList bits,
-              at::TensorList word_rank, at::TensorList marks, at::IntArrayRef fanouts,
-              at::IntArrayRef keys, int64_t steps, int64_t stamp, bool static_shapes,
-              const optional<Tensor>& sizes_out,
-              at::IntArrayRef node_cap_hint, const optional<Tensor>& overflow,
-              at::TensorList edge_tables, at::IntArrayRef edge_table_rel,
-              at::TensorList node_tables, at::IntArrayRef node_table_type,
-              at::TensorList edge_recs) {
-  const OneDevice one_device_;
-  const size_t R = indptrs.size(), NT = n_nodes.size();
-  TORCH_CHECK_VALUE(edge_recs.empty() || edge_recs.size() == R,
-                    "sample_blocks: edge_recs holds one packed record array per relation or none");
-  TORCH_CHECK_VALUE(indices.size() == R && eids.size() == R && src_type.size() == R &&
-                        dst_type.size() == R && excl_eids.size() == R && coo_dst.size() == R &&
-                        excl_masks.size() == R && excl_rows.size() == R,
-                    "sample_blocks: one entry per relation in every relation list");
-  TORCH_CHECK_VALUE(seeds.size() == NT && pos.size() == NT && bits.size() == NT &&
-                        word_rank.size() == NT && marks.size() == NT,
-                    "sample_blocks: one seed list and one scratch set per node type");
-  TORCH_CHECK_VALUE(steps >= 1 && steps <= GNNREC_SB_MAX_STEPS && R <= GNNREC_SB_MAX_RELS &&
-                        NT >= 1 && NT <= GNNREC_SB_MAX_TYPES,
-                    "sample_blocks: ", steps, " steps, ", R, " relations, ", NT,
-                    " types exceed the fused sampler's limits");
-  TORCH_CHECK_VALUE((int64_t)fanouts.size() == steps * (int64_t)R &&
-                        (int64_t)keys.size() == steps * (int64_t)R,
-                    "sample_blocks: fanouts / keys must hold steps x relations entries");
-  gnnrec_sample_plan P{};
-  P.n_rels = (int)R;
-  P.n_types = (int)NT;
-  P.n_steps = (int)steps;
-  P.stamp = (uint32_t)stamp;
-  P.static_shapes = static_shapes ? 1 : 0;
-  // static capacity hints [step][type] (empty: none) and the overflow flag they may raise
-  TORCH_CHECK_VALUE(node_cap_hint.empty() || (int64_t)node_cap_hint.size() == steps * (int64_t)NT,
-                    "sample_blocks: node_cap_hint must hold steps x types entries");
-  for (int64_t s = 0; s < steps && !node_cap_hint.empty(); ++s)
-    for (size_t t = 0; t < NT; ++t) P.node_cap_hint[s][t] = node_cap_hint[s * NT + t];
-  if (has(overflow)) {
-    dev(overflow, "overflow", at::kLong);
-    TORCH_CHECK_VALUE(overflow->numel() >= 1, "sample_blocks: overflow holds one flag");
-    P.overflow = p<int64_t>(overflow);
-  }
-  for (size_t r = 0; r < R; ++r) {
-    dev(indptrs[r], "indptr", at::kLong);
-    dev(indices[r], "indices", at::kInt);
-    dev(eids[r], "eids", at::kLong);
-    TORCH_CHECK_VALUE(src_type[r] >= 0 && (size_t)src_type[r] < NT && dst_type[r] >= 0 &&
-                          (size_t)dst_type[r] < NT,
-                      "sample_blocks: node-type index out of range");
-    TORCH_CHECK_VALUE(indptrs[r].numel() == n_nodes[dst_type[r]] + 1 &&
-                          eids[r].numel() == indices[r].numel(),
-                      "sample_blocks: relation ", r, ": indptr must hold n_dst + 1 entries and "
-                      "eids one per index");
-    gnnrec_sample_rel& re = P.rel[r];
-    re.indptr = p<int64_t>(indptrs[r]);
-    re.indices = p<int32_t>(indices[r]);
-    re.eids = p<int64_t>(eids[r]);
-    if (!edge_recs.empty()) {  // {eid << 32 | src} per CSR edge (HeteroGraph.edge_records)
-      dev(edge_recs[r], "edge_recs", at::kLong);
-      TORCH_CHECK_VALUE(edge_recs[r].is_contiguous() && edge_recs[r].numel() == eids[r].numel(),
-                        "sample_blocks: relation ", r, ": edge_recs must hold one record per edge");
-      re.edge_rec = p<uint64_t>(edge_recs[r]);
-    }
-    re.src_type = (int32_t)src_type[r];
-    re.dst_type = (int32_t)dst_type[r];
-    const optional<Tensor> xe = excl_eids.get(r), cd = coo_dst.get(r), xm = excl_masks.get(r),
-                           xr = excl_rows.get(r);
-    TORCH_CHECK_VALUE(has(xe) == has(cd) && has(xe) == has(xm) && has(xe) == has(xr),
-                      "sample_blocks: relation ", r,
-                      ": exclusion needs the eids, the COO dst and both flag arrays");
-    if (has(xe)) {
-      dev(xe, "excl_eids", at::kLong);
-      dev(cd, "coo_dst", at::kLong);
-      dev(xm, "excl_mask", at::kByte);
-      dev(xr, "excl_rows", at::kByte);
-      TORCH_CHECK_VALUE(xe->is_contiguous() && cd->numel() == eids[r].numel() &&
-                            xm->numel() == eids[r].numel() &&
-                            xr->numel() == n_nodes[dst_type[r]],
-                        "sample_blocks: relation ", r, ": exclusion arrays sized E, E, n_dst");
-      re.excl_eids = p<int64_t>(xe);
-      re.n_excl = xe->numel();
-      re.coo_dst = p<int64_t>(cd);
-      re.excl_mask = p<uint8_t>(xm);
-      re.excl_rows = p<uint8_t>(xr);
-    }
-    for (int64_t s = 0; s < steps; ++s) {
-      P.fanout[s][r] = fanouts[s * R + r];
-      P.key[s][r] = (uint64_t)keys[s * R + r];
-    }
-  }
-  for (size_t t = 0; t < NT; ++t) {
-    dev(seeds[t], "seeds", at::kLong);
-    dev(pos[t], "pos", at::kLong);
-    dev(bits[t], "bits", at::kLong);
-    dev(word_rank[t], "word_rank", at::kLong);
-    dev(marks[t], "marks", at::kByte);
-    const int64_t W = (n_nodes[t] + 63) / 64;
-    TORCH_CHECK_VALUE(seeds[t].is_contiguous() && pos[t].numel() == 2 * n_nodes[t] &&
-                          bits[t].numel() == 2 * W && word_rank[t].numel() == W + 1 &&
-                          marks[t].numel() == 4 * 64 * W,
-                      "sample_blocks: type ", t,
-                      ": scratch sized 2n, 2 ceil(n/64), ceil(n/64)+1, 256 ceil(n/64) bytes");
-    gnnrec_sample_type& ty = P.type[t];
-    ty.n_nodes = n_nodes[t];
-    ty.seeds = p<int64_t>(seeds[t]);
-    ty.n_seeds = seeds[t].numel();
-    ty.pos = p<int64_t>(pos[t]);
-    ty.bits = p<uint64_t>(bits[t]);
-    ty.word_rank = p<int64_t>(word_rank[t]);
-    ty.marks = p<uint8_t>(marks[t]);
-  }
-  int64_t seed_cap[GNNREC_SB_MAX_STEPS * GNNREC_SB_MAX_TYPES];
-  int64_t edge_cap[GNNREC_SB_MAX_STEPS * GNNREC_SB_MAX_RELS];
-  int64_t node_cap[GNNREC_SB_MAX_STEPS * GNNREC_SB_MAX_TYPES];
-  int64_t dump_rows[GNNREC_SB_MAX_STEPS * GNNREC_SB_MAX_TYPES];
-  int64_t ws_bytes = 0;
-  ck(gnnrec_sample_blocks_caps(&P, seed_cap, edge_cap, node_cap, dump_rows, &ws_bytes),
-     "gnnrec_sample_blocks_caps");
-  // static shapes: a node list also holds the next step's dump rows (the last step: one)
-  auto node_len = [&](int64_t s, size_t t) {
-    if (!static_shapes) return node_cap[s * GNNREC_SB_MAX_TYPES + t];
-    return node_cap[s * GNNREC_SB_MAX_TYPES + t] +
-           (s + 1 < steps ? dump_rows[(s + 1) * GNNREC_SB_MAX_TYPES + t] : 1);
-  };
-  const c10::DeviceGuard g(pos[0].device());
-  const auto i64 = pos[0].options();
-  std::vector<Tensor> o_ip(steps * R), o_src(steps * R), o_eid(steps * R), nodes(steps * NT);
-  for (int64_t s = 0; s < steps; ++s) {
-    for (size_t r = 0; r < R; ++r) {
-      const int64_t sc = seed_cap[s * GNNREC_SB_MAX_TYPES + dst_type[r]];
-      const int64_t ec = edge_cap[s * GNNREC_SB_MAX_RELS + r];
-      o_ip[s * R + r] = at::empty(
-          {sc + 1 + (static_shapes ? dump_rows[s * GNNREC_SB_MAX_TYPES + dst_type[r]] : 0)}, i64);
-      o_src[s * R + r] = at::empty({ec}, i64.dtype(at::kInt));
-      o_eid[s * R + r] = at::empty({ec}, i64);
-      P.out_indptr[s][r] = p<int64_t>(o_ip[s * R + r]);
-      P.out_src[s][r] = p<int32_t>(o_src[s * R + r]);
-      P.out_eid[s][r] = p<int64_t>(o_eid[s * R + r]);
-    }
-    for (size_t t = 0; t < NT; ++t) {
-      nodes[s * NT + t] = at::empty({node_len(s, t)}, i64);
-      P.nodes[s][t] = p<int64_t>(nodes[s * NT + t]);
-    }
-  }
-  const int64_t n_sizes = (steps + 1) * (int64_t)NT + steps * (int64_t)R;
-  // sizes_out: the device sizes land there and nothing is read back — the caller queues
-  // work sized by them (gathers with device row counts) before its own one read
-  if (has(sizes_out)) {
-    dev(sizes_out, "sizes_out", at::kLong);
-    TORCH_CHECK_VALUE(sizes_out->numel() == n_sizes && sizes_out->is_contiguous(),
-                      "sample_blocks: sizes_out must hold ", n_sizes, " entries");
-  }
-  Tensor sizes = has(sizes_out) ? *sizes_out : at::empty({n_sizes}, i64);
-  Tensor ws = at::empty({std::max<int64_t>(ws_bytes, 1)}, i64.dtype(at::kByte));
-  P.sizes = p<int64_t>(sizes);
-  P.workspace = ws.data_ptr();
-  ck(gnnrec_sample_blocks(&P, stream_of(pos[0])), "gnnrec_sample_blocks");
-  // the block data (a10): every step's edge data tables at its edge ids, the input block's
-  // node tables at its source ids — queued behind the sampler, row counts read on the device
-  // (static shapes: every slot; -1 ids give zero rows), ahead of the one size read below
-  TORCH_CHECK_VALUE(edge_table_rel.size() == edge_tables.size() &&
-                        node_table_type.size() == node_tables.size(),
-                    "sample_blocks: one relation / node type per data table");
-  std::vector<Tensor> gathered;
-  std::vector<gnnrec_gather_job> jobs;
-  auto add_job = [&](const Tensor& src, const Tensor& idx, int64_t n, const int64_t* n_dev) {
-    TORCH_CHECK_VALUE(src.is_cuda() && src.dim() >= 1, "sample_blocks: data tables on the device");
-    same_dev(src, "data table");
-    std::vector<int64_t> shape(src.sizes().begin(), src.sizes().end());
-    shape[0] = n;
-    int64_t inner = 1;
-    for (int64_t k = src.dim() - 1; k >= 1; --k) {
-      TORCH_CHECK_VALUE(src.size(k) <= 1 || src.stride(k) == inner,
-                        "sample_blocks: data table rows must be contiguous");
-      inner *= src.size(k);
-    }
-    Tensor out = at::empty(shape, src.options());
-    const int64_t es = src.element_size();
-    jobs.push_back(gnnrec_gather_job{src.data_ptr(), src.stride(0) * es, p<int64_t>(idx), n,
-                                     inner * es, out.data_ptr(), inner * es, n_dev});
-    gathered.push_back(out);
-  };
-  const bool exact = !static_shapes;
-  for (int64_t s = 0; s < steps; ++s)
-    for (size_t j = 0; j < edge_tables.size(); ++j) {
-      const int64_t r = edge_table_rel[j];
-      TORCH_CHECK_VALUE(r >= 0 && (size_t)r < R, "sample_blocks: edge table relation");
-      add_job(edge_tables[j], o_eid[s * R + r], edge_cap[s * GNNREC_SB_MAX_RELS + r],
-              exact ? p<int64_t>(sizes) + (steps + 1) * NT + s * R + r : nullptr);
-    }
-  for (size_t j = 0; j < node_tables.size(); ++j) {
-    const int64_t t = node_table_type[j];
-    TORCH_CHECK_VALUE(t >= 0 && (size_t)t < NT, "sample_blocks: node table type");
-    add_job(node_tables[j], nodes[(steps - 1) * NT + t], node_len(steps - 1, t),
-            exact ? p<int64_t>(sizes) + steps * NT + t : nullptr);
-  }
-  for (size_t i = 0; i < jobs.size(); i += GNNREC_GATHER_MAX_JOBS)
-    ck(gnnrec_gather_rows_batch(jobs.data() + i,
-                                (int)std::min<size_t>(GNNREC_GATHER_MAX_JOBS, jobs.size() - i),
-                                stream_of(pos[0])),
-       "gnnrec_gather_rows_batch");
-  if (static_shapes || has(sizes_out)) {  // every output at its capacity: return those
-    std::vector<int64_t> caps;  // seed caps [T], node caps [L x T], edge caps [L x R], and
-    for (size_t t = 0; t < NT; ++t) caps.push_back(seed_cap[t]);  // dump rows [L x T]
-    for (int64_t s = 0; s < steps; ++s)
-      for (size_t t = 0; t < NT; ++t) caps.push_back(node_cap[s * GNNREC_SB_MAX_TYPES + t]);
-    for (int64_t s = 0; s < steps; ++s)
-      for (size_t r = 0; r < R; ++r) caps.push_back(edge_cap[s * GNNREC_SB_MAX_RELS + r]);
-    for (int64_t s = 0; s < steps; ++s)
-      for (size_t t = 0; t < NT; ++t) caps.push_back(dump_rows[s * GNNREC_SB_MAX_TYPES + t]);
-    return {o_ip, o_src, o_eid, nodes, caps, gathered};
-  }
-  const Tensor hs = sizes.to(at::kCPU);  // the call's one size readback
-  const int64_t* h = hs.data_ptr<int64_t>();
-  std::vector<int64_t> out_sizes(h, h + n_sizes);
-  for (int64_t s = 0; s < steps; ++s) {
-    for (size_t r = 0; r < R; ++r) {
-      const int64_t n_dst = h[s * NT + dst_type[r]];
-      const int64_t ne = h[(steps + 1) * NT + s * R + r];
-      o_ip[s * R + r] = o_ip[s * R + r].narrow(0, 0, n_dst + 1);
-      o_src[s * R + r] = o_src[s * R + r].narrow(0, 0, ne);
-      o_eid[s * R + r] = o_eid[s * R + r].narrow(0, 0, ne);
-    }
-    for (size_t t = 0; t < NT; ++t)
-      nodes[s * NT + t] = nodes[s * NT + t].narrow(0, 0, h[(s + 1) * NT + t]);
-  }
-  size_t gi = 0;
-  for (int64_t s = 0; s < steps; ++s)
-    for (size_t j = 0; j < edge_tables.size(); ++j, ++gi)
-      gathered[gi] = gathered[gi].narrow(0, 0, h[(steps + 1) * NT + s * R + edge_table_rel[j]]);
-  for (size_t j = 0; j < node_tables.size(); ++j, ++gi)
-    gathered[gi] = gathered[gi].narrow(0, 0, h[steps * NT + node_table_type[j]]);
-  return {o_ip, o_src, o_eid, nodes, out_sizes, gathered};
-}
-
-// a10: several row gathers in one launch (gnnrec_gather_rows_batch): out[j] = src[j][idx[j]]
-void gather_rows_batch(at::TensorList src, at::TensorList idx, at::TensorList out,
-                       at::TensorList n_dev) {
-  const OneDevice one_device_;
-  const size_t n = src.size();
-  TORCH_CHECK_VALUE(idx.size() == n && out.size() == n && n <= GNNREC_GATHER_MAX_JOBS &&
-                        (n_dev.empty() || n_dev.size() == n),
-                    "gather_rows_batch: one idx and out (and n_dev, if any) per src, at most ",
-                    GNNREC_GATHER_MAX_JOBS, " jobs");
-  std::vector<gnnrec_gather_job> jobs(n);
-  for (size_t j = 0; j < n; ++j) {
-    dev(idx[j], "idx", at::kLong);
-    TORCH_CHECK_VALUE(src[j].is_cuda() || src[j].is_meta(),
-                      "src: expected a device tensor (there is no CPU path)");
-    same_dev(src[j], "src");
-    same_dev(out[j], "out");
-    TORCH_CHECK_VALUE(src[j].dim() >= 1 && out[j].dim() == src[j].dim() &&
-                          out[j].scalar_type() == src[j].scalar_type() && idx[j].is_contiguous() &&
-                          out[j].size(0) == idx[j].numel() && out[j].is_contiguous(),
-                      "gather_rows_batch: job ", j, ": out [n, ...] of src's dtype and rank, "
-                      "contiguous idx [n]");
-    int64_t inner = 1;
-    for (int64_t k = src[j].dim() - 1; k >= 1; --k) {
-      TORCH_CHECK_VALUE(out[j].size(k) == src[j].size(k), "gather_rows_batch: row shapes differ");
-      TORCH_CHECK_VALUE(src[j].size(k) <= 1 || src[j].stride(k) == inner,
-                        "gather_rows_batch: src rows must be contiguous");
-      inner *= src[j].size(k);
-    }
-    const int64_t es = src[j].element_size();
-    // n_dev[j] (one device int64, or empty): rows min(*n_dev, n) — a producer's count
-    const int64_t* cnt = nullptr;
-    if (!n_dev.empty() && n_dev[j].numel() > 0) {
-      dev(n_dev[j], "n_dev", at::kLong);
-      TORCH_CHECK_VALUE(n_dev[j].numel() == 1, "gather_rows_batch: n_dev entries hold one count");
-      cnt = p<int64_t>(n_dev[j]);
-    }
-    jobs[j] = gnnrec_gather_job{src[j].data_ptr(), src[j].stride(0) * es, p<int64_t>(idx[j]),
-                                idx[j].numel(), inner * es, out[j].data_ptr(), inner * es, cnt};
-  }
-  if (n == 0 || meta(src[0])) return;
-  const c10::DeviceGuard g(src[0].device());
-  ck(gnnrec_gather_rows_batch(jobs.data(), (int)n, stream_of(src[0])), "gnnrec_gather_rows_batch");
-}
-
-// a11: compact_graphs over id lists at static shapes (gnnrec_compact_ids): per node type the
-// sorted distinct ids of its lists in nodes[t] [caps[t]] (-1 past the count), each list
-// relabelled to local ids, the per-type counts left on the device — no host read, so a
-// loader feeding a captured step keeps every shape fixed.  bits [2 ceil(n/64) +
-// GNNREC_COMPACT_SCAN_WS(n)] and word_rank [ceil(n/64) + 1] per type; the bitmaps zero before
-// the first call, parity alternating.
-std::tuple<std::vector<Tensor>, std::vector<Tensor>, Tensor>
-compact_ids(at::TensorList ids, at::IntArrayRef type, at::IntArrayRef n_nodes,
-            at::IntArrayRef caps, at::TensorList bits, at::TensorList word_rank,
-            at::TensorList marks, int64_t parity) {
-  const OneDevice one_device_;
-  const size_t L = ids.size(), NT = n_nodes.size();
-  TORCH_CHECK_VALUE(type.size() == L && L <= GNNREC_COMPACT_MAX_LISTS && NT >= 1 &&
-                        NT <= GNNREC_SB_MAX_TYPES && caps.size() == NT && bits.size() == NT &&
-                        word_rank.size() == NT && marks.size() == NT,
-                    "compact_ids: at most ", GNNREC_COMPACT_MAX_LISTS, " lists (one type each) "
-                    "and 1..", GNNREC_SB_MAX_TYPES, " types (a cap and a scratch pair each)");
-  TORCH_CHECK_VALUE(parity == 0 || parity == 1, "compact_ids: parity is 0 or 1");
-  gnnrec_compact_type T[GNNREC_SB_MAX_TYPES] = {};
-  gnnrec_compact_list Ls[GNNREC_COMPACT_MAX_LISTS] = {};
-  const c10::DeviceGuard g(bits[0].device());
-  const auto i64 = bits[0].options();
-  std::vector<Tensor> nodes(NT), local(L);
-  for (size_t t = 0; t < NT; ++t) {
-    dev(bits[t], "bits", at::kLong);
-    dev(word_rank[t], "word_rank", at::kLong);
-    const int64_t W = (n_nodes[t] + 63) / 64;
-    dev(marks[t], "marks", at::kByte);
-    // bits: the two parity bitmaps, then the scan's workspace
-    const int64_t ws = GNNREC_COMPACT_SCAN_WS(n_nodes[t]);
-    TORCH_CHECK_VALUE(n_nodes[t] >= 0 && caps[t] >= 0 && bits[t].numel() == 2 * W + ws &&
-                          word_rank[t].numel() == W + 1 && marks[t].numel() == 2 * 64 * W,
-                      "compact_ids: type ", t, ": scratch sized 2 ceil(n/64) + ", ws,
-                      ", ceil(n/64)+1, 128 ceil(n/64) bytes");
-    nodes[t] = at::empty({caps[t]}, i64);
-    T[t] = gnnrec_compact_type{n_nodes[t], p<uint64_t>(bits[t]), p<int64_t>(word_rank[t]),
-                               p<int64_t>(nodes[t]), caps[t], p<uint8_t>(marks[t]),
-                               p<uint64_t>(bits[t]) + 2 * W};
-  }
-  // the lists' local ids are consecutive views of one buffer (lists given one after the
-  // other, e.g. an etype's positive then negative sources, come back joined)
-  int64_t n_all = 0;
-  for (size_t l = 0; l < L; ++l) n_all += ids[l].numel();
-  const Tensor local_all = at::empty({n_all}, i64);
-  int64_t off = 0;
-  for (size_t l = 0; l < L; ++l) {
-    dev(ids[l], "ids", at::kLong);
-    TORCH_CHECK_VALUE(type[l] >= 0 && (size_t)type[l] < NT && ids[l].is_contiguous(),
-                      "compact_ids: list ", l, ": type out of range or ids not contiguous");
-    local[l] = local_all.narrow(0, off, ids[l].numel());
-    off += ids[l].numel();
-    Ls[l] = gnnrec_compact_list{p<int64_t>(ids[l]), ids[l].numel(), (int32_t)type[l],
-                                p<int64_t>(local[l])};
-  }
-  Tensor count = at::empty({(int64_t)NT}, i64);
-  ck(gnnrec_compact_ids(Ls, (int)L, T, (int)NT, (int)parity, p<int64_t>(count),
-                        stream_of(bits[0])),
-     "gnnrec_compact_ids");
-  return {nodes, local, count};
-}
-
-// a12: many contiguous same-size copies dst[j] <- src[j] in one launch per 64
-// (gnnrec_copy_batch: a static batch into a captured step's buffers, gnnrec/capture.py)
-void copy_batch(at::TensorList src, at::TensorList dst) {
-  const OneDevice one_device_;
-  TORCH_CHECK_VALUE(src.size() == dst.size(), "copy_batch: one dst per src");
-  std::vector<const void*> sp;
-  std::vector<void*> dp;
-  std::vector<int64_t> nb;
-  for (size_t j = 0; j < src.size(); ++j) {
-    TORCH_CHECK_VALUE(src[j].is_cuda() && dst[j].is_cuda(),
-                      "copy_batch: device tensors (there is no CPU path)");
-    same_dev(src[j], "src");
-    same_dev(dst[j], "dst");
-    TORCH_CHECK_VALUE(src[j].scalar_type() == dst[j].scalar_type() &&
-                          src[j].sizes() == dst[j].sizes() && src[j].is_contiguous() &&
-                          dst[j].is_contiguous(),
-                      "copy_batch: job ", j, ": contiguous tensors of one dtype and shape");
-    sp.push_back(src[j].data_ptr());
-    dp.push_back(dst[j].data_ptr());
-    nb.push_back(src[j].nbytes());
-  }
-  if (src.empty()) return;
-  const c10::DeviceGuard g(src[0].device());
-  for (size_t i = 0; i < sp.size(); i += GNNREC_COPY_MAX_JOBS) {
-    const int n = (int)std::min<size_t>(GNNREC_COPY_MAX_JOBS, sp.size() - i);
-    ck(gnnrec_copy_batch(sp.data() + i, dp.data() + i, nb.data() + i, n, stream_of(src[0])),
-       "gnnrec_copy_batch");
-  }
-}
-
-// EdgeDataLoader's batch head in one call (gnnrec/sampling.py _iter_batches): the batch's
-// positive pairs (find_edges), the uniform negatives (src repeated K times, dst =
-// randint(N_dst) from the default generator — the same draws as negative_sampler.Uniform),
-// and DGL's compact_graphs([pos, neg]) over both (relabel per node type, ONE size
-// readback), returning every pair list in local ids.  The same kernels, generator calls and
-// order as the Python form it replaces (bitwise the same pair graphs), issued from C++ with
-// the GIL released, so a prefetching loader thread leaves the training thread alone.
-//   batch[r]: edge ids of relation r in the batch (empty: not in it); neg_order: the
-//   relations in the order their negatives are drawn (the batch's type order)
-std::tuple<std::vector<Tensor>, std::vector<Tensor>, std::vector<Tensor>, std::vector<Tensor>,
-           std::vector<Tensor>>
-edge_batch_pairs(at::TensorList rel_src, at::TensorList rel_dst, at::IntArrayRef src_type,
-                 at::IntArrayRef dst_type, at::TensorList batch, at::IntArrayRef neg_order,
-                 int64_t K, at::IntArrayRef n_nodes, at::TensorList prefix_pos,
-                 at::TensorList marks) {
-  const OneDevice one_device_;
-  const size_t R = rel_src.size(), NT = n_nodes.size();
-  TORCH_CHECK_VALUE(rel_dst.size() == R && src_type.size() == R && dst_type.size() == R &&
-                        batch.size() == R && prefix_pos.size() == NT && marks.size() == NT &&
-                        NT > 0,
-                    "edge_batch_pairs: list lengths");
-  for (size_t r = 0; r < R; ++r)
-    TORCH_CHECK_VALUE(src_type[r] >= 0 && (size_t)src_type[r] < NT && dst_type[r] >= 0 &&
-                          (size_t)dst_type[r] < NT,
-                      "edge_batch_pairs: node-type index out of range");
-  const c10::DeviceGuard g(prefix_pos[0].device());
-  const auto opt = prefix_pos[0].options();  // int64 on the device
-  const Tensor empty = at::empty({0}, opt);
-  std::vector<Tensor> ps(R, empty), pd(R, empty), ns(R, empty), nd(R, empty);
-  for (size_t r = 0; r < R; ++r) {
-    if (batch[r].numel() == 0) continue;
-    ps[r] = rel_src[r].index_select(0, batch[r]);
-    pd[r] = rel_dst[r].index_select(0, batch[r]);
-  }
-  if (K > 0) {
-    for (int64_t r : neg_order) {
-      TORCH_CHECK_VALUE(r >= 0 && (size_t)r < R, "edge_batch_pairs: neg_order out of range");
-      if (batch[r].numel() == 0) continue;
-      ns[r] = ps[r].repeat_interleave(K);
-      nd[r] = at::randint(0, n_nodes[dst_type[r]], {ns[r].numel()}, opt);
-    }
-  }
-  // compact_graphs([pos, neg]): per node type the lists in (pos, neg) x relation order
-  std::vector<std::vector<Tensor*>> lists(NT);
-  for (auto* side : {&ps, &ns})
-    for (size_t r = 0; r < R; ++r) {
-      lists[src_type[r]].push_back(&(*side)[r]);
-      auto& dlist = side == &ps ? pd : nd;
-      lists[dst_type[r]].push_back(&dlist[r]);
-    }
-  // a relation's positive and negative local ids of one side are written into one buffer
-  // [positives | negatives]: the cosine backward then joins them as a view, not a cat
-  std::map<const Tensor*, Tensor> joined_out;
-  for (size_t r = 0; r < R; ++r)
-    for (auto side : {std::make_pair(&ps[r], &ns[r]), std::make_pair(&pd[r], &nd[r])}) {
-      const int64_t a = side.first->numel(), b = side.second->numel();
-      if (a == 0 || b == 0) continue;
-      const Tensor buf = at::empty({a + b}, opt);
-      joined_out[side.first] = buf.narrow(0, 0, a);
-      joined_out[side.second] = buf.narrow(0, a, b);
-    }
-  std::vector<Tensor> rank(NT);
-  for (size_t t = 0; t < NT; ++t) {
-    Tensor pp = prefix_pos[t], mk = marks[t];
-    set_prefix_pos(empty, pp);
-    for (Tensor* ids : lists[t]) mark_ids(*ids, pp, mk);
-    rank[t] = exclusive_scan_new(mk);
-  }
-  std::vector<Tensor> last;
-  for (size_t t = 0; t < NT; ++t) last.push_back(rank[t].narrow(0, rank[t].numel() - 1, 1));
-  const Tensor n_new = at::cat(last).to(at::kCPU);  // the one size readback
-  std::vector<Tensor> nodes(NT);
-  for (size_t t = 0; t < NT; ++t) {
-    const int64_t nn = n_new.data_ptr<int64_t>()[t];
-    Tensor pp = prefix_pos[t], mk = marks[t];
-    nodes[t] = at::empty({nn}, opt);
-    if (nn) compact_marked(mk, rank[t], nodes[t]);
-    for (Tensor* ids : lists[t]) {
-      const auto j = joined_out.find(ids);
-      Tensor loc = j != joined_out.end() ? j->second : at::empty({ids->numel()}, opt);
-      relabel_ids(*ids, pp, rank[t], 0, loc);
-      *ids = loc;  // the list entry becomes its local ids
-    }
-    clear_prefix_pos(empty, pp);
-    if (nn) mk.index_fill_(0, nodes[t], 0);
-  }
-  return {nodes, ps, pd, ns, nd};
 }
 
 // ---------------------------------------------------------------- host-only queries
@@ -2170,18 +1294,6 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor b3, Tensor(a!) out) -> ()");
   m.def("edge_mlp_grouped(Tensor src_g, Tensor? first, int K, Tensor dst, Tensor P, Tensor Q, "
         "Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor(a!) out_first, Tensor(b!) out) -> ()");
-  m.def("sample_count(Tensor indptr, Tensor eids, Tensor? excluded, Tensor seeds, int fanout, "
-        "int seed_key, Tensor(a!) counts, Tensor? excluded_rows=None) -> ()");
-  m.def("sample_fill(Tensor indptr, Tensor indices, Tensor eids, Tensor? excluded, Tensor seeds, "
-        "int fanout, int seed_key, Tensor out_indptr, Tensor(a!) out_src, Tensor(b!) out_eid, "
-        "Tensor? excluded_rows=None) -> ()");
-  m.def("exclusive_scan(Tensor x, Tensor(a!) out, Tensor(b!) workspace) -> ()");
-  m.def("mark_ids(Tensor ids, Tensor prefix_pos, Tensor(a!) mark) -> ()");
-  m.def("relabel_ids(Tensor ids, Tensor prefix_pos, Tensor rank, int n_prefix, "
-        "Tensor(a!) local) -> ()");
-  m.def("compact_marked(Tensor mark, Tensor rank, Tensor(a!) out_ids) -> ()");
-  m.def("set_prefix_pos(Tensor prefix, Tensor(a!) prefix_pos) -> ()");
-  m.def("clear_prefix_pos(Tensor prefix, Tensor(a!) prefix_pos) -> ()");
   m.def("topk_rows(Tensor scores, int k, Tensor? exclude_indptr, Tensor? exclude_indices, "
         "Tensor(a!) out_vals, Tensor(b!) out_idx) -> ()");
   m.def("gemm_tn(Tensor A, Tensor B, Tensor(b!)? colsum, bool accumulate, Tensor(a!) out, "
@@ -2208,7 +1320,6 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor(b!) dc_prev) -> ()");
   m.def("lstm_slots(Tensor indptr, Tensor indices, Tensor order, Tensor step_off, int n_slots, "
         "Tensor(a!) src, Tensor(b!) prev) -> ()");
-  m.def("gather_rows(Tensor src, Tensor idx, Tensor(a!) out) -> ()");
   m.def("csr_has_edges(Tensor indptr, Tensor sorted_indices, int n_src, Tensor u, Tensor v, "
         "Tensor(a!) out) -> ()");
   m.def("sage_rel_forward(Tensor m, Tensor h_self, int n_self, Tensor W_self, Tensor W_neigh, "
@@ -2223,33 +1334,12 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor? live_src=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("block_transposes(Tensor[] indptrs, Tensor[] indices, int[] n_src, int[] nnz) "
         "-> (Tensor[], Tensor[], Tensor[])");
-  m.def("edge_batch_pairs(Tensor[] rel_src, Tensor[] rel_dst, int[] src_type, int[] dst_type, "
-        "Tensor[] batch, int[] neg_order, int K, int[] n_nodes, Tensor[] prefix_pos, "
-        "Tensor[] marks) -> (Tensor[], Tensor[], Tensor[], Tensor[], Tensor[])");
   m.def("margin_loss(Tensor pos, Tensor neg, int K, float delta, Tensor? mask, Tensor? recency, "
         "Tensor(a!) g_pos, Tensor(b!) g_neg, Tensor(c!) partial) -> ()");
   m.def("sum_scaled(Tensor x, float scale, Tensor(a!) out) -> ()");
   m.def("synth_edges(int seed, int e0, int n_u, int n_i, Tensor? zipf_cdf, Tensor(a!) u, "
         "Tensor(b!) i) -> ()");
   m.def("hold_cus(int blocks, int threads, int lds_bytes, int usec, Tensor(a!) sink) -> ()");
-  m.def("sample_layer(Tensor[] indptrs, Tensor[] indices, Tensor[] eids, Tensor?[] masks, "
-        "Tensor?[] mask_rows, int[] src_type, int[] dst_type, int[] fanouts, int[] keys, Tensor[] seeds, "
-        "Tensor(a!)[] prefix_pos, Tensor(b!)[] marks) -> "
-        "(Tensor[] out_indptr, Tensor[] src_local, Tensor[] eids, Tensor[] src_nid, int[] n_edges)");
-  m.def("sample_blocks(Tensor[] indptrs, Tensor[] indices, Tensor[] eids, int[] src_type, "
-        "int[] dst_type, Tensor?[] excl_eids, Tensor?[] coo_dst, Tensor?[] excl_masks, "
-        "Tensor?[] excl_rows, int[] n_nodes, Tensor[] seeds, Tensor(a!)[] pos, "
-        "Tensor(b!)[] bits, Tensor(c!)[] word_rank, Tensor(f!)[] marks, int[] fanouts, "
-        "int[] keys, int steps, "
-        "int stamp, bool static_shapes, Tensor(d!)? sizes_out, int[] node_cap_hint, "
-        "Tensor(e!)? overflow, Tensor[] edge_tables, int[] edge_table_rel, Tensor[] node_tables, "
-        "int[] node_table_type, Tensor[] edge_recs) -> (Tensor[] out_indptr, Tensor[] src_local, Tensor[] eids, "
-        "Tensor[] src_nid, int[] sizes, Tensor[] data)");
-  m.def("gather_rows_batch(Tensor[] src, Tensor[] idx, Tensor(a!)[] out, Tensor[] n_dev) -> ()");
-  m.def("copy_batch(Tensor[] src, Tensor(a!)[] dst) -> ()");
-  m.def("compact_ids(Tensor[] ids, int[] type, int[] n_nodes, int[] caps, Tensor(a!)[] bits, "
-        "Tensor(b!)[] word_rank, Tensor(c!)[] marks, int parity) -> (Tensor[] nodes, "
-        "Tensor[] local, Tensor count)");
   // host-only entry points (no tensors: one catch-all kernel each)
   m.def("version() -> int", &version);
   m.def("set_concurrency(int reserve_cus, bool dynamic) -> ()", &set_concurrency);
@@ -2285,14 +1375,6 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("sddmm_cos_backward", &sddmm_cos_backward);     \
   m.impl("edge_mlp", &edge_mlp);                         \
   m.impl("edge_mlp_grouped", &edge_mlp_grouped);         \
-  m.impl("sample_count", &sample_count);                 \
-  m.impl("sample_fill", &sample_fill);                   \
-  m.impl("exclusive_scan", &exclusive_scan);             \
-  m.impl("mark_ids", &mark_ids);                         \
-  m.impl("relabel_ids", &relabel_ids);                   \
-  m.impl("compact_marked", &compact_marked);             \
-  m.impl("set_prefix_pos", &set_prefix_pos);             \
-  m.impl("clear_prefix_pos", &clear_prefix_pos);         \
   m.impl("topk_rows", &topk_rows);                       \
   m.impl("gemm_tn", &gemm_tn);                           \
   m.impl("act_backward", &act_backward);                 \
@@ -2306,8 +1388,6 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("lstm_step_save", &lstm_step_save);             \
   m.impl("lstm_backward_step", &lstm_backward_step);     \
   m.impl("lstm_slots", &lstm_slots);                     \
-  m.impl("gather_rows", &gather_rows);                   \
-  m.impl("gather_rows_batch", &gather_rows_batch);       \
   m.impl("csr_has_edges", &csr_has_edges);               \
   m.impl("sage_rel_forward", &sage_rel_forward);         \
   m.impl("sage_rel_backward", &sage_rel_backward);       \
@@ -2318,14 +1398,7 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("hold_cus", &hold_cus)
 
 // HIP tensors dispatch under the CUDA key in ROCm PyTorch.
-TORCH_LIBRARY_IMPL(gnnrec, CUDA, m) {
-  GNNREC_IMPLS(m);
-  m.impl("sample_layer", &sample_layer);  // data-dependent sizes: device only, no meta form
-  m.impl("edge_batch_pairs", &edge_batch_pairs);
-  m.impl("sample_blocks", &sample_blocks);
-  m.impl("compact_ids", &compact_ids);
-  m.impl("copy_batch", &copy_batch);
-}
+TORCH_LIBRARY_IMPL(gnnrec, CUDA, m) { GNNREC_IMPLS(m); }
 // Meta / fake tensors (torch.compile tracing): the same functions stop after their checks.
 TORCH_LIBRARY_IMPL(gnnrec, Meta, m) { GNNREC_IMPLS(m); }
 // CPU tensors: the same functions refuse them in their first operand check (ValueError:

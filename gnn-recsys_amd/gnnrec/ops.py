@@ -9,6 +9,7 @@ capture.  There is no fallback: a missing library or a CPU tensor is an error.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import os
 
@@ -1322,6 +1323,30 @@ class SampleScratch:
         self.marks = torch.zeros(4 * 64 * w, dtype=torch.uint8, device=device)
 
 
+SampleSizes = collections.namedtuple("SampleSizes", "nodes edges dump")
+
+
+def sample_sizes(flat, L: int, T: int, R: int, dump: bool = True) -> SampleSizes:
+    """The fused sampler's sizes of L steps (step 0 = the output block), T node types and R
+    relations, from gnnrec::sample_blocks' flat layout — a list of ints, or a device tensor
+    (one-entry views): nodes[0][t] the seeds and nodes[s + 1][t] step s's source nodes (so
+    step s has nodes[s][t] destinations), edges[s][r], then dump[s][t], the dump rows after
+    step s's destination rows (static shapes; zero otherwise; dump=False: flat has none)."""
+    if len(flat) != (L + 1) * T + L * R + (L * T if dump else 0):
+        raise ValueError(f"sample_sizes: {len(flat)} entries for {(L, T, R)} steps, types, rels")
+    at = (lambda i: flat.narrow(0, i, 1)) if torch.is_tensor(flat) else flat.__getitem__
+    rows = iter(range(len(flat)))  # the entries in order: no offsets to keep in step
+    return SampleSizes([[at(next(rows)) for _ in range(T)] for _ in range(L + 1)],
+                       [[at(next(rows)) for _ in range(R)] for _ in range(L)],
+                       [[at(next(rows)) for _ in range(T)] for _ in range(L)] if dump else [])
+
+
+def sample_sizes_out(L: int, T: int, R: int, device):
+    """A static sample_blocks call's sizes_out, and its entries as one-entry device views."""
+    flat = torch.empty((L + 1) * T + L * R, dtype=torch.int64, device=device)
+    return flat, sample_sizes(flat, L, T, R, dump=False)
+
+
 def sample_blocks(indptrs, indices, eids, src_type, dst_type, excl, n_nodes, seeds, scratch,
                   fanouts, keys, stamp, static_shapes=False, sizes_out=None, node_cap_hint=None,
                   overflow=None, edge_tables=(), node_tables=(), edge_recs=()):
@@ -1329,22 +1354,23 @@ def sample_blocks(indptrs, indices, eids, src_type, dst_type, excl, n_nodes, see
     1 + 3L launches, one host size read).  fanouts / keys: [step][relation] (step 0 = the
     output block); excl: per relation None or (eids, coo_dst, mask, rows).
     -> per step: ([out_indptr], [local src int32], [eids]) per relation, [src node ids] per
-    type, and the sizes (node counts rows -1..L-1 x types, then edge counts).
+    type; the sizes (SampleSizes); the gathered block data.
     static_shapes: every output at its capacity, no host read (the -1-padded layout of
-    include/gnnrec.h); the sizes are then the capacities (seed caps, node caps, edge caps).
-    sizes_out (int64 device tensor of the sizes' length): the exact outputs at their
-    capacities and the sizes left there, not read back — the caller queues work sized by
-    them on the device (gather_rows_batch's n_dev) before it reads them itself; the returned
-    sizes are the capacities then too.  node_cap_hint ([step][type], static): tighter node
-    capacities than the provable ones; a batch that does not fit sets `overflow` (int64
-    device flag) and must be discarded or redone.
+    include/gnnrec.h); the sizes returned are then the capacities, and the actual ones are
+    left on the device in sizes_out (int64, the flat layout of sample_sizes without the dump
+    rows), which is given exactly when static_shapes is.  node_cap_hint ([step][type],
+    static): tighter node capacities than the provable ones; a batch that does not fit sets
+    `overflow` (int64 device flag) and must be discarded or redone.
     edge_tables [(table, relation)] / node_tables [(table, node type)]: the block data (a10),
-    gathered inside the call — every step's edge data at its edge ids, the input block's
-    (the last step's) node rows at its source ids — returned as a third value in that order
-    (step-major for the edge tables).  edge_recs: per relation the packed {eid << 32 | src}
-    records of its CSR (HeteroGraph.edge_records), or empty (the index / eid arrays)."""
-    steps, R = len(fanouts), len(indptrs)
-    ex = [e if e is not None else (None,) * 4 for e in excl]
+    gathered inside an exact call (never a static one) — every step's edge data at its edge
+    ids, the input block's (the last step's) node rows at its source ids — returned as a
+    third value in that order (step-major for the edge tables).  edge_recs: per relation the
+    packed {eid << 32 | src} records of its CSR (HeteroGraph.edge_records), or empty (the
+    index / eid arrays)."""
+    steps, R, NT = len(fanouts), len(indptrs), len(n_nodes)
+    if (sizes_out is not None) != bool(static_shapes):
+        raise ValueError("sample_blocks: sizes_out goes with static_shapes, and only with it")
+    ex =[e if e is not None else (None,) * 4 for e in excl]
     o_ip, o_src, o_eid, nodes, sizes, data = _T().sample_blocks(
         list(indptrs), list(indices), list(eids), list(src_type), list(dst_type),
         [e[0] for e in ex], [e[1] for e in ex], [e[2] for e in ex], [e[3] for e in ex],
@@ -1355,12 +1381,9 @@ def sample_blocks(indptrs, indices, eids, src_type, dst_type, excl, n_nodes, see
         sizes_out, [int(h) for hs in (node_cap_hint or []) for h in hs], overflow,
         [t for t, _ in edge_tables], [int(r) for _, r in edge_tables],
         [t for t, _ in node_tables], [int(x) for _, x in node_tables], list(edge_recs))
-    NT = len(n_nodes)
-    out = []
-    for s in range(steps):
-        out.append(([o_ip[s * R + r] for r in range(R)], [o_src[s * R + r] for r in range(R)],
-                    [o_eid[s * R + r] for r in range(R)], [nodes[s * NT + t] for t in range(NT)]))
-    return out, sizes, data
+    out = [(o_ip[s * R:(s + 1) * R], o_src[s * R:(s + 1) * R], o_eid[s * R:(s + 1) * R],
+            nodes[s * NT:(s + 1) * NT]) for s in range(steps)]
+    return out, sample_sizes(sizes, steps, NT, R), data
 
 
 class CompactScratch:

@@ -69,9 +69,6 @@ class BlockSampler:
         # .edge_records) when every eid fits 31 bits; False: the index and eid arrays
         # (bitwise the same blocks; tests compare the two)
         self.packed = True
-        # static-shape blocks hold their block data as LazyRows (gathered when read); False:
-        # gathered by the sampler call like the exact blocks' (the same values)
-        self.lazy_static_data = True
         self._sb_scratch = {}
         self._stamp = 1
         # the first block's source-major CSRs (sample_blocks(transposes=True)) are skipped
@@ -173,19 +170,17 @@ class BlockSampler:
         fans = [[self._fanout(L - 1 - s, ce) for ce in ces] for s in range(L)]
         keys = [[_mix(self.seed, self._calls, L - 1 - s, r) for r in range(len(ces))]
                 for s in range(L)]
-        NT, R = len(nts), len(ces)
         # the block data (DGL copies it at block creation; the reference reads
-        # blocks[0].srcdata['features']) is gathered inside the call, behind the sampler and
-        # ahead of its one size read; static: -1 ids -> zero rows
+        # blocks[0].srcdata['features']) is gathered inside an exact call, behind the sampler
+        # and ahead of its one size read
         etab = [(ce, k, v if v.dim() < 2 or v[0].is_contiguous() else v.contiguous())
                 for ce in ces for k, v in g._edata[ce].items()]
         ntab = [(nt, k, v if v.dim() < 2 or v[0].is_contiguous() else v.contiguous())
                 for nt in nts for k, v in g._ndata[nt].items()]
-        lazy = static and self.lazy_static_data
-        # static: the real counts stay on the device (sizes_out: [L + 1][T] node counts, the
-        # seed counts first, then [L][R] edge counts) and drive the kernels over the blocks
-        dsz = torch.empty((L + 1) * len(nts) + L * len(ces), dtype=torch.int64,
-                          device=g.device) if static else None
+        # static: the real counts stay on the device (sizes_out) and drive the kernels over
+        # the blocks; `live` holds them as one-entry views
+        dsz, live = ops.sample_sizes_out(L, len(nts), len(ces), g.device) if static \
+            else (None, None)
         steps, sizes, data = ops.sample_blocks(
             [c[0] for c in csrs], [c[1] for c in csrs], [c[2] for c in csrs],
             [tix[ce[0]] for ce in ces], [tix[ce[2]] for ce in ces], excl,
@@ -193,30 +188,18 @@ class BlockSampler:
             fans, keys, stamp, static_shapes=static, sizes_out=dsz,
             node_cap_hint=[[(hints or {}).get((s_, nt), 0) for nt in nts] for s_ in range(L)]
             if hints else None, overflow=overflow,
-            # static: the block data is left to LazyRows (gathered when read: inside a
-            # captured step's graph, from its captured ids), not gathered here
-            edge_tables=[] if lazy else [(v, ces.index(ce)) for ce, _k, v in etab],
-            node_tables=[] if lazy else [(v, tix[nt]) for nt, _k, v in ntab],
+            edge_tables=[] if static else [(v, ces.index(ce)) for ce, _k, v in etab],
+            node_tables=[] if static else [(v, tix[nt]) for nt, _k, v in ntab],
             edge_recs=self._edge_recs(g, ces))
         blocks = []
         for s_, (o_ip, src_loc, o_eid, nodes) in enumerate(steps):
             rels = {}
             for r, ce in enumerate(ces):
-                ip, loc, eid = o_ip[r], src_loc[r], o_eid[r]
-                if static:  # sizes = seed caps, node caps [L x T], edge caps [L x R], dump rows
-                    ip._gnnrec_nnz = int(sizes[NT + L * NT + s_ * R + r])
-                    if 0 <= fans[s_][r] <= ops.DEFAULT_SPLIT:  # dump rows: <= 2048 edges
-                        ip._gnnrec_split_plan = (ops.DEFAULT_SPLIT, None)
-                else:
-                    ip._gnnrec_nnz = int(sizes[(L + 1) * NT + s_ * R + r])
-                    if 0 <= fans[s_][r] <= ops.DEFAULT_SPLIT:
-                        ip._gnnrec_split_plan = (ops.DEFAULT_SPLIT, None)  # no heavy rows
-                rels[ce] = (ip, loc, eid)
-            if static:
-                dump = [int(sizes[NT + L * NT + L * R + s_ * NT + t]) for t in range(NT)]
-                num_dst = {nt: int(sizes[s_ * NT + t]) + dump[t] for t, nt in enumerate(nts)}
-            else:
-                num_dst = {nt: int(sizes[s_ * NT + t]) for t, nt in enumerate(nts)}
+                # (static: the capacity; the dump rows hold at most 2048 edges each)
+                _tag_csr(o_ip[r], sizes.edges[s_][r], fans[s_][r])
+                rels[ce] = (o_ip[r], src_loc[r], o_eid[r])
+            # static: the seed slots, then the dump rows (exact: there are none)
+            num_dst = {nt: sizes.nodes[s_][t] + sizes.dump[s_][t] for t, nt in enumerate(nts)}
             b = Block(dict(zip(nts, nodes)), num_dst, rels)
             if static:
                 # the destination ids are the step's seed slots (-1: padding rows, the dump
@@ -225,32 +208,22 @@ class BlockSampler:
                 # the real destination / source counts (device): the aggregation gathers the
                 # real rows only, and the backward's transposed gathers the real sources
                 for t, nt in enumerate(nts):
-                    b._live[('dst', nt)] = dsz.narrow(0, s_ * NT + t, 1)
-                    b._live[('src', nt)] = dsz.narrow(0, (s_ + 1) * NT + t, 1)
+                    b._live[('dst', nt)] = live.nodes[s_][t]
+                    b._live[('src', nt)] = live.nodes[s_ + 1][t]
+                    b._dst[nt][NID] = steps[s_ - 1][3][t] if s_ else torch.cat(
+                        [seeds.get(nt, empty), empty.new_full((sizes.dump[0][t],), -1)])
                 for ce in ces:
                     rels[ce][0]._gnnrec_live = b._live[('dst', ce[2])]
-                for t, nt in enumerate(nts):
-                    if s_ == 0:
-                        dst_ids = torch.cat([seeds.get(nt, empty),
-                                             empty.new_full((dump[t],), -1)])
-                    else:
-                        dst_ids = steps[s_ - 1][3][t]
-                    b._dst[nt][NID] = dst_ids
             blocks.insert(0, b)
-        if lazy:  # -1 ids (padding edges / source slots) read as zero rows
-            for b in blocks:
-                for ce, k, v in etab:
-                    b._edata[ce][k] = LazyRows(v, b._rels[ce][2])
-            for nt, k, v in ntab:
-                blocks[0]._src[nt][k] = LazyRows(v, blocks[0]._src[nt][NID])
-        else:
-            it = iter(data)
-            for s_ in range(L):
-                b = blocks[L - 1 - s_]
-                for ce, k, _v in etab:
-                    b._edata[ce][k] = next(it)
-            for nt, k, _v in ntab:
-                blocks[0]._src[nt][k] = next(it)
+        # exact: the call's gathers, in step order; static: LazyRows, gathered when read (inside
+        # a captured step's graph, from its captured ids; -1 ids — padding edges / source
+        # slots — read as zero rows)
+        it = iter(data)
+        for b in reversed(blocks):
+            for ce, k, v in etab:
+                b._edata[ce][k] = LazyRows(v, b._rels[ce][2]) if static else next(it)
+        for nt, k, v in ntab:
+            blocks[0]._src[nt][k] = LazyRows(v, blocks[0]._src[nt][NID]) if static else next(it)
         if transposes:
             for block_id, b in enumerate(blocks):
                 if block_id > 0 or self._first_transposes(b):
@@ -335,11 +308,8 @@ class BlockSampler:
             mask_rows=[masks.get(ce, (None, None, None))[2] for ce in ces])
         rels = {}
         for r, ce in enumerate(ces):
-            ip = o_ip[r]
-            ip._gnnrec_nnz = int(totals[r])  # edge count known on the host: no later readback
-            if fans[r] is not None and 0 <= fans[r] <= ops.DEFAULT_SPLIT:
-                ip._gnnrec_split_plan = (ops.DEFAULT_SPLIT, None)  # no heavy rows possible
-            rels[ce] = (ip, src_loc[r], o_eid[r])
+            _tag_csr(o_ip[r], totals[r], fans[r])
+            rels[ce] = (o_ip[r], src_loc[r], o_eid[r])
         num_dst = {nt: int(seeds.get(nt, empty).numel()) for nt in nts}
         return Block(dict(zip(nts, src_nid)), num_dst, rels)
 
@@ -361,9 +331,7 @@ class BlockSampler:
         for (ce, indptr, indices, eids, dseeds, fan, key, mask, o_ip), tot in zip(plan, totals):
             o_src, o_eid = ops.sample_fill(indptr, indices, eids, dseeds, fan, key, o_ip, tot,
                                            *mask)
-            o_ip._gnnrec_nnz = int(tot)  # edge count known on the host: no later readback
-            if fan is not None and 0 <= fan <= ops.DEFAULT_SPLIT:
-                o_ip._gnnrec_split_plan = (ops.DEFAULT_SPLIT, None)  # no heavy rows possible
+            _tag_csr(o_ip, tot, fan)
             rels[ce] = [o_ip, o_src, o_eid]
             src_lists.setdefault(ce[0], []).append(ce)
         prefixes, ranks = {}, {}
@@ -382,6 +350,14 @@ class BlockSampler:
             for ce, loc in zip(ces, locs):
                 rels[ce][1] = loc.to(torch.int32)
         return Block(src_nid, num_dst, {ce: tuple(v) for ce, v in rels.items()})
+
+
+def _tag_csr(indptr, nnz, fanout=None) -> None:
+    """Left on a block CSR's indptr for ops / autograd: its edge count (known on the host: no
+    later readback) and, under a fanout <= DEFAULT_SPLIT, that no row is heavy (no plan)."""
+    indptr._gnnrec_nnz = int(nnz)
+    if fanout is not None and 0 <= fanout <= ops.DEFAULT_SPLIT:
+        indptr._gnnrec_split_plan = (ops.DEFAULT_SPLIT, None)
 
 
 def _copy_block_data(g, blocks) -> None:
@@ -417,7 +393,7 @@ def _add_transposes(block: Block) -> None:
         [block.number_of_src_nodes(ce[0]) for ce in ces],
         [ops._nnz(block._rels[ce][0]) for ce in ces])
     for ce, ip, ix, w in zip(ces, ips, ixs, ws):
-        ip._gnnrec_nnz = ops._nnz(block._rels[ce][0])
+        _tag_csr(ip, ops._nnz(block._rels[ce][0]))
         live = block._live.get(('src', ce[0]))
         if live is not None:  # a static block: its real sources (rows past them are padding)
             ip._gnnrec_live = live
