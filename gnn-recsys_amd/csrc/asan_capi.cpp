@@ -144,9 +144,42 @@ static void sampler_plans() {
   CHECK(gnnrec_sample_blocks(&P, nullptr) == GNNREC_EINVAL && err_has("stamp"), "stamp wrap");
 }
 
+// the dropout mask's host routine writes exactly n_rows x d bytes (exact-size buffers: a
+// write past them is an ASan report), for widths that are and are not multiples of 4
+static void dropout_mask() {
+  for (const int64_t d : {1, 6, 64, 130}) {
+    std::vector<uint8_t> keep((size_t)(37 * d), 2);
+    CHECK(gnnrec_dropout_mask_host(5, 1, 2, 37, d, 0.5, keep.data()) == GNNREC_OK, "mask");
+    size_t kept = 0;
+    for (const uint8_t k : keep) {
+      CHECK(k <= 1, "mask byte");
+      kept += k;
+    }
+    CHECK(d < 64 || (kept > keep.size() / 4 && kept < keep.size() * 3 / 4), "keep rate");
+    CHECK(gnnrec_dropout_mask_host(5, 1, 2, 37, d, 0.0, keep.data()) == GNNREC_OK, "p = 0");
+    for (const uint8_t k : keep) CHECK(k == 1, "p = 0 keeps everything");
+  }
+  CHECK(gnnrec_dropout_mask_host(5, 1, 2, 0, 64, 0.5, nullptr) == GNNREC_OK, "empty mask");
+  CHECK(gnnrec_dropout_mask_host(5, 1, 2, 4, 64, 1.5, nullptr) == GNNREC_EINVAL && err_has("p="),
+        "p range");
+  CHECK(gnnrec_dropout_scale(0.5) == 2.0f && gnnrec_dropout_scale(1.0) == 0.0f, "scale");
+  CHECK(gnnrec_dropout_keys(1, nullptr, 0, 4, nullptr, nullptr) == GNNREC_EINVAL, "keys null");
+  CHECK(gnnrec_dropout_rows_f32(nullptr, 4, 3, 4, nullptr, 0, 0.5, 0, nullptr, 4, nullptr) ==
+            GNNREC_EINVAL && err_has("null pointer"), "rows null");
+  CHECK(gnnrec_spmm_csr_dropout_live_f32(nullptr, nullptr, nullptr, nullptr, 4, 3, 4,
+                                         GNNREC_REDUCE_MAX, 0, nullptr, 4, nullptr, nullptr, 0,
+                                         0.5, GNNREC_DROPOUT_SRC, nullptr) == GNNREC_EINVAL &&
+            err_has("sum or mean"), "dropout gather reduce");
+  CHECK(gnnrec_spmm_csr_dropout_live_f32(nullptr, nullptr, nullptr, nullptr, 4, 0, 4,
+                                         GNNREC_REDUCE_SUM, 0, nullptr, 4, nullptr, nullptr, 0,
+                                         0.5, GNNREC_DROPOUT_OUT, nullptr) == GNNREC_OK,
+        "dropout gather empty");
+}
+
 int main() {
   validation();
   sampler_plans();
+  dropout_mask();
   std::fprintf(stderr, g_fail ? "asan_capi: FAILED\n" : "asan_capi: ok\n");
   return g_fail;
 }

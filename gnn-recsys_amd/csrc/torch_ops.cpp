@@ -707,14 +707,44 @@ Tensor row_degrees(const Tensor& indptr) {
 // gather of X over a CSR whose edge count is known on the host but whose degrees are
 // not (the transposed block, a static-shape block's dump row): heavy rows planned on the
 // device, as ops.spmm does
+//
+// drop (nullable): the gather with the dropout mask inside (csrc/dropout.hip), by gathered
+// row (GNNREC_DROPOUT_SRC) or at the store of the output row (GNNREC_DROPOUT_OUT)
+struct Drop {
+  const uint64_t* keys;
+  int64_t index;
+  double p;
+  int where;
+};
+
+// the keys tensor of a forward call (int64 storage of the uint64 keys) and one stream of it
+const uint64_t* drop_keys_ptr(const optional<Tensor>& keys, std::initializer_list<int64_t> idx) {
+  TORCH_CHECK_VALUE(has(keys), "dropout: p > 0 needs the keys tensor of the forward call");
+  dev(keys, "drop_keys", at::kLong);
+  TORCH_CHECK_VALUE(keys->is_contiguous(), "dropout: keys must be contiguous");
+  for (const int64_t i : idx)
+    TORCH_CHECK_VALUE(i >= 0 && i < keys->numel(), "dropout: stream ", i, " outside the ",
+                      keys->numel(), " keys");
+  return keys->is_meta() ? nullptr : reinterpret_cast<const uint64_t*>(keys->data_ptr());
+}
+
 void gather_planned(const Tensor& ip, const Tensor& ix, const Tensor& w, const Tensor& X,
                     int64_t nnz, Tensor& out, bool accumulate = false,
-                    int reduce = GNNREC_REDUCE_SUM, const int64_t* live = nullptr) {
+                    int reduce = GNNREC_REDUCE_SUM, const int64_t* live = nullptr,
+                    const Drop* drop = nullptr) {
   const int64_t n = ip.numel() - 1, d = X.size(1);
   const int64_t cap_h = std::min<int64_t>(n, nnz / (kSplit + 1));
   void* s = stream_of(X);
   const int flags = accumulate ? GNNREC_SPMM_ACCUM : 0;
   if (cap_h <= 0) {
+    if (drop) {
+      ck(gnnrec_spmm_csr_dropout_live_f32(p<int64_t>(ip), p<int32_t>(ix), pw(w), p<float>(X),
+                                          ld(X, "X"), n, d, reduce, flags, p<float>(out),
+                                          ld(out, "out"), live, drop->keys, drop->index, drop->p,
+                                          drop->where, s),
+         "gnnrec_spmm_csr_dropout_f32");
+      return;
+    }
     ck(gnnrec_spmm_csr_live_f32(p<int64_t>(ip), p<int32_t>(ix), pw(w), p<float>(X), ld(X, "X"), n,
                                 d, reduce, flags, p<float>(out), ld(out, "out"), live, s),
        "gnnrec_spmm_csr_f32");
@@ -726,13 +756,131 @@ void gather_planned(const Tensor& ip, const Tensor& ix, const Tensor& w, const T
                                  s),
      "gnnrec_spmm_plan_build");
   Tensor wsp = at::empty({cap_c, d}, X.options());
+  if (drop) {
+    ck(gnnrec_spmm_csr_planned_dropout_live_f32(
+           p<int64_t>(ip), p<int32_t>(ix), pw(w), p<float>(X), ld(X, "X"), n, d, reduce, flags,
+           p<float>(out), ld(out, "out"), kSplit, p<int64_t>(plan), cap_h, cap_c, p<float>(wsp),
+           live, drop->keys, drop->index, drop->p, drop->where, s),
+       "gnnrec_spmm_csr_planned_dropout_f32");
+    return;
+  }
   ck(gnnrec_spmm_csr_planned_live_f32(p<int64_t>(ip), p<int32_t>(ix), pw(w), p<float>(X),
                                       ld(X, "X"), n, d, reduce, flags, p<float>(out),
                                       ld(out, "out"), kSplit, p<int64_t>(plan), cap_h, cap_c,
                                       p<float>(wsp), live, s),
      "gnnrec_spmm_csr_planned_f32");
 }
+
+// x[:n] ⊙ mask · scale into out[:n] (stored, or added under accumulate); out may be x
+void drop_rows(const Tensor& x, int64_t n, const uint64_t* keys, int64_t index, double p_drop,
+               bool accumulate, Tensor& out) {
+  ck(gnnrec_dropout_rows_f32(p<float>(x), ld(x, "x"), n, x.size(1), keys, index, p_drop,
+                             (int)accumulate, p<float>(out), ld(out, "out"), stream_of(x)),
+     "gnnrec_dropout_rows_f32");
+}
 }  // namespace
+
+// ---------------------------------------------------------------- training dropout
+// keys[i] = hash3(seed, *counter, stream0 + i), then *counter += 1, in one launch
+void dropout_keys(int64_t seed, Tensor& counter, int64_t stream0, Tensor& keys) {
+  const OneDevice one_device_;
+  dev(counter, "counter", at::kLong);
+  dev(keys, "keys", at::kLong);
+  TORCH_CHECK_VALUE(counter.numel() == 1 && keys.is_contiguous() && stream0 >= 0,
+                    "dropout_keys: one counter, contiguous keys, stream0 >= 0");
+  if (meta(keys)) return;
+  const c10::DeviceGuard g(keys.device());
+  ck(gnnrec_dropout_keys((uint64_t)seed, p<int64_t>(counter), stream0, keys.numel(),
+                         reinterpret_cast<uint64_t*>(p<int64_t>(keys)), stream_of(keys)),
+     "gnnrec_dropout_keys");
+}
+
+void dropout_rows_f32(const Tensor& x, int64_t n, const Tensor& keys, int64_t key_index,
+                      double p_drop, bool accumulate, Tensor& out) {
+  const OneDevice one_device_;
+  dev(x, "x", at::kFloat);
+  dev(out, "out", at::kFloat);
+  TORCH_CHECK_VALUE(x.dim() == 2 && out.dim() == 2 && n >= 0 && x.size(0) >= n &&
+                        out.size(0) >= n && out.size(1) == x.size(1),
+                    "dropout_rows: x and out must hold n rows of one width");
+  const uint64_t* k = drop_keys_ptr(keys, {key_index});
+  ld(x, "x");
+  ld(out, "out");
+  if (meta(x)) return;
+  const c10::DeviceGuard g(x.device());
+  drop_rows(x, n, k, key_index, p_drop, accumulate, out);
+}
+
+// the sum / mean gathers with the dropout mask inside (gnnrec_spmm_csr_dropout_live_f32 and
+// its planned form): spmm_csr / spmm_csr_planned with the keys, the stream, p and the side
+void spmm_csr_dropout_live_f32(const Tensor& indptr, const Tensor& indices,
+                               const optional<Tensor>& ew, const Tensor& X, int64_t reduce,
+                               int64_t flags, Tensor& out, const optional<Tensor>& live,
+                               const Tensor& keys, int64_t key_index, double p_drop,
+                               int64_t where) {
+  const OneDevice one_device_;
+  dev(indptr, "indptr", at::kLong);
+  dev(indices, "indices", at::kInt);
+  dev(X, "X", at::kFloat);
+  dev(ew, "edge_weight", at::kFloat);
+  dev(out, "out", at::kFloat);
+  const int64_t n_dst = indptr.numel() - 1, d = X.size(1);
+  TORCH_CHECK_VALUE(out.size(0) == n_dst && out.size(1) == d, "out must be [", n_dst, ", ", d,
+                    "], got ", out.sizes());
+  const uint64_t* k = drop_keys_ptr(keys, {key_index});
+  const int64_t ldx = ld(X, "X"), ldo = ld(out, "out");
+  if (meta(X)) return;
+  const c10::DeviceGuard g(X.device());
+  ck(gnnrec_spmm_csr_dropout_live_f32(p<int64_t>(indptr), p<int32_t>(indices), p<float>(ew),
+                                      p<float>(X), ldx, n_dst, d, (int)reduce, (int)flags,
+                                      p<float>(out), ldo, live_ptr(live), k, key_index, p_drop,
+                                      (int)where, stream_of(X)),
+     "gnnrec_spmm_csr_dropout_f32");
+}
+
+void spmm_csr_planned_dropout_live_f32(const Tensor& indptr, const Tensor& indices,
+                                       const optional<Tensor>& ew, const Tensor& X,
+                                       int64_t reduce, int64_t flags, int64_t split,
+                                       const Tensor& plan, int64_t cap_h, int64_t cap_c,
+                                       Tensor& out, Tensor& ws, const optional<Tensor>& live,
+                                       const Tensor& keys, int64_t key_index, double p_drop,
+                                       int64_t where) {
+  const OneDevice one_device_;
+  dev(indptr, "indptr", at::kLong);
+  dev(indices, "indices", at::kInt);
+  dev(X, "X", at::kFloat);
+  dev(ew, "edge_weight", at::kFloat);
+  dev(plan, "plan", at::kLong);
+  dev(out, "out", at::kFloat);
+  dev(ws, "workspace", at::kFloat);
+  const int64_t n_dst = indptr.numel() - 1, d = X.size(1);
+  TORCH_CHECK_VALUE(out.size(0) == n_dst && out.size(1) == d, "out must be [", n_dst, ", ", d, "]");
+  TORCH_CHECK_VALUE(cap_h >= 0 && cap_c >= 0 && plan.numel() >= 3 + 2 * cap_h + cap_c,
+                    "plan shorter than 3 + 2 cap_h + cap_c");
+  TORCH_CHECK_VALUE(ws.numel() >= cap_c * d, "workspace must hold cap_c x d floats");
+  const uint64_t* k = drop_keys_ptr(keys, {key_index});
+  const int64_t ldx = ld(X, "X"), ldo = ld(out, "out");
+  if (meta(X)) return;
+  const c10::DeviceGuard g(X.device());
+  ck(gnnrec_spmm_csr_planned_dropout_live_f32(
+         p<int64_t>(indptr), p<int32_t>(indices), p<float>(ew), p<float>(X), ldx, n_dst, d,
+         (int)reduce, (int)flags, p<float>(out), ldo, split, p<int64_t>(plan), cap_h, cap_c,
+         p<float>(ws), live_ptr(live), k, key_index, p_drop, (int)where, stream_of(X)),
+     "gnnrec_spmm_csr_planned_dropout_f32");
+}
+
+// host only: the keep mask as a CPU uint8 tensor [n_rows, d], and the scale of p
+Tensor dropout_mask_host(int64_t seed, int64_t step, int64_t stream, int64_t n_rows, int64_t d,
+                         double p_drop) {
+  TORCH_CHECK_VALUE(n_rows >= 0 && d >= 0, "dropout_mask_host: negative size");
+  Tensor keep = at::empty({n_rows, d}, at::TensorOptions().dtype(at::kByte));
+  ck(gnnrec_dropout_mask_host((uint64_t)seed, (uint64_t)step, (uint64_t)stream, n_rows, d, p_drop,
+                              keep.data_ptr<uint8_t>()),
+     "gnnrec_dropout_mask_host");
+  return keep;
+}
+
+double dropout_scale(double p_drop) { return gnnrec_dropout_scale(p_drop); }
 
 std::tuple<Tensor, Tensor, Tensor> sage_rel_forward(const Tensor& m, const Tensor& h_self,
                                                     int64_t n_self, const Tensor& Ws,
@@ -741,7 +889,9 @@ std::tuple<Tensor, Tensor, Tensor> sage_rel_forward(const Tensor& m, const Tenso
                                                     const optional<Tensor>& ew, int64_t reduce,
                                                     bool norm, const optional<Tensor>& bias,
                                                     const optional<Tensor>& bias_ne,
-                                                    const optional<Tensor>& live) {
+                                                    const optional<Tensor>& live, double drop_p,
+                                                    const optional<Tensor>& drop_keys,
+                                                    int64_t drop_neigh, int64_t drop_self) {
   const OneDevice one_device_;
   dev(m, "m", at::kFloat);
   dev(h_self, "h_self", at::kFloat);
@@ -764,7 +914,15 @@ std::tuple<Tensor, Tensor, Tensor> sage_rel_forward(const Tensor& m, const Tenso
   dev(bias_ne, "bias_nonempty", at::kFloat);
   TORCH_CHECK_VALUE((!has(bias) || bias->numel() == N) && (!has(bias_ne) || bias_ne->numel() == N),
                     "sage_rel_forward: biases must have ", N, " entries");
-  const Tensor X = m.contiguous(), H = h_self.narrow(0, 0, M).contiguous();
+  // drop_p > 0: dropout inside the node (csrc/dropout.hip).  The neighbour mask is applied to
+  // every gathered row of m (stream drop_neigh, rows = m's rows), the self mask to a dropped
+  // copy of the M destination rows (stream drop_self); no dropped copy of m is written
+  const bool drop = drop_p > 0.0;
+  const uint64_t* dkeys = drop ? drop_keys_ptr(drop_keys, {drop_neigh, drop_self}) : nullptr;
+  TORCH_CHECK_VALUE(!drop || (!has(bias) && !has(bias_ne)),
+                    "sage_rel_forward: a folded embedding and dropout exclude each other");
+  const Tensor X = m.contiguous();
+  Tensor H = h_self.narrow(0, 0, M).contiguous();
   const Tensor bc = has(bias) ? bias->contiguous() : Tensor();
   const Tensor bnc = has(bias_ne) ? bias_ne->contiguous() : Tensor();
   const optional<Tensor> ewc = has(ew) ? optional<Tensor>(ew->contiguous()) : ew;
@@ -780,10 +938,21 @@ std::tuple<Tensor, Tensor, Tensor> sage_rel_forward(const Tensor& m, const Tenso
   // most kDumpEdges = the heavy-row split), so the gather needs no heavy-row plan; a
   // full-neighbour block's long rows run unsplit (one wave each, the same values)
   const int64_t* lv = live_ptr(live);
-  ck(gnnrec_spmm_csr_live_f32(p<int64_t>(indptr), p<int32_t>(indices), p<float>(ewc),
-                              p<float>(X), ld(X, "m"), M, X.size(1), (int)reduce, 0,
-                              p<float>(agg), ld(agg, "agg"), lv, stream_of(m)),
-     "gnnrec_spmm_csr_f32");
+  if (drop) {
+    ck(gnnrec_spmm_csr_dropout_live_f32(p<int64_t>(indptr), p<int32_t>(indices), p<float>(ewc),
+                                        p<float>(X), ld(X, "m"), M, X.size(1), (int)reduce, 0,
+                                        p<float>(agg), ld(agg, "agg"), lv, dkeys, drop_neigh,
+                                        drop_p, GNNREC_DROPOUT_SRC, stream_of(m)),
+       "gnnrec_spmm_csr_dropout_f32");
+    Tensor Hd = at::empty({M, h_self.size(1)}, m.options());
+    drop_rows(H, M, dkeys, drop_self, drop_p, false, Hd);
+    H = Hd;
+  } else {
+    ck(gnnrec_spmm_csr_live_f32(p<int64_t>(indptr), p<int32_t>(indices), p<float>(ewc),
+                                p<float>(X), ld(X, "m"), M, X.size(1), (int)reduce, 0,
+                                p<float>(agg), ld(agg, "agg"), lv, stream_of(m)),
+       "gnnrec_spmm_csr_f32");
+  }
   // bias_ne's non-empty test reads the block CSR's indptr directly (GNNREC_A2_DEG_INDPTR)
   const Tensor ipc = bnc.defined() ? indptr.contiguous() : Tensor();
   gemm_nt(H, Wsc, &agg, &Wnc, GNNREC_EPI_RELU | (norm ? GNNREC_EPI_L2NORM : 0), z,
@@ -801,7 +970,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> sage_rel_backward(
     int64_t nnz, bool norm, int64_t need, const optional<Tensor>& indptr_t_in,
     const optional<Tensor>& indices_t_in, const optional<Tensor>& w_mean_in,
     const optional<Tensor>& g_self_out, bool g_self_acc, const optional<Tensor>& g_m_out,
-    bool g_m_acc, const optional<Tensor>& live_src) {
+    bool g_m_acc, const optional<Tensor>& live_src, double drop_p,
+    const optional<Tensor>& drop_keys, int64_t drop_neigh, int64_t drop_self) {
+  // drop_*: the forward's dropout arguments and the keys tensor it read (the same masks)
   // need bits: 1 g_self, 2 g_m, 4 g_Ws, 8 g_Wn, 16 g_bias (Σ rows of the pre-activation
   // gradient), 32 g_bias_nonempty (the same over rows with an in-edge)
   const OneDevice one_device_;
@@ -841,6 +1012,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> sage_rel_backward(
     if (need & 32) g_bne = at::empty({N}, z.options());
     return {g_self, g_m, g_Ws, g_Wn, g_b, g_bne};
   }
+  const bool drop = drop_p > 0.0;
+  const uint64_t* dkeys = drop ? drop_keys_ptr(drop_keys, {drop_neigh, drop_self}) : nullptr;
   const c10::DeviceGuard g(z.device());
   void* s = stream_of(z);
   Tensor gu = at::empty({M, N}, z.options());
@@ -858,8 +1031,16 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> sage_rel_backward(
     const bool acc = has(g_self_out) && g_self_acc;
     g_self = has(g_self_out) ? *g_self_out : at::empty({h_self.size(0), Ws.size(1)}, z.options());
     Tensor head = g_self.narrow(0, 0, M);
-    gemm_nt(gu, Ws.t().contiguous(), nullptr, nullptr, 0, head, nullptr,
-            acc ? GNNREC_ACC_ADD : GNNREC_ACC_STORE);
+    if (drop) {
+      // (gu Ws) ⊙ the self mask: in place when stored; through a copy of the M rows when the
+      // table already holds other relations' gradient, which the mask must not touch
+      Tensor t = acc ? at::empty({M, Ws.size(1)}, z.options()) : head;
+      gemm_nt(gu, Ws.t().contiguous(), nullptr, nullptr, 0, t, nullptr);
+      drop_rows(t, M, dkeys, drop_self, drop_p, acc, head);
+    } else {
+      gemm_nt(gu, Ws.t().contiguous(), nullptr, nullptr, 0, head, nullptr,
+              acc ? GNNREC_ACC_ADD : GNNREC_ACC_STORE);
+    }
     if (!acc && h_self.size(0) > M) g_self.narrow(0, M, h_self.size(0) - M).zero_();
   }
   if (need & 2) {  // transposed gather of g_agg = gu Wn (DGL: the backward of a gSpMM)
@@ -892,12 +1073,20 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> sage_rel_backward(
     g_m = has(g_m_out) ? *g_m_out : at::empty({n_src, Wn.size(1)}, z.options());
     // live_src: the static block's real source count (its padding sources' gradient rows
     // are zero: only padding rows, whose gradient is zero, point at them)
+    // dropout: the mask of the source row at the store of its gradient row
+    const Drop dm{dkeys, drop_neigh, drop_p, GNNREC_DROPOUT_OUT};
     gather_planned(ip_t, ix_t, w_t, g_agg, nnz, g_m, has(g_m_out) && g_m_acc, GNNREC_REDUCE_SUM,
-                   live_ptr(live_src));
+                   live_ptr(live_src), drop ? &dm : nullptr);
   }
   if (need & 16) g_b = at::empty({N}, z.options());
   if (need & 4) {
-    g_Ws = weight_grad(gu, h_self.narrow(0, 0, M).contiguous(), (need & 16) ? &g_b : nullptr);
+    Tensor Hs = h_self.narrow(0, 0, M).contiguous();
+    if (drop) {  // the dropped self rows the forward projected, regenerated
+      Tensor Hd = at::empty({M, h_self.size(1)}, z.options());
+      drop_rows(Hs, M, dkeys, drop_self, drop_p, false, Hd);
+      Hs = Hd;
+    }
+    g_Ws = weight_grad(gu, Hs, (need & 16) ? &g_b : nullptr);
   } else if (need & 16) {
     g_b = gu.sum(0);
   }
@@ -1324,14 +1513,26 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor(a!) out) -> ()");
   m.def("sage_rel_forward(Tensor m, Tensor h_self, int n_self, Tensor W_self, Tensor W_neigh, "
         "Tensor indptr, Tensor indices, Tensor? edge_weight, int reduce, bool norm, "
-        "Tensor? bias=None, Tensor? bias_nonempty=None, Tensor? live=None) "
+        "Tensor? bias=None, Tensor? bias_nonempty=None, Tensor? live=None, float drop_p=0.0, "
+        "Tensor? drop_keys=None, int drop_neigh=0, int drop_self=0) "
         "-> (Tensor, Tensor, Tensor)");
   m.def("sage_rel_backward(Tensor gz, Tensor z, Tensor row_norm, Tensor h_self, Tensor agg, "
         "Tensor W_self, Tensor W_neigh, Tensor indptr, Tensor indices, Tensor? edge_weight, "
         "int reduce, int n_src, int nnz, bool norm, int need, Tensor? indptr_t=None, "
         "Tensor? indices_t=None, Tensor? w_mean=None, Tensor(a!)? g_self_out=None, "
         "bool g_self_acc=False, Tensor(b!)? g_m_out=None, bool g_m_acc=False, "
-        "Tensor? live_src=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+        "Tensor? live_src=None, float drop_p=0.0, Tensor? drop_keys=None, int drop_neigh=0, "
+        "int drop_self=0) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("dropout_keys(int seed, Tensor(a!) counter, int stream0, Tensor(b!) keys) -> ()");
+  m.def("dropout_rows_f32(Tensor x, int n, Tensor keys, int key_index, float p, bool accumulate, "
+        "Tensor(a!) out) -> ()");
+  m.def("spmm_csr_dropout_live_f32(Tensor indptr, Tensor indices, Tensor? edge_weight, Tensor X, "
+        "int reduce, int flags, Tensor(a!) out, Tensor? live, Tensor keys, int key_index, "
+        "float p, int where) -> ()");
+  m.def("spmm_csr_planned_dropout_live_f32(Tensor indptr, Tensor indices, Tensor? edge_weight, "
+        "Tensor X, int reduce, int flags, int split, Tensor plan, int cap_h, int cap_c, "
+        "Tensor(a!) out, Tensor(b!) workspace, Tensor? live, Tensor keys, int key_index, "
+        "float p, int where) -> ()");
   m.def("block_transposes(Tensor[] indptrs, Tensor[] indices, int[] n_src, int[] nnz) "
         "-> (Tensor[], Tensor[], Tensor[])");
   m.def("margin_loss(Tensor pos, Tensor neg, int K, float delta, Tensor? mask, Tensor? recency, "
@@ -1342,6 +1543,9 @@ TORCH_LIBRARY(gnnrec, m) {
   m.def("hold_cus(int blocks, int threads, int lds_bytes, int usec, Tensor(a!) sink) -> ()");
   // host-only entry points (no tensors: one catch-all kernel each)
   m.def("version() -> int", &version);
+  m.def("dropout_mask_host(int seed, int step, int stream, int n_rows, int d, float p) -> Tensor",
+        &dropout_mask_host);
+  m.def("dropout_scale(float p) -> float", &dropout_scale);
   m.def("set_concurrency(int reserve_cus, bool dynamic) -> ()", &set_concurrency);
   m.def("get_concurrency() -> (int, int)", &get_concurrency);
   m.def("rowq_stats() -> (int, int)", &rowq_stats);
@@ -1391,6 +1595,10 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("csr_has_edges", &csr_has_edges);               \
   m.impl("sage_rel_forward", &sage_rel_forward);         \
   m.impl("sage_rel_backward", &sage_rel_backward);       \
+  m.impl("dropout_keys", &dropout_keys);                 \
+  m.impl("dropout_rows_f32", &dropout_rows_f32);         \
+  m.impl("spmm_csr_dropout_live_f32", &spmm_csr_dropout_live_f32); \
+  m.impl("spmm_csr_planned_dropout_live_f32", &spmm_csr_planned_dropout_live_f32); \
   m.impl("block_transposes", &block_transposes);         \
   m.impl("margin_loss", &margin_loss);                   \
   m.impl("sum_scaled", &sum_scaled);                     \

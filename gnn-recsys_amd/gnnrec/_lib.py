@@ -28,6 +28,7 @@ EPI_RELU, EPI_L2NORM, EPI_SIGMOID = 1, 2, 4
 ACC_STORE, ACC_ADD, ACC_MAX = 0, 1, 2
 ACC_ATTN_FIRST, ACC_ATTN, ACC_ATTN_LAST = 3, 4, 5
 A2_NONE, A2_DIV_DEG, A2_ZERO_DEG = 0, 1, 2
+DROPOUT_SRC, DROPOUT_OUT = 0, 1
 
 
 class GnnrecLibraryError(RuntimeError):
@@ -39,6 +40,7 @@ _I64 = ctypes.c_int64
 _U64 = ctypes.c_uint64
 _INT = ctypes.c_int
 _F32 = ctypes.c_float
+_F64 = ctypes.c_double
 
 # name -> (restype, argtypes); every symbol declared in include/gnnrec.h
 SIGNATURES = {
@@ -58,6 +60,16 @@ SIGNATURES = {
                                         _P, _P]),
     "gnnrec_spmm_csr_planned_live_f32": (_INT, [_P, _P, _P, _P, _I64, _I64, _I64, _INT, _INT, _P,
                                                 _I64, _I64, _P, _I64, _I64, _P, _P, _P]),
+    # training dropout (csrc/dropout.hip): host mask, scale, device keys, rows, gathers
+    "gnnrec_dropout_mask_host": (_INT, [_U64, _U64, _U64, _I64, _I64, _F64, _P]),
+    "gnnrec_dropout_scale": (_F32, [_F64]),
+    "gnnrec_dropout_keys": (_INT, [_U64, _P, _I64, _I64, _P, _P]),
+    "gnnrec_dropout_rows_f32": (_INT, [_P, _I64, _I64, _I64, _P, _I64, _F64, _INT, _P, _I64, _P]),
+    "gnnrec_spmm_csr_dropout_live_f32": (_INT, [_P, _P, _P, _P, _I64, _I64, _I64, _INT, _INT, _P,
+                                                _I64, _P, _P, _I64, _F64, _INT, _P]),
+    "gnnrec_spmm_csr_planned_dropout_live_f32": (_INT, [_P, _P, _P, _P, _I64, _I64, _I64, _INT,
+                                                        _INT, _P, _I64, _I64, _P, _I64, _I64, _P,
+                                                        _P, _P, _I64, _F64, _INT, _P]),
     "gnnrec_spmm_csr2_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _INT, _P,
                                     _P, _I64, _P]),
     "gnnrec_spmm_csr_planned_f32": (_INT, [_P, _P, _P, _P, _I64, _I64, _I64, _INT, _INT, _P, _I64,

@@ -195,11 +195,16 @@ class SageRelFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, m, h_self, Ws, Wn, indptr, indices, ew, reduce: str, norm: bool,
-                n_self: int = 0, transposed=None):
+                n_self: int = 0, transposed=None, drop=None):
+        # drop: (p, keys, neighbour stream, self stream) — dropout of m's gathered rows and of
+        # the destination rows inside the node (csrc/dropout.hip), keys kept for the backward
+        p, keys, s_neigh, s_self = drop if drop is not None else (0.0, None, 0, 0)
         z, agg, nrm = ops._T().sage_rel_forward(m, h_self, n_self, Ws.detach(), Wn.detach(),
                                                 indptr, indices, ew, ops.REDUCE[reduce],
-                                                bool(norm), None, None, _live(indptr))
-        ctx.save_for_backward(h_self, agg, Ws, Wn, z, nrm, indptr, indices, ew)
+                                                bool(norm), None, None, _live(indptr), p, keys,
+                                                s_neigh, s_self)
+        ctx.save_for_backward(h_self, agg, Ws, Wn, z, nrm, indptr, indices, ew, keys)
+        ctx.drop = (p, s_neigh, s_self)
         ctx.reduce, ctx.norm, ctx.n_src = reduce, bool(norm), m.shape[0]
         ctx.nnz = ops._nnz(indptr)  # sampled blocks carry it: no readback
         # the block's source-major CSR when the sampler built it (unweighted relations)
@@ -208,7 +213,8 @@ class SageRelFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gz):
-        h_self, agg, Ws, Wn, z, nrm, indptr, indices, ew = ctx.saved_tensors
+        h_self, agg, Ws, Wn, z, nrm, indptr, indices, ew, keys = ctx.saved_tensors
+        p, s_neigh, s_self = ctx.drop
         need = ctx.needs_input_grad
         mask = (1 if need[1] else 0) | (2 if need[0] else 0) | (4 if need[2] else 0) | \
             (8 if need[3] else 0)
@@ -216,10 +222,18 @@ class SageRelFn(torch.autograd.Function):
         g_self, g_m, g_Ws, g_Wn, _gb, _gbne = ops._T().sage_rel_backward(
             gz, z, nrm, h_self, agg, Ws.detach(), Wn.detach(), indptr, indices, ew,
             ops.REDUCE[ctx.reduce], ctx.n_src, ctx.nnz, ctx.norm, mask, *tr,
-            live_src=_live(tr[0]) if tr[0] is not None else None)
+            live_src=_live(tr[0]) if tr[0] is not None else None, drop_p=p, drop_keys=keys,
+            drop_neigh=s_neigh, drop_self=s_self)
         return (g_m if need[0] else None, g_self if need[1] else None,
                 g_Ws if need[2] else None, g_Wn if need[3] else None,
-                None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None)
+
+
+def _rel_drop(rel):
+    """(p, keys, neighbour stream, self stream) of a HeteroSageFn relation (its optional
+    tenth entry; the keys tensor lives in the spec, as the block's CSR does)."""
+    drop = rel[9] if len(rel) > 9 else None
+    return drop if drop is not None else (0.0, None, 0, 0)
 
 
 PER = 5  # HeteroSageFn parameters per relation: W_preagg, W_self, W_neigh, bias, bias_nonempty
@@ -240,7 +254,8 @@ class HeteroSageFn(torch.autograd.Function):
     are then the raw features, W_self_r = W_s W_e,dst, bias_r = W_s b_e,dst, W_neigh_r = W_n
     W_e,src, bias_nonempty_r = W_n b_e,src (rows with an in-edge: the mean of an empty set
     is 0).  spec = (n_tables, rels, groups): rels[r] = (src table, dst table, reduce,
-    norm, n_dst, indptr, indices, edge weight, transposed); groups[k] = (dst table, relation
+    norm, n_dst, indptr, indices, edge weight, transposed[, dropout (p, keys, neighbour
+    stream, self stream) or None]); groups[k] = (dst table, relation
     indices, 'sum' | 'mean').  W_preagg_r: the relation's fc_preagg (messages relu(x W_preᵀ),
     src/model.py:102,151), whose input gradient is accumulated into the table as well."""
 
@@ -252,7 +267,9 @@ class HeteroSageFn(torch.autograd.Function):
         T = ops._T()
         zs, saved = [], []
         msgs = []
-        for r, (si, di, reduce, norm, n_dst, ip, ix, ew, _tr) in enumerate(rels):
+        for r, rel in enumerate(rels):
+            si, di, reduce, norm, n_dst, ip, ix, ew, _tr = rel[:9]
+            p, keys, s_neigh, s_self = _rel_drop(rel)
             Wp = per[PER * r]
             m = tables[si] if Wp is None else ops.gemm(tables[si].contiguous(), Wp.detach(),
                                                        relu=True)
@@ -261,7 +278,7 @@ class HeteroSageFn(torch.autograd.Function):
             z, agg, nrm = T.sage_rel_forward(
                 m, tables[di], n_dst, Ws.detach(), Wn.detach(), ip, ix, ew, ops.REDUCE[reduce],
                 bool(norm), None if b is None else b.detach(),
-                None if bne is None else bne.detach(), _live(ip))
+                None if bne is None else bne.detach(), _live(ip), p, keys, s_neigh, s_self)
             zs.append(z)
             saved += [agg, z, nrm]
         outs = []
@@ -300,7 +317,8 @@ class HeteroSageFn(torch.autograd.Function):
             if mode == 'mean' and len(idx) > 1:
                 g = g / len(idx)
             for r in idx:
-                si, di, reduce, norm, _n, ip, ix, ew, tr = rels[r]
+                si, di, reduce, norm, _n, ip, ix, ew, tr = rels[r][:9]
+                p, keys, s_neigh, s_self = _rel_drop(rels[r])
                 agg, z, nrm = saved[3 * r:3 * r + 3]
                 Ws, Wn = per[PER * r + 1], per[PER * r + 2]
                 given = ctx.m_given[r]  # messages through fc_preagg
@@ -309,6 +327,8 @@ class HeteroSageFn(torch.autograd.Function):
                     (4 if need_per[PER * r + 1] else 0) | (8 if need_per[PER * r + 2] else 0) | \
                     (16 if need_per[PER * r + 3] else 0) | (32 if need_per[PER * r + 4] else 0)
                 kw = {}
+                if p:  # the forward's masks again, from the keys it read
+                    kw.update(drop_p=p, drop_keys=keys, drop_neigh=s_neigh, drop_self=s_self)
                 if need_t[di]:
                     acc = g_tab[di] is not None
                     if not acc:

@@ -147,18 +147,31 @@ class ConvLayer(nn.Module):
     def _dropout_active(self) -> bool:
         return self.training and self.dropout_fn.p > 0
 
-    def _run(self, graph, x, out, accum: str, out_div: float, attn=None, n_self: int = 0):
+    def _fused_dropout(self) -> bool:
+        """Active dropout that the fused training nodes apply themselves (counter-based mask,
+        csrc/dropout.hip): plain messages only — sum / mean, edge-weighted or not.  With
+        fc_preagg the dropout precedes a GEMM over the whole table, and the LSTM and max
+        reducers have no fused node: those keep nn.Dropout (as does GNNREC_TRAIN_DROPOUT=torch)."""
+        return self._dropout_active() and self._aggre_type in ('mean', 'mean_edge') and \
+            os.environ.get("GNNREC_TRAIN_DROPOUT", "fused") != "torch"
+
+    def _run(self, graph, x, out, accum: str, out_div: float, attn=None, n_self: int = 0,
+             drop=None):
         """attn: (attn_vec, attn_state) for the attention accumulate modes.  n_self > 0
-        (autograd, no dropout): x[1] is the block's whole source table of the dst type and
-        its first n_self rows are the dst rows."""
+        (autograd): x[1] is the block's whole source table of the dst type and its first
+        n_self rows are the dst rows.  drop: (p, keys, neighbour stream, self stream) of this
+        relation from the model's key derivation (ConvModel._dropout_keys), or None."""
         av, ast = attn if attn is not None else (None, None)
         h_neigh, h_self = x
         preagg, weighted, reduce = self._plan(graph)
-        if self._dropout_active():
+        grad = _grad_mode(h_neigh, h_self, module=self)
+        if drop is not None and not (grad and self._fused_dropout() and ag.sage_rel_fusable(
+                h_neigh, h_self, self.fc_neigh.weight, reduce, bool(self.norm))):
+            drop = None
+        if self._dropout_active() and drop is None:
             h_neigh = self.dropout_fn(h_neigh)
             h_self = self.dropout_fn(h_self)
         ew = self._edge_weight(graph) if weighted else None
-        grad = _grad_mode(h_neigh, h_self, module=self)
         if n_self and not grad:
             h_self = h_self[:n_self]
         if grad:
@@ -169,7 +182,7 @@ class ConvLayer(nn.Module):
                 return ag.SageRelFn.apply(m, h_self, self.fc_self.weight, self.fc_neigh.weight,
                                           graph.indptr, graph.indices, ew, reduce,
                                           bool(self.norm), n_self,
-                                          getattr(graph, 'transposed', None))
+                                          getattr(graph, 'transposed', None), drop)
             if reduce == 'lstm':
                 L = self.lstm
                 agg = ag.LstmAggFn.apply(m, L.weight_ih_l0, L.weight_hh_l0, L.bias_ih_l0,
@@ -217,6 +230,9 @@ class HeteroGraphConv(nn.Module):
         if aggregate not in ('sum', 'mean', 'max', 'attention'):
             raise KeyError('Invalid cross type reducer: {}'.format(aggregate))
         self.aggregate = aggregate
+        # training dropout keys of the layer call under way: (keys, {relation: (neighbour
+        # stream, self stream)}), set by ConvModel around the call, else None
+        self._drop = None
         self.attn = None
         if aggregate == 'attention':
             if not attn_dims:
@@ -241,6 +257,11 @@ class HeteroGraphConv(nn.Module):
         on every row, W_neigh W_e,src with W_neigh b_e,src on rows with an in-edge (the
         mean of x W_eᵀ + b_e over a non-empty set is mean(x) W_eᵀ + b_e).  Only for mean
         relations without fc_preagg or edge weights; None otherwise (the caller embeds)."""
+        if fold is not None and any(self.mods[ce[1]]._dropout_active()
+                                    for ces in active.values() for ce in ces):
+            # dropout(W_e x + b_e) sits between the NodeEmbedding and this layer: the fold
+            # (a linear map applied after the mean) is not that function
+            return None
         plan = _layer_plan(self, g, src_inputs, dst_inputs, active)
         if plan is None:
             return None
@@ -265,7 +286,7 @@ class HeteroGraphConv(nn.Module):
             groups[dtype].append(len(rels))
             rels.append((tix[ce[0]], tix[dtype], reduce, bool(mod.norm),
                          dst_inputs[dtype].shape[0], rg.indptr, rg.indices, ew,
-                         getattr(rg, 'transposed', None)))
+                         getattr(rg, 'transposed', None), self._rel_drop(mod, ce)))
             if folded is None:
                 per += [mod.fc_preagg.weight if preagg else None, mod.fc_self.weight,
                         mod.fc_neigh.weight, None, None]
@@ -275,6 +296,21 @@ class HeteroGraphConv(nn.Module):
                 tuple((tix[dt], tuple(groups[dt]), self.aggregate) for dt in order))
         outs = ag.HeteroSageFn.apply(spec, *[src_inputs[nt] for nt in types], *per)
         return dict(zip(order, outs))
+
+    def _wants_drop_keys(self) -> bool:
+        """Some relation of this layer applies its dropout inside the fused nodes."""
+        return torch.is_grad_enabled() and any(m._fused_dropout() for m in self.mods.values())
+
+    def _drop_streams(self):
+        """{relation name: (neighbour stream, self stream)}: indices into one call's keys."""
+        return {name: (2 * i, 2 * i + 1) for i, name in enumerate(self.mods.keys())}
+
+    def _rel_drop(self, mod, ce):
+        """(p, keys, neighbour stream, self stream) of relation ce in the call under way."""
+        if self._drop is None or not mod._fused_dropout():
+            return None
+        keys, streams = self._drop
+        return (float(mod.dropout_fn.p), keys, *streams[ce[1]])
 
     def _pair(self, g, ces, src_inputs, h_dst, out) -> bool:
         """Inference, exactly two relations into one type, both pre-projectable
@@ -345,13 +381,20 @@ class HeteroGraphConv(nn.Module):
                 outs = []
                 for ce in ces:
                     mod = self.mods[ce[1]]
-                    if (g.is_block and not isinstance(inputs, tuple) and not mod._dropout_active()
+                    drop = self._rel_drop(mod, ce)
+                    if (g.is_block and not isinstance(inputs, tuple) and
+                            (drop is not None or not mod._dropout_active())
                             and dst_inputs[dtype].shape[0] > 0):
                         # dst rows = prefix of the src table: hand over the whole table so
                         # the self-gradient needs no slice backward
                         outs.append(mod._run(g.rel_graph(ce), (src_inputs[ce[0]],
                                                                src_inputs[dtype]), None,
-                                             'store', 0.0, n_self=dst_inputs[dtype].shape[0]))
+                                             'store', 0.0, n_self=dst_inputs[dtype].shape[0],
+                                             drop=drop))
+                    elif drop is not None:
+                        outs.append(mod._run(g.rel_graph(ce), (src_inputs[ce[0]],
+                                                               dst_inputs[dtype]), None,
+                                             'store', 0.0, drop=drop))
                     else:
                         outs.append(mod(g.rel_graph(ce), (src_inputs[ce[0]], dst_inputs[dtype])))
                 if len(outs) == 1 and self.aggregate != 'attention':
@@ -390,8 +433,9 @@ class HeteroGraphConv(nn.Module):
 
 def _layer_plan(hconv, g, src_inputs, dst_inputs, active):
     """The relations of one training layer as ag.HeteroSageFn takes them, or None when a
-    relation needs the per-relation path (max / LSTM reducers, dropout, attention or max
-    across relations, rows wider than one GEMM block, GNNREC_TRAIN_LAYER=0)."""
+    relation needs the per-relation path (max / LSTM reducers, dropout the node cannot apply
+    itself, attention or max across relations, rows wider than one GEMM block,
+    GNNREC_TRAIN_LAYER=0)."""
     if os.environ.get("GNNREC_TRAIN_LAYER", "1") == "0" or \
             hconv.aggregate not in ('sum', 'mean'):
         return None
@@ -401,8 +445,8 @@ def _layer_plan(hconv, g, src_inputs, dst_inputs, active):
             return None
         for ce in ces:
             mod = hconv.mods[ce[1]]
-            if mod._dropout_active():
-                return None
+            if mod._dropout_active() and hconv._rel_drop(mod, ce) is None:
+                return None  # nn.Dropout on the tables (fc_preagg, no keys, GNNREC_TRAIN_DROPOUT)
             rg = g.rel_graph(ce)
             preagg, weighted, reduce = mod._plan(rg)
             if not ag.sage_rel_fusable(src_inputs[ce[0]], src_inputs[dtype], mod.fc_neigh.weight,
@@ -602,6 +646,48 @@ class ConvModel(nn.Module):
 
     # None: GNNREC_TRAIN_FOLD decides ('auto' by default); '0' / '1' / 'auto' for this model
     train_fold = None
+    # training dropout (counter-based mask, csrc/dropout.hpp): the seed (None: torch's
+    # initial seed at first use) and the step counter, which lives on the device
+    _dropout_seed = None
+    _dropout_counter = None
+
+    @property
+    def dropout_seed(self) -> int:
+        """Seed of the training dropout masks.  Setting it restarts the step counter, so two
+        runs from one seed draw the same masks; GNNREC_TRAIN_DROPOUT=torch ignores it."""
+        if self._dropout_seed is None:
+            self._dropout_seed = int(torch.initial_seed())
+        return self._dropout_seed
+
+    @dropout_seed.setter
+    def dropout_seed(self, seed: int):
+        self._dropout_seed = int(seed)
+        if self._dropout_counter is not None:
+            self._dropout_counter.zero_()  # in place: a captured step keeps reading it
+
+    def _dropout_keys(self, i: int, layer, device):
+        """The keys of one call of layer i — one per (relation, role), stream id (i << 16) +
+        2 · relation + role — from the device step counter, which the same launch advances:
+        a replayed graph draws new masks every replay, and the call's backward reads the
+        keys its forward read."""
+        c = self._dropout_counter
+        if c is None or c.device != device:
+            c = self._dropout_counter = torch.zeros(1, dtype=torch.int64, device=device)
+        streams = layer._drop_streams()
+        return ops.dropout_keys(self.dropout_seed, c, 2 * len(streams), stream0=i << 16), streams
+
+    def _call_layer(self, i: int, block, h):
+        layer = self.layers[i]
+        if self.training and isinstance(layer, HeteroGraphConv) and layer._wants_drop_keys():
+            t = next((v for v in h.values() if torch.is_tensor(v) and v.is_cuda), None) \
+                if isinstance(h, dict) else None
+            if t is not None:
+                layer._drop = self._dropout_keys(i, layer, t.device)
+                try:
+                    return layer(block, h)
+                finally:
+                    layer._drop = None
+        return layer(block, h)
 
     def __init__(self, g, n_layers: int, dim_dict, norm: bool = True, dropout: float = 0.0,
                  aggregator_type: str = 'mean', pred: str = 'cos',
@@ -645,8 +731,7 @@ class ConvModel(nn.Module):
 
     def get_repr(self, blocks, h):
         for i in range(len(blocks)):
-            layer = self.layers[i]
-            h = layer(blocks[i], h)
+            h = self._call_layer(i, blocks[i], h)
         return h
 
     def embed(self, h):
@@ -715,7 +800,7 @@ class ConvModel(nn.Module):
             else:
                 h = self.embed(h)
         for i in range(start, len(blocks)):
-            h = self.layers[i](blocks[i], h)
+            h = self._call_layer(i, blocks[i], h)
         if isinstance(self.pred_fn, CosinePrediction):
             pos_score, neg_score = self.pred_fn.pair(pos_g, neg_g, h)
         else:

@@ -402,6 +402,79 @@ def spmm_backward(indptr, indices, grad_out, reduce, edge_weight=None, X=None, o
     return grad_X
 
 
+# ---- training dropout with a counter-based mask (csrc/dropout.hpp, dropout.hip) ----------
+def dropout_mask_host(seed: int, step: int, stream: int, n_rows: int, d: int, p: float):
+    """The keep mask of (seed, step, stream) as a numpy bool [n_rows, d], computed on the
+    host by the library (gnnrec_dropout_mask_host): what every dropout kernel regenerates."""
+    import numpy as np
+    lib = _lib.load()
+    keep = np.empty((n_rows, d), dtype=np.uint8)
+    mask64 = 0xFFFFFFFFFFFFFFFF
+    _lib.check(lib.gnnrec_dropout_mask_host(seed & mask64, step & mask64, stream & mask64, n_rows,
+                                            d, float(p), keep.ctypes.data),
+               "gnnrec_dropout_mask_host")
+    return keep.astype(bool)
+
+
+def dropout_scale(p: float) -> float:
+    """65536 / (65536 - round(p * 65536)): what kept elements are multiplied by."""
+    return float(_lib.load().gnnrec_dropout_scale(float(p)))
+
+
+def dropout_keys(seed: int, counter: torch.Tensor, n_streams: int, stream0: int = 0):
+    """keys[i] = hash3(seed, counter, stream0 + i) as an int64 device tensor, and counter += 1
+    on the device, in one launch (gnnrec_dropout_keys)."""
+    _dev(counter, "counter", torch.int64)
+    keys = torch.empty(n_streams, dtype=torch.int64, device=counter.device)
+    _T().dropout_keys(_lib.i64(seed), counter, stream0, keys)
+    return keys
+
+
+def dropout_rows(x: torch.Tensor, keys: torch.Tensor, key_index: int, p: float, n=None,
+                 out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """out[:n] (+)= x[:n] ⊙ mask · scale with the key keys[key_index] (n: every row)."""
+    _dev(x, "x", torch.float32)
+    n = x.shape[0] if n is None else n
+    if out is None:
+        if accumulate:
+            raise ValueError("dropout_rows: accumulate needs out")
+        out = torch.empty((n, x.shape[1]), dtype=torch.float32, device=x.device)
+    _T().dropout_rows_f32(x, n, keys, key_index, float(p), accumulate, out)
+    return out
+
+
+def spmm_dropout(indptr, indices, X, reduce: str, keys, key_index: int, p: float, where: str,
+                 edge_weight=None, out=None, accumulate: bool = False, live=None, nnz=None,
+                 split: int = DEFAULT_SPLIT):
+    """The sum / mean gather with the dropout mask inside: where='src' masks every gathered
+    row of X (the training forward), where='out' masks the output row at its store (the
+    backward over the source-major CSR; under accumulate only this call's contribution).
+    Heavy rows are planned on the device from the edge count, as the training backward's."""
+    _dev(X, "X", torch.float32)
+    if out is None:
+        if accumulate:
+            raise ValueError("spmm_dropout: accumulate needs out")
+        out = torch.empty((indptr.numel() - 1, X.shape[1]), dtype=torch.float32, device=X.device)
+    nnz = _nnz(indptr) if nnz is None else nnz
+    T = _T()
+    n, d = indptr.numel() - 1, X.shape[1]
+    side = {"src": _lib.DROPOUT_SRC, "out": _lib.DROPOUT_OUT}[where]
+    flags = _lib.SPMM_ACCUM if accumulate else 0
+    cap_h = min(n, nnz // (split + 1))
+    if cap_h <= 0:  # no row can exceed the split
+        T.spmm_csr_dropout_live_f32(indptr, indices, edge_weight, X, REDUCE[reduce], flags, out,
+                                    live, keys, key_index, float(p), side)
+        return out
+    cap_c = nnz // split + cap_h
+    plan = torch.empty(3 + 2 * cap_h + cap_c, dtype=torch.int64, device=X.device)
+    T.spmm_plan_build(indptr, split, cap_h, plan, live)
+    ws = torch.empty((cap_c, d), dtype=torch.float32, device=X.device)
+    T.spmm_csr_planned_dropout_live_f32(indptr, indices, edge_weight, X, REDUCE[reduce], flags,
+                                        split, plan, cap_h, cap_c, out, ws, live, keys,
+                                        key_index, float(p), side)
+    return out
+
+
 def gemm(A1: torch.Tensor, W1: torch.Tensor, A2: Optional[torch.Tensor] = None,
          W2: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, *,
          relu: bool = False, l2norm: bool = False, sigmoid: bool = False,

@@ -197,6 +197,53 @@ int gnnrec_spmm_csr_planned_live_f32(const int64_t* indptr, const int32_t* indic
                                      int64_t cap_c, float* workspace, const int64_t* live,
                                      void* stream);
 
+/* ---- training dropout with a counter-based mask (ConvLayer.forward, src/model.py:140-141)
+ * keep(r, c) is a pure function of (seed, step, stream, row, column) (csrc/dropout.hpp):
+ *   key = hash3(seed, step, stream); word(r, q) = mix64(key ^ (r * ceil(d / 4) + q));
+ *   draw(r, c) = 16 bits of word(r, c / 4) from bit 16 * (c % 4); T = round(p * 65536);
+ *   keep = draw >= T; kept elements are multiplied by scale = 65536 / (65536 - T)
+ * so no mask is stored: every kernel regenerates it.  The mask stream is the build's own,
+ * as the sampler's RNG is: parity with torch.nn.Dropout is distributional, not elementwise.
+ *
+ * gnnrec_dropout_mask_host  keep[n_rows, d] as bytes, on the host (no GPU needed).
+ * gnnrec_dropout_scale      the scale of p (0 when p = 1).
+ * gnnrec_dropout_keys       keys[i] = hash3(seed, *counter, stream0 + i) for i < n_streams,
+ *                           then *counter += 1, in one launch: the step counter lives on the
+ *                           device, so a replayed graph draws new masks on every replay,
+ *                           and the backward of a call reads the keys its forward read.
+ * gnnrec_dropout_rows_f32   out[r, :] (+)= x[r, :] * keep(r, :) * scale for r < n, with the
+ *                           key keys[key_index] (accumulate != 0: added to out); also
+ *                           "multiply a gradient by the mask".
+ * gnnrec_spmm_csr_dropout_live_f32 / gnnrec_spmm_csr_planned_dropout_live_f32
+ *                           the sum / mean gathers of gnnrec_spmm_csr_live_f32 and
+ *                           gnnrec_spmm_csr_planned_live_f32 with the mask inside:
+ *   GNNREC_DROPOUT_SRC  out[v] = scale * reduce_e keep(indices[e], :) X[indices[e], :] (w_e)
+ *                       (the forward: rows are X's rows, no dropped copy of X is written);
+ *   GNNREC_DROPOUT_OUT  out[v] = keep(v, :) * scale * reduce_e X[indices[e], :] (w_e), the
+ *                       mask applied at the store of the row (the backward over the
+ *                       source-major CSR); under GNNREC_SPMM_ACCUM it multiplies this call's
+ *                       contribution only, not what out already holds. */
+#define GNNREC_DROPOUT_SRC 0
+#define GNNREC_DROPOUT_OUT 1
+int gnnrec_dropout_mask_host(uint64_t seed, uint64_t step, uint64_t stream, int64_t n_rows,
+                             int64_t d, double p, uint8_t* keep);
+float gnnrec_dropout_scale(double p);
+int gnnrec_dropout_keys(uint64_t seed, int64_t* counter, int64_t stream0, int64_t n_streams,
+                        uint64_t* keys, void* stream);
+int gnnrec_dropout_rows_f32(const float* x, int64_t ldx, int64_t n, int64_t d,
+                            const uint64_t* keys, int64_t key_index, double p, int accumulate,
+                            float* out, int64_t ldo, void* stream);
+int gnnrec_spmm_csr_dropout_live_f32(const int64_t* indptr, const int32_t* indices,
+                                     const float* ew, const float* X, int64_t ldx, int64_t n_dst,
+                                     int64_t d, int reduce, int flags, float* out, int64_t ldo,
+                                     const int64_t* live, const uint64_t* keys,
+                                     int64_t key_index, double p, int where, void* stream);
+int gnnrec_spmm_csr_planned_dropout_live_f32(
+    const int64_t* indptr, const int32_t* indices, const float* ew, const float* X, int64_t ldx,
+    int64_t n_dst, int64_t d, int reduce, int flags, float* out, int64_t ldo, int64_t split,
+    const int64_t* plan, int64_t cap_h, int64_t cap_c, float* workspace, const int64_t* live,
+    const uint64_t* keys, int64_t key_index, double p, int where, void* stream);
+
 /* Two relations into one destination type in one launch: out_a[v] = reduce over relation
  * A's in-edges of v, out_b[v] likewise over relation B, both gathering from the same source
  * table X (C5's clicks and buys source tiles: the 12.5-edges-per-row relation runs beside
