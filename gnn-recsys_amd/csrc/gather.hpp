@@ -3,6 +3,7 @@
 // (spmm_project.hip), so both reduce every row in the same fixed order.
 #pragma once
 #include "common.hpp"
+#include "pack_rows.hpp"
 #include <cmath>
 
 namespace gnnrec {
@@ -111,6 +112,82 @@ __device__ __forceinline__ void gather_range(int64_t beg, int64_t end,
           }
         }
       }
+    }
+  }
+}
+
+// gather_range (LPR = 32, VEC = 4, sum / mean, unweighted) over a packed table
+// (pack_rows.hpp): the same chunks, lane groups, UNROLL and adds in the same order, so an
+// aggregate is bitwise the dense gather's — an unset mask bit decodes to +0.0, the value it
+// stands for.  Per step, lanes 0-23 of a group load the 16-B pieces of the packed row (no
+// dependent load); the wave stages the step's UNROLL row pairs in its own LDS (`stage`:
+// UNROLL x 192 words, written and read by this wave only) and every lane reads back its
+// mask nibble, the popcount prefix and its up to four values at their packed positions.
+// A step in which any group drew a `dense` row takes a wave-uniform branch and reads those
+// rows' fragments from the dense table X.
+template <int UNROLL, bool PRE = false>
+__device__ __forceinline__ void gather_range_packed(int64_t beg, int64_t end,
+                                                    const int32_t* __restrict__ indices,
+                                                    const uint32_t* __restrict__ P,
+                                                    const float* __restrict__ X, int64_t ldx,
+                                                    int lane, int grp, Frag<4>& acc,
+                                                    uint32_t* stage, int pre_idx = 0) {
+  constexpr int NPI = 2;
+  const int l = lane & 31;
+  const int w = l >> 3, sh = (l & 7) * 4;
+  uint32_t* mine = stage + grp * kPackWords;
+  for (int64_t base = beg; base < end; base += 64) {
+    const int cnt = (int)((end - base) < 64 ? (end - base) : 64);
+    int myidx;
+    if (PRE && base == beg) myidx = pre_idx;
+    else myidx = lane < cnt ? ld_stream(indices + base + lane) : 0;
+    for (int j = 0; j < cnt; j += NPI * UNROLL) {
+      uint4 q[UNROLL];
+      int src[UNROLL];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const int k = j + u * NPI + grp;
+        src[u] = edge_bcast<NPI>(myidx, j + u * NPI, grp);
+        q[u] = make_uint4(0u, 0u, 0u, 0u);
+        if (k < cnt && l < kPackWords / 4)
+          q[u] = *reinterpret_cast<const uint4*>(P + (int64_t)src[u] * kPackWords + 4 * l);
+      }
+      Frag<4> val[UNROLL];
+      uint64_t dense[UNROLL], any_dense = 0;  // lane 1 of a group holds its row's flag word
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        if (l < kPackWords / 4)
+          *reinterpret_cast<uint4*>(mine + u * 2 * kPackWords + 4 * l) = q[u];
+        dense[u] = __ballot(l == 1 && (q[u].y & kPackDenseBit) != 0u);
+        any_dense |= dense[u];
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const uint32_t* r = mine + u * 2 * kPackWords;
+        const uint32_t m = r[w];
+        const uint32_t nib = (m >> sh) & 15u;
+        uint32_t p = ((r[4] >> (8 * w)) & 255u) + __popc(m & ((1u << sh) - 1u));
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          // slot of column 4l + v (read whether or not the bit is set: clamped to the row)
+          const uint32_t x =
+              r[kPackHdrWords + (p < (uint32_t)kPackSlots - 1 ? p : kPackSlots - 1)];
+          val[u].v[v] = (nib >> v) & 1u ? __builtin_bit_cast(float, x) : 0.f;
+          p += (nib >> v) & 1u;
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the stage is rewritten next
+      if (any_dense != 0) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u)
+          if ((dense[u] >> (32 * grp + 1)) & 1ull)
+            load_frag<4>(val[u], X + (int64_t)src[u] * ldx + 4 * l);
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) acc.v[v] += val[u].v[v];
     }
   }
 }

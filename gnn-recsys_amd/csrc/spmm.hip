@@ -25,6 +25,7 @@
 #include "rowq.hpp"
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 namespace gnnrec {
 namespace {
@@ -326,6 +327,107 @@ __global__ __launch_bounds__(256) void spmm_combine_kernel(
   }
 }
 
+// ---- a packed source table (pack_rows.hpp): d = 128, sum / mean, unweighted ------------
+// The row and chunk kernels above with gather_range_packed as their gather: the same rows,
+// schedules (static grid-stride or the row queue), heavy-row split and accumulate-into-
+// partial, so every output is bitwise what they write from the dense table X.  A table
+// whose packed_ok is 0 (too many rows that do not fit) is read through the dense loop.
+template <int REDUCE, int UNROLL>
+__global__ __launch_bounds__(256) void spmm_csr_packed_kernel(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+    const uint32_t* __restrict__ P, const int* __restrict__ pstatus, const float* __restrict__ X,
+    int64_t ldx, int64_t n_dst, float* __restrict__ out, int64_t ldo, int flags, int64_t max_deg,
+    unsigned* rq, int rq_ch, const int64_t* __restrict__ plan_counts) {
+  __shared__ __attribute__((aligned(16))) uint32_t stage_all[4][UNROLL * 2 * kPackWords];
+  if (plan_counts != nullptr && plan_counts[0] < 0) max_deg = INT64_MAX;
+  const bool packed = pstatus[0] != 0;  // uniform
+  const int lane = threadIdx.x & 63;
+  const int grp = lane >> 5;
+  const int col = (lane & 31) * 4;
+  uint32_t* stage = stage_all[threadIdx.x >> 6];
+  // one destination row; idx: the range's first 64 indices when the caller prefetched them
+  auto reduce_row = [&](int64_t row, int64_t beg, int64_t end, auto pre, int idx) {
+    constexpr bool PRE = decltype(pre)::value;
+    Frag<4> acc;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) acc.v[v] = 0.f;
+    if (packed)
+      gather_range_packed<UNROLL, PRE>(beg, end, indices, P, X, ldx, lane, grp, acc, stage, idx);
+    else
+      gather_range<32, 4, REDUCE, false, UNROLL, PRE>(beg, end, indices, nullptr, X, ldx, col,
+                                                      true, lane, grp, acc, idx);
+    combine_groups<32, 4, REDUCE>(acc);
+    finalize<4, REDUCE>(acc, end - beg, 0);
+    if (grp == 0) {
+      if (flags & GNNREC_SPMM_ACCUM) accumulate_into<4, REDUCE>(acc, out + row * ldo + col);
+      store_frag<4>(out + row * ldo + col, acc);
+    }
+  };
+  if (rq != nullptr) {  // the queued row loop of spmm_csr_kernel
+    if (rq_ch <= 0) {
+      const int64_t avg = (indptr[n_dst] - indptr[0]) / n_dst;
+      rq_ch = ticket_rows(avg, n_dst, gridDim.x * 4);
+    }
+    rq_for_each(rq, n_dst, rq_ch, [&](int64_t r0, int64_t r1) {
+      const int nr = (int)(r1 - r0);  // <= 64
+      const int64_t ipl = lane < nr ? ld_stream(indptr + r0 + lane) : 0;
+      const int64_t ip_end = indptr[r1];
+      auto bound = [&](int k) { return k < nr ? __shfl(ipl, k) : ip_end; };
+      int64_t beg = bound(0), end = bound(1);
+      int nidx = lane < end - beg ? ld_stream(indices + beg + lane) : 0;
+      for (int k = 0; k < nr; ++k) {
+        const int idx = nidx;
+        const int64_t nbeg = end, nend = k + 1 < nr ? bound(k + 2) : end;
+        if (k + 1 < nr) nidx = lane < nend - nbeg ? ld_stream(indices + nbeg + lane) : 0;
+        if (end - beg <= max_deg) reduce_row(r0 + k, beg, end, std::true_type{}, idx);
+        beg = nbeg;
+        end = nend;
+      }
+    });
+    rq_finish(rq);
+    return;
+  }
+  const int64_t wstride = (int64_t)gridDim.x * 4;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n_dst; row += wstride) {
+    const int64_t beg = indptr[row], end = indptr[row + 1];
+    if (end - beg <= max_deg) reduce_row(row, beg, end, std::false_type{}, 0);
+  }
+}
+
+template <int REDUCE, int UNROLL>
+__global__ __launch_bounds__(256) void spmm_chunk_packed_kernel(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+    const uint32_t* __restrict__ P, const int* __restrict__ pstatus, const float* __restrict__ X,
+    int64_t ldx, int64_t split, const int64_t* __restrict__ heavy_rows,
+    const int64_t* __restrict__ chunk_ptr, const int64_t* __restrict__ chunk_row, int64_t n_chunks,
+    const int64_t* __restrict__ counts, float* __restrict__ ws) {
+  __shared__ __attribute__((aligned(16))) uint32_t stage_all[4][UNROLL * 2 * kPackWords];
+  const bool packed = pstatus[0] != 0;
+  const int lane = threadIdx.x & 63;
+  const int grp = lane >> 5;
+  const int col = (lane & 31) * 4;
+  uint32_t* stage = stage_all[threadIdx.x >> 6];
+  const int64_t wstride = (int64_t)gridDim.x * 4;
+  if (counts) n_chunks = counts[1];
+  for (int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); c < n_chunks; c += wstride) {
+    const int64_t h = chunk_row[c];
+    const int64_t row = heavy_rows[h];
+    const int64_t rbeg = indptr[row], rend = indptr[row + 1];
+    const int64_t beg = rbeg + (c - chunk_ptr[h]) * split;
+    const int64_t end = (beg + split < rend) ? beg + split : rend;
+    Frag<4> acc;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) acc.v[v] = 0.f;
+    if (packed)
+      gather_range_packed<UNROLL>(beg, end, indices, P, X, ldx, lane, grp, acc, stage);
+    else
+      gather_range<32, 4, REDUCE, false, UNROLL>(beg, end, indices, nullptr, X, ldx, col, true,
+                                                 lane, grp, acc);
+    combine_groups<32, 4, REDUCE>(acc);
+    if (grp == 0) store_frag<4>(ws + c * (int64_t)kPackD + col, acc);
+  }
+}
+
 struct SpmmArgs {
   const int64_t* indptr; const int32_t* indices; const float* ew; const float* X; int64_t ldx;
   int64_t n_dst; int d; float* out; int64_t ldo; int flags;
@@ -334,6 +436,8 @@ struct SpmmArgs {
   const int64_t* counts;  // device-built plan: {n_heavy, n_chunks}; n_heavy/n_chunks above
                           // are then the plan's capacities (grid sizes)
   const int64_t* live;    // device row count (nullable): rows from it on are empty rows
+  const uint32_t* P;      // packed copy of X (nullable; pack_rows.hpp) and its status words:
+  const int* pstatus;     // the gathers then read P, and X only for rows P does not hold
 };
 
 // Resident 256-thread blocks per CU the row kernels occupy (grid-stride beyond): every wave
@@ -363,6 +467,24 @@ int launch_all(const SpmmArgs& a, hipStream_t s) {
   unsigned* rq = slices == 1 && a.n_dst >= (int64_t)grid * 4 * kRqMinRowsPerWave
                      ? rowq_slot(s, &ticket)
                      : nullptr;
+  if constexpr (LPR == 32 && VEC == 4 && REDUCE != GNNREC_REDUCE_MAX && !WEIGHTED) {
+    if (a.P != nullptr) {  // (spmm_entry: d = 128, so one column slice)
+      hipLaunchKernelGGL((spmm_csr_packed_kernel<REDUCE, UNROLL>), dim3(grid), dim3(256), 0, s,
+                         a.indptr, a.indices, a.P, a.pstatus, a.X, a.ldx, a.n_dst, a.out, a.ldo,
+                         eni, max_deg, rq, kRowChunk, a.counts);
+      rowq_launched(ticket, s);
+      if (a.n_heavy > 0) {
+        hipLaunchKernelGGL((spmm_chunk_packed_kernel<REDUCE, UNROLL>),
+                           dim3(grid_waves(a.n_chunks)), dim3(256), 0, s, a.indptr, a.indices, a.P,
+                           a.pstatus, a.X, a.ldx, a.split, a.heavy_rows, a.chunk_ptr, a.chunk_row,
+                           a.n_chunks, a.counts, a.ws);
+        hipLaunchKernelGGL((spmm_combine_kernel<VEC, REDUCE>), dim3(grid_waves(a.n_heavy), 1),
+                           dim3(256), 0, s, a.indptr, a.d, a.heavy_rows, a.n_heavy, a.chunk_ptr,
+                           a.ws, a.out, a.ldo, eni, a.counts);
+      }
+      return check_launch("gnnrec_spmm_csr_packed_f32");
+    }
+  }
   hipLaunchKernelGGL((spmm_csr_kernel<LPR, VEC, REDUCE, WEIGHTED, UNROLL>),
                      dim3(grid, slices), dim3(256), 0, s, a.indptr, a.indices, a.ew,
                      a.X, a.ldx, a.n_dst, a.d, a.out, a.ldo, eni, max_deg, rq, kRowChunk,
@@ -514,6 +636,13 @@ int spmm_entry(SpmmArgs a, int64_t d, int reduce, void* stream) {
   GNNREC_REQUIRE(a.live == nullptr || reduce != GNNREC_REDUCE_MAX,
                  "gnnrec_spmm_csr_live_f32: a device row count needs sum or mean");
   a.d = (int)d;
+  if (a.P != nullptr)
+    GNNREC_REQUIRE(d == kPackD && reduce != GNNREC_REDUCE_MAX && a.ew == nullptr &&
+                       a.live == nullptr && a.pstatus != nullptr && a.ldx % 4 == 0 &&
+                       a.ldo % 4 == 0 && aligned16(a.X) && aligned16(a.out) && aligned16(a.P) &&
+                       (a.n_heavy == 0 || aligned16(a.ws)),
+                   "gnnrec_spmm_csr_packed_f32: needs d = %d, sum or mean, no edge weights, no "
+                   "device row count and 16-B aligned rows", kPackD);
   const bool vec4 = (d % 4 == 0) && (a.ldx % 4 == 0) && (a.ldo % 4 == 0) && aligned16(a.X) &&
                     aligned16(a.out) && (a.n_heavy == 0 || aligned16(a.ws));
   int lpr = 64;
@@ -534,6 +663,21 @@ extern "C" int gnnrec_spmm_csr_f32(const int64_t* indptr, const int32_t* indices
                                    int reduce, int flags, float* out, int64_t ldo, void* stream) {
   gnnrec::SpmmArgs a{indptr, indices, ew, X, ldx, n_dst, 0, out, ldo, flags,
                      0, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
+  return gnnrec::spmm_entry(a, d, reduce, stream);
+}
+
+extern "C" int gnnrec_spmm_csr_packed_f32(const int64_t* indptr, const int32_t* indices,
+                                          const void* packed, const int32_t* status,
+                                          const float* X, int64_t ldx, int64_t n_dst, int64_t d,
+                                          int reduce, int flags, float* out, int64_t ldo,
+                                          int64_t split, const int64_t* heavy_rows,
+                                          int64_t n_heavy, const int64_t* chunk_ptr,
+                                          const int64_t* chunk_row, int64_t n_chunks,
+                                          float* workspace, const int64_t* counts, void* stream) {
+  GNNREC_REQUIRE(packed && status && X, "gnnrec_spmm_csr_packed_f32: null table");
+  gnnrec::SpmmArgs a{indptr, indices, nullptr, X, ldx, n_dst, 0, out, ldo, flags,
+                     split, heavy_rows, n_heavy, chunk_ptr, chunk_row, n_chunks, workspace,
+                     counts, nullptr, static_cast<const uint32_t*>(packed), status};
   return gnnrec::spmm_entry(a, d, reduce, stream);
 }
 

@@ -269,6 +269,95 @@ void spmm_project(const Tensor& indptr, const Tensor& indices, const optional<Te
      mfma ? "gnnrec_spmm_project_mfma_f32" : "gnnrec_spmm_project_f32");
 }
 
+// ---------------------------------------------------------------- packed rows
+// packed: int32 [n, 96] (csrc/pack_rows.hpp), status: int32 [4]
+void packed_pair(const Tensor& packed, const Tensor& status, const Tensor& X) {
+  dev(packed, "packed", at::kInt);
+  dev(status, "status", at::kInt);
+  TORCH_CHECK_VALUE(X.dim() == 2 && X.size(1) == 128, "packed rows need X [n, 128]");
+  TORCH_CHECK_VALUE(packed.dim() == 2 && packed.size(0) == X.size(0) && packed.size(1) == 96 &&
+                        packed.is_contiguous(),
+                    "packed must be a contiguous int32 [", X.size(0), ", 96]");
+  TORCH_CHECK_VALUE(status.numel() == 4 && status.is_contiguous(), "status must be int32 [4]");
+}
+
+void pack_rows_f32(const Tensor& X, double max_dense_frac, Tensor& packed, Tensor& status) {
+  const OneDevice one_device_;
+  dev(X, "X", at::kFloat);
+  packed_pair(packed, status, X);
+  const int64_t ldx = ld(X, "X");
+  if (meta(X)) return;
+  const c10::DeviceGuard g(X.device());
+  ck(gnnrec_pack_rows_f32(p<float>(X), ldx, X.size(0), X.size(1), max_dense_frac,
+                          p<int32_t>(packed), p<int32_t>(status), stream_of(X)),
+     "gnnrec_pack_rows_f32");
+}
+
+// host only: a CPU fp32 [n, 128] table -> (packed int32 [n, 96], dense rows), and back
+std::tuple<Tensor, int64_t> pack_rows_host(const Tensor& X) {
+  TORCH_CHECK_VALUE(X.device().is_cpu() && X.scalar_type() == at::kFloat && X.dim() == 2 &&
+                        X.size(1) == 128,
+                    "pack_rows_host: needs a CPU float32 [n, 128] table");
+  const Tensor x = X.contiguous();
+  Tensor packed = at::empty({x.size(0), 96}, at::TensorOptions().dtype(at::kInt));
+  int64_t dense = 0;
+  ck(gnnrec_pack_rows_host(x.data_ptr<float>(), x.size(0), packed.data_ptr<int32_t>(), &dense),
+     "gnnrec_pack_rows_host");
+  return {packed, dense};
+}
+
+Tensor unpack_rows_host(const Tensor& packed, const Tensor& X_dense) {
+  TORCH_CHECK_VALUE(packed.device().is_cpu() && packed.scalar_type() == at::kInt &&
+                        packed.dim() == 2 && packed.size(1) == 96 && X_dense.device().is_cpu() &&
+                        X_dense.scalar_type() == at::kFloat && X_dense.dim() == 2 &&
+                        X_dense.size(0) == packed.size(0) && X_dense.size(1) == 128,
+                    "unpack_rows_host: needs CPU int32 [n, 96] and float32 [n, 128]");
+  const Tensor pk = packed.contiguous(), x = X_dense.contiguous();
+  Tensor out = at::empty({pk.size(0), 128}, at::TensorOptions().dtype(at::kFloat));
+  ck(gnnrec_unpack_rows_host(pk.data_ptr<int32_t>(), x.data_ptr<float>(), pk.size(0),
+                             out.data_ptr<float>()),
+     "gnnrec_unpack_rows_host");
+  return out;
+}
+
+// n_heavy > 0: a heavy-row plan (host-built: the three lists; device-built: views of the
+// plan tensor and `counts` = the plan itself, n_heavy / n_chunks its capacities)
+void spmm_csr_packed_f32(const Tensor& indptr, const Tensor& indices, const Tensor& packed,
+                         const Tensor& status, const Tensor& X, int64_t reduce, int64_t flags,
+                         int64_t split, const optional<Tensor>& heavy, int64_t n_heavy,
+                         const optional<Tensor>& chunk_ptr, const optional<Tensor>& chunk_row,
+                         int64_t n_chunks, const optional<Tensor>& counts, Tensor& out,
+                         const optional<Tensor>& ws) {
+  const OneDevice one_device_;
+  dev(indptr, "indptr", at::kLong);
+  dev(indices, "indices", at::kInt);
+  dev(X, "X", at::kFloat);
+  packed_pair(packed, status, X);
+  dev(heavy, "heavy_rows", at::kLong);
+  dev(chunk_ptr, "chunk_ptr", at::kLong);
+  dev(chunk_row, "chunk_row", at::kLong);
+  dev(counts, "counts", at::kLong);
+  dev(out, "out", at::kFloat);
+  dev(ws, "workspace", at::kFloat);
+  const int64_t n_dst = indptr.numel() - 1, d = X.size(1);
+  TORCH_CHECK_VALUE(out.size(0) == n_dst && out.size(1) == d, "out must be [", n_dst, ", ", d, "]");
+  TORCH_CHECK_VALUE(n_heavy >= 0 && n_chunks >= 0, "negative plan size");
+  if (n_heavy > 0)
+    TORCH_CHECK_VALUE(has(heavy) && has(chunk_ptr) && has(chunk_row) && has(ws) &&
+                          heavy->numel() >= n_heavy && chunk_ptr->numel() >= n_heavy + 1 &&
+                          chunk_row->numel() >= n_chunks && ws->numel() >= n_chunks * d,
+                      "spmm_csr_packed_f32: incomplete heavy-row plan");
+  const int64_t ldx = ld(X, "X"), ldo = ld(out, "out");
+  if (meta(X)) return;
+  const c10::DeviceGuard g(X.device());
+  ck(gnnrec_spmm_csr_packed_f32(p<int64_t>(indptr), p<int32_t>(indices), p<int32_t>(packed),
+                                p<int32_t>(status), p<float>(X), ldx, n_dst, d, (int)reduce,
+                                (int)flags, p<float>(out), ldo, split, p<int64_t>(heavy), n_heavy,
+                                p<int64_t>(chunk_ptr), p<int64_t>(chunk_row), n_chunks,
+                                p<float>(ws), p<int64_t>(counts), stream_of(X)),
+     "gnnrec_spmm_csr_packed_f32");
+}
+
 void spmm_project2(const Tensor& indptr_a, const Tensor& indices_a, const optional<Tensor>& ew_a,
                    const Tensor& Ya, int64_t reduce_a, const optional<Tensor>& bias_nonempty_a,
                    const Tensor& indptr_b, const Tensor& indices_b, const optional<Tensor>& ew_b,
@@ -1463,6 +1552,12 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor W_selfT, Tensor? W_neighT, Tensor? bias, Tensor? bias_nonempty, int reduce, "
         "int epilogue, int accum, float out_div, Tensor? attn_vec, Tensor(b!)? attn_state, "
         "bool mfma, Tensor(a!) out) -> ()");
+  m.def("pack_rows_f32(Tensor X, float max_dense_frac, Tensor(a!) packed, Tensor(b!) status) "
+        "-> ()");
+  m.def("spmm_csr_packed_f32(Tensor indptr, Tensor indices, Tensor packed, Tensor status, "
+        "Tensor X, int reduce, int flags, int split, Tensor? heavy_rows, int n_heavy, "
+        "Tensor? chunk_ptr, Tensor? chunk_row, int n_chunks, Tensor? counts, Tensor(a!) out, "
+        "Tensor(b!)? workspace) -> ()");
   m.def("spmm_project2(Tensor indptr_a, Tensor indices_a, Tensor? ew_a, Tensor Ya, int reduce_a, "
         "Tensor? bias_nonempty_a, Tensor indptr_b, Tensor indices_b, Tensor? ew_b, Tensor Yb, "
         "int reduce_b, Tensor? bias_nonempty_b, Tensor H, Tensor W_self_aT, Tensor W_self_bT, "
@@ -1546,6 +1641,8 @@ TORCH_LIBRARY(gnnrec, m) {
   m.def("dropout_mask_host(int seed, int step, int stream, int n_rows, int d, float p) -> Tensor",
         &dropout_mask_host);
   m.def("dropout_scale(float p) -> float", &dropout_scale);
+  m.def("pack_rows_host(Tensor X) -> (Tensor, int)", &pack_rows_host);
+  m.def("unpack_rows_host(Tensor packed, Tensor X_dense) -> Tensor", &unpack_rows_host);
   m.def("set_concurrency(int reserve_cus, bool dynamic) -> ()", &set_concurrency);
   m.def("get_concurrency() -> (int, int)", &get_concurrency);
   m.def("rowq_stats() -> (int, int)", &rowq_stats);
@@ -1573,6 +1670,8 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("row_epilogue", &row_epilogue);                 \
   m.impl("spmm_project", &spmm_project);                 \
   m.impl("spmm_project2", &spmm_project2);               \
+  m.impl("pack_rows_f32", &pack_rows_f32);               \
+  m.impl("spmm_csr_packed_f32", &spmm_csr_packed_f32);   \
   m.impl("spmm_pair", &spmm_pair);                       \
   m.impl("sddmm_cos", &sddmm_cos);                       \
   m.impl("sddmm_cos_grouped", &sddmm_cos_grouped);       \

@@ -60,6 +60,12 @@ SIGNATURES = {
                                         _P, _P]),
     "gnnrec_spmm_csr_planned_live_f32": (_INT, [_P, _P, _P, _P, _I64, _I64, _I64, _INT, _INT, _P,
                                                 _I64, _I64, _P, _I64, _I64, _P, _P, _P]),
+    # packed rows (csrc/pack_rows.hip) and the gather that reads them
+    "gnnrec_pack_rows_f32": (_INT, [_P, _I64, _I64, _I64, _F64, _P, _P, _P]),
+    "gnnrec_pack_rows_host": (_INT, [_P, _I64, _P, _P]),
+    "gnnrec_unpack_rows_host": (_INT, [_P, _P, _I64, _P]),
+    "gnnrec_spmm_csr_packed_f32": (_INT, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _INT, _P,
+                                          _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P]),
     # training dropout (csrc/dropout.hip): host mask, scale, device keys, rows, gathers
     "gnnrec_dropout_mask_host": (_INT, [_U64, _U64, _U64, _I64, _I64, _F64, _P]),
     "gnnrec_dropout_scale": (_F32, [_F64]),

@@ -390,6 +390,12 @@ class ShardedFullGraphPass:
         self.pair_raw = set()  # ... of them, the one-table form (gnnrec_spmm_pair_f32)
         self.tile_pairs = set()  # (relation a, relation b) whose tiles ran as one launch
         self._pool = {}  # scratch tables reused across passes (_scratch)
+        # packed copies of the hidden tables the layers after the first gather (ops.pack_rows;
+        # _pack): (node type, stream, rows) -> buffers kept for the runner's life, and the
+        # tables packed so far in the current layer
+        self._pack_pool, self._packs = {}, {}
+        self._packed_on = False
+        self.packed = set()  # relations whose gather read packed rows
         self._scratch_ev = {}  # scratch key -> event of the side-stream work reading it
         self._last, self._replicate_last = False, True
 
@@ -408,6 +414,39 @@ class ShardedFullGraphPass:
             t = torch.empty(shape, dtype=torch.float32, device=device)
             self._pool[key] = t
         return t
+
+    def _pack(self, msg, nt, reduce, weighted):
+        """The packed copy of hidden table `msg` = h[nt] (384-B rows: a ReLU output is about
+        half zeros, ops.pack_rows) for a sum / mean, unweighted gather of a layer after the
+        first, or None (GNNREC_PACKED_ROWS=0, another backend, width or reducer: the dense
+        gather).  Packed once per layer and stream, on the stream that reads it, into
+        buffers allocated once per runner; a table that does not compress sets packed_ok = 0
+        on the device and its gathers run their dense loop."""
+        if not self._packed_on or self._layer_idx == 0 or weighted or \
+                reduce not in ('sum', 'mean') or not msg.is_cuda or msg.dim() != 2 or \
+                msg.shape[1] != ops.PACK_D or msg.dtype != torch.float32 or \
+                msg.stride(1) != 1 or msg.stride(0) % 4 or msg.data_ptr() % 16:
+            return None
+        cur = torch.cuda.current_stream(msg.device).cuda_stream
+        pk = self._packs.get((id(msg), cur))
+        if pk is None:
+            key = (nt, cur, msg.shape[0])
+            buf = self._pack_pool.get(key)
+            if buf is None:
+                buf = self._pack_pool[key] = ops.PackedRows(msg.shape[0], msg.device)
+            self._packs = {k: v for k, v in self._packs.items() if v is not buf}
+            with self._time('pack_rows'):
+                pk = ops.pack_rows(msg, into=buf)
+            self._packs[(id(msg), cur)] = pk
+        return pk
+
+    def _spmm(self, ip, ix, msg, op, pk, **kw):
+        """O.spmm, from the packed copy of msg when there is one (the same bits)."""
+        if pk is None:
+            return self.ops.spmm(ip, ix, msg, op, **kw)
+        kw.pop('edge_weight', None)
+        kw.pop('empty_neginf', None)
+        return ops.spmm_packed(ip, ix, pk, op, **kw)
 
     def _par(self) -> int:
         """Scratch set of this layer's replicated-type partials: alternating by layer when
@@ -488,6 +527,9 @@ class ShardedFullGraphPass:
         self._ready.clear()
         self._fold.clear()
         self._folded_types.clear()
+        self._packed_on = self.ops is ops and sh.device.type == 'cuda' and \
+            os.environ.get("GNNREC_PACKED_ROWS", "1") != "0"
+        self.packed.clear()
         if embedding_layer is None:
             embedding_layer = m.embedding_layer
         h = dict(feats)
@@ -618,7 +660,7 @@ class ShardedFullGraphPass:
                 msg = self._message(mod, ce, h, preagg)
                 can_fuse = getattr(O, 'can_spmm_project', None)
                 if self.deterministic and reduce in ('sum', 'mean'):
-                    tree_rels.append((ce, rs, msg, weighted, reduce))
+                    tree_rels.append((ce, rs, msg, weighted, reduce, preagg))
                     continue
                 if rs.segs is not None and reduce != 'lstm':
                     # source-range tiles: each tile gathers from a slice of the source table
@@ -626,11 +668,14 @@ class ShardedFullGraphPass:
                     op = 'max' if reduce == 'max' else 'sum'
                     part = self._scratch(('part', ce, self._par()), (rs.n_rows, msg.shape[1]),
                                          msg.device)
+                    pk = None if preagg else self._pack(msg, ce[0], reduce, weighted)
+                    if pk is not None:
+                        self.packed.add(ce)
                     for j, (ip, ix, w) in enumerate(rs.segs):
                         with self._time('spmm_tile'):
-                            O.spmm(ip, ix, msg, op, edge_weight=w if weighted else None,
-                                   empty_neginf=op == 'max', out=part, accumulate=j > 0,
-                                   split=TILE_SPLIT)
+                            self._spmm(ip, ix, msg, op, pk, edge_weight=w if weighted else None,
+                                       empty_neginf=op == 'max', out=part, accumulate=j > 0,
+                                       split=TILE_SPLIT)
                     own, work = self.ex.reduce_scatter_rows(part, op, async_op=self.overlap)
                     partials[ce] = (own, work, reduce)
                     continue
@@ -704,7 +749,7 @@ class ShardedFullGraphPass:
         for j in range(n_seg):
             for item in pairs:
                 if len(item) == 2:  # two relations, one launch per tile (gnnrec_spmm_csr2_f32)
-                    (ca, ra, msg, weighted, _), (cb, rb, *_r) = item
+                    (ca, ra, msg, weighted, *_), (cb, rb, *_r) = item
                     self.tile_pairs.add((ca, cb))
                     sa, sb = ra.segs[j], rb.segs[j]
                     csr_a = (sa[0], sa[1], sa[2] if weighted else None)
@@ -724,22 +769,25 @@ class ShardedFullGraphPass:
                             self.ops.spmm2(csr_a, csr_b, msg, 'sum', out_a=parts[ca][-1],
                                            out_b=parts[cb][-1], accumulate=True)
                     continue
-                ce, rs, msg, weighted, _ = item[0]
+                ce, rs, msg, weighted, reduce, preagg = item[0]
                 if j >= len(rs.segs):
                     continue
                 ip, ix, w = rs.segs[j]
                 ew = w if weighted else None
+                pk = None if preagg else self._pack(msg, ce[0], reduce, weighted)
+                if pk is not None:
+                    self.packed.add(ce)
                 with self._time('spmm_tile'):
                     if j % 2 == 0:
-                        parts[ce].append(self.ops.spmm(
-                            ip, ix, msg, 'sum', edge_weight=ew, split=TILE_SPLIT,
+                        parts[ce].append(self._spmm(
+                            ip, ix, msg, 'sum', pk, edge_weight=ew, split=TILE_SPLIT,
                             out=self._scratch(('tile', ce, j, self._par()),
                                               (rs.n_rows, msg.shape[1]), msg.device)))
                     else:
-                        self.ops.spmm(ip, ix, msg, 'sum', edge_weight=ew, out=parts[ce][-1],
-                                      accumulate=True, split=TILE_SPLIT)
+                        self._spmm(ip, ix, msg, 'sum', pk, edge_weight=ew, out=parts[ce][-1],
+                                   accumulate=True, split=TILE_SPLIT)
         out = {}
-        for ce, rs, msg, weighted, reduce in rels:
+        for ce, rs, msg, weighted, reduce, _ in rels:
             if not multi_rank(self.ex) and self._owned_side:
                 # one rank, owner work on the side stream: the whole tree is folded there
                 # (_owned), off the main stream that runs the pair launch's inputs next
@@ -1060,6 +1108,7 @@ class ShardedFullGraphPass:
             out[T] = t
 
     def _layer(self, hconv, h):
+        self._packs = {}
         active = self._active(hconv, h)
         out = {}
         if self._owned_side:

@@ -402,6 +402,111 @@ def spmm_backward(indptr, indices, grad_out, reduce, edge_weight=None, X=None, o
     return grad_X
 
 
+# ---- packed rows of a ReLU-sparse table (csrc/pack_rows.hpp, pack_rows.hip) --------------
+PACK_D = 128           # columns of a packable table
+PACK_WORDS = 96        # int32 words per packed row (384 B)
+PACK_SLOTS = 88        # values a packed row holds; above: a `dense` row
+PACK_DENSE_BIT = 1 << 31
+PACK_MAX_DENSE_FRAC = 1.0 / 8  # kPackMaxDenseFrac
+
+
+class PackedRows:
+    """A packed copy of a dense [n, 128] fp32 table: `data` int32 [n, 96], `status` int32 [4]
+    ({packed_ok, dense rows, two counters of the pack kernel}) and the dense table `X` itself,
+    which rows that do not fit are read from.  The buffers are allocated once and refilled
+    by pack_rows(X, into=...)."""
+
+    def __init__(self, n: int, device):
+        self.data = torch.empty((n, PACK_WORDS), dtype=torch.int32, device=device)
+        self.status = torch.zeros(4, dtype=torch.int32, device=device)
+        self.X = None
+
+    def rows(self, lo: int, hi: int) -> "PackedRows":
+        """Rows [lo, hi) of the table (a source tile's slice), sharing the buffers."""
+        v = object.__new__(PackedRows)
+        v.data, v.status, v.X = self.data[lo:hi], self.status, self.X[lo:hi]
+        return v
+
+
+def pack_rows(X: torch.Tensor, into: Optional[PackedRows] = None,
+              max_dense_frac: Optional[float] = None) -> PackedRows:
+    """Pack the dense table X [n, 128] (gnnrec_pack_rows_f32) on the current stream.
+    packed_ok = 1 iff at most max_dense_frac * n rows have more than 88 non-zeros."""
+    _dev(X, "X", torch.float32)
+    _rowmajor(X, "X")
+    n, d = X.shape
+    if d != PACK_D:
+        raise ValueError(f"pack_rows: packed rows are {PACK_D} wide (got {d})")
+    if into is None:
+        into = PackedRows(n, X.device)
+    elif into.data.shape[0] != n or into.data.device != X.device:
+        raise ValueError("pack_rows: `into` was allocated for another table")
+    _T().pack_rows_f32(X, -1.0 if max_dense_frac is None else float(max_dense_frac), into.data,
+                       into.status)
+    into.X = X
+    return into
+
+
+def pack_rows_host(x):
+    """(packed uint32 [n, 96], dense rows) of a numpy fp32 [n, 128] table, on the host."""
+    import numpy as np
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    p, dense = _T().pack_rows_host(torch.from_numpy(x))
+    return p.numpy().view(np.uint32), int(dense)
+
+
+def unpack_rows_host(p, x_dense):
+    """The fp32 [n, 128] table that `p` packs (`dense` rows copied from x_dense), on the host."""
+    import numpy as np
+    p = np.ascontiguousarray(p, dtype=np.uint32).view(np.int32)
+    x_dense = np.ascontiguousarray(x_dense, dtype=np.float32)
+    return _T().unpack_rows_host(torch.from_numpy(p), torch.from_numpy(x_dense)).numpy()
+
+
+def spmm_packed(indptr: torch.Tensor, indices: torch.Tensor, packed: PackedRows,
+                reduce: str = "mean", out: Optional[torch.Tensor] = None,
+                split: Optional[int] = DEFAULT_SPLIT, accumulate: bool = False) -> torch.Tensor:
+    """spmm(indptr, indices, packed.X, reduce) gathering from the packed copy of the table
+    (gnnrec_spmm_csr_packed_f32): bitwise the same result.  sum / mean, no edge weights."""
+    _dev(indptr, "indptr", torch.int64)
+    _dev(indices, "indices", torch.int32)
+    X = packed.X
+    if reduce not in ("sum", "mean"):
+        raise ValueError(f"spmm_packed: reduce {reduce!r} (sum or mean)")
+    n_dst = indptr.numel() - 1
+    if out is None:
+        if accumulate:
+            raise ValueError("spmm_packed: accumulate needs out")
+        out = torch.empty((n_dst, PACK_D), dtype=torch.float32, device=X.device)
+    else:
+        _dev(out, "out", torch.float32)
+        if tuple(out.shape) != (n_dst, PACK_D):
+            raise ValueError(f"out must be [{n_dst}, {PACK_D}]")
+    flags = _lib.SPMM_ACCUM if accumulate else 0
+    heavy = chunk_ptr = chunk_row = counts = ws = None
+    n_heavy = n_chunks = 0
+    if split and getattr(indptr, "_gnnrec_split_plan", None) is None and \
+            getattr(indptr, "_gnnrec_nnz", None) is not None:
+        dplan = _device_plan(indptr, split)  # built on the device: {counts, rows, ptr, row}
+        if dplan is not None:
+            pl, n_heavy, n_chunks = dplan
+            counts, heavy = pl, pl[2:]
+            chunk_ptr, chunk_row = pl[2 + n_heavy:], pl[3 + 2 * n_heavy:]
+        else:
+            split = None
+    elif split:
+        plan = split_plan(indptr, split)
+        if plan is not None:
+            heavy, chunk_ptr, chunk_row, n_chunks = plan
+            n_heavy = heavy.numel()
+    if n_heavy:
+        ws = torch.empty((n_chunks, PACK_D), dtype=torch.float32, device=X.device)
+    _T().spmm_csr_packed_f32(indptr, indices, packed.data, packed.status, X, REDUCE[reduce], flags,
+                             split or 0, heavy, n_heavy, chunk_ptr, chunk_row, n_chunks, counts,
+                             out, ws)
+    return out
+
+
 # ---- training dropout with a counter-based mask (csrc/dropout.hpp, dropout.hip) ----------
 def dropout_mask_host(seed: int, step: int, stream: int, n_rows: int, d: int, p: float):
     """The keep mask of (seed, step, stream) as a numpy bool [n_rows, d], computed on the

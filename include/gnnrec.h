@@ -197,6 +197,36 @@ int gnnrec_spmm_csr_planned_live_f32(const int64_t* indptr, const int32_t* indic
                                      int64_t cap_c, float* workspace, const int64_t* live,
                                      void* stream);
 
+/* ---- packed rows of a ReLU-sparse [n, 128] fp32 table (csrc/pack_rows.hpp) --------------
+ * A packed row is 384 B (96 words) at packed + 384 * r: a 128-bit mask of the columns whose
+ * 32-bit pattern is non-zero, the popcount prefix of its words, nnz, and the non-zero values
+ * in column order (88 slots).  Lossless; a row with nnz > 88 is flagged `dense`, stores no
+ * values and is read from the dense table instead.  status is 4 int32, zero before the
+ * first pack: [0] packed_ok (dense rows <= max_dense_frac * n), [1] dense rows, [2..3] the
+ * kernel's counters (zero again when it ends).
+ *
+ * gnnrec_pack_rows_f32        X [n, 128] -> packed, status.  max_dense_frac < 0: the default.
+ * gnnrec_pack_rows_host / gnnrec_unpack_rows_host
+ *                             the format restated on the host (no GPU needed): X contiguous;
+ *                             unpack takes `dense` rows from X_dense.
+ * gnnrec_spmm_csr_packed_f32  gnnrec_spmm_csr_f32 (sum / mean, unweighted, d = 128) gathering
+ *                             from the packed copy of X: bitwise the same out.  A table whose
+ *                             packed_ok is 0 is read from X alone.  n_heavy > 0: the heavy-row
+ *                             plan of gnnrec_spmm_csr_split_f32; counts != NULL: a device-
+ *                             built plan's {n_heavy, n_chunks} (n_heavy / n_chunks are then
+ *                             its capacities, as in gnnrec_spmm_csr_planned_f32). */
+int gnnrec_pack_rows_f32(const float* X, int64_t ldx, int64_t n, int64_t d, double max_dense_frac,
+                         void* packed, int32_t* status, void* stream);
+int gnnrec_pack_rows_host(const float* X, int64_t n, void* packed, int64_t* dense_rows);
+int gnnrec_unpack_rows_host(const void* packed, const float* X_dense, int64_t n, float* out);
+int gnnrec_spmm_csr_packed_f32(const int64_t* indptr, const int32_t* indices, const void* packed,
+                               const int32_t* status, const float* X, int64_t ldx, int64_t n_dst,
+                               int64_t d, int reduce, int flags, float* out, int64_t ldo,
+                               int64_t split, const int64_t* heavy_rows, int64_t n_heavy,
+                               const int64_t* chunk_ptr, const int64_t* chunk_row,
+                               int64_t n_chunks, float* workspace, const int64_t* counts,
+                               void* stream);
+
 /* ---- training dropout with a counter-based mask (ConvLayer.forward, src/model.py:140-141)
  * keep(r, c) is a pure function of (seed, step, stream, row, column) (csrc/dropout.hpp):
  *   key = hash3(seed, step, stream); word(r, q) = mix64(key ^ (r * ceil(d / 4) + q));
