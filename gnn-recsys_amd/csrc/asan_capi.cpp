@@ -79,6 +79,77 @@ static void validation() {
                              nullptr, 1000, nullptr, nullptr, 1000, nullptr) != GNNREC_OK &&
             err_has("hidden size"),
         "lstm hidden");
+  // the bf16-prefiltered top-k (recommend.hip): every refusal comes before a launch
+  float* f16 = static_cast<float*>(p16);
+  int32_t* i16 = static_cast<int32_t*>(p16);
+  int64_t* l16 = static_cast<int64_t*>(p16);
+  CHECK(gnnrec_normalize_rows_bf16(f16, 100, 5, 100, nullptr, p16, 100, nullptr) == GNNREC_EINVAL &&
+            err_has("dpad"),
+        "normalize dpad");
+  CHECK(gnnrec_normalize_rows_bf16(f16, 64, 5, 100, nullptr, p16, 128, nullptr) == GNNREC_EINVAL,
+        "normalize ld < d");
+  CHECK(gnnrec_normalize_rows_bf16(f16, 100, 5, 100, nullptr, reinterpret_cast<void*>(24), 128,
+                                   nullptr) == GNNREC_EINVAL && err_has("aligned"),
+        "normalize unaligned out");
+  CHECK(gnnrec_normalize_rows_bf16(nullptr, 100, 0, 100, nullptr, nullptr, 128, nullptr) ==
+            GNNREC_OK,
+        "normalize empty");
+  CHECK(gnnrec_score_bf16_store(p16, 4, p16, 9, 48, f16, 9, nullptr) == GNNREC_EINVAL &&
+            err_has("multiple of 32"),
+        "store dpad");
+  CHECK(gnnrec_score_bf16_store(p16, 4, p16, 9, 4096, f16, 9, nullptr) == GNNREC_EINVAL,
+        "store dpad past the bound's range");
+  CHECK(gnnrec_score_bf16_store(p16, 4, p16, 9, 32, f16, 8, nullptr) == GNNREC_EINVAL &&
+            err_has("ldo"),
+        "store ldo");
+  CHECK(gnnrec_score_bf16_store(p16, 4, reinterpret_cast<void*>(8), 9, 32, f16, 9, nullptr) ==
+            GNNREC_EINVAL,
+        "store unaligned table");
+  CHECK(gnnrec_score_bf16_store(p16, 4, p16, (int64_t)1 << 31, 32, f16, (int64_t)1 << 31,
+                                nullptr) == GNNREC_EINVAL && err_has("int32"),
+        "store item ids");
+  CHECK(gnnrec_score_bf16_store(nullptr, 0, nullptr, 9, 32, nullptr, 9, nullptr) == GNNREC_OK,
+        "store empty");
+  CHECK(gnnrec_score_bf16_filter(p16, 4, p16, 9, 32, f16, i16, i16, 4097, nullptr) ==
+            GNNREC_EINVAL && err_has("cap"),
+        "filter cap");
+  CHECK(gnnrec_score_bf16_filter(p16, 4, p16, 9, 32, f16, i16, i16, 0, nullptr) == GNNREC_EINVAL,
+        "filter cap 0");
+  CHECK(gnnrec_score_bf16_filter(p16, 4, p16, 9, 32, nullptr, i16, i16, 64, nullptr) ==
+            GNNREC_EINVAL && err_has("null pointer"),
+        "filter null tau");
+  CHECK(gnnrec_score_bf16_filter(nullptr, 4, nullptr, 0, 32, nullptr, nullptr, nullptr, 64,
+                                 nullptr) == GNNREC_OK,
+        "filter empty");
+  CHECK(gnnrec_mask_excluded_f32(f16, 4, 3, 9, nullptr, l16, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("ld"),
+        "mask ld");
+  CHECK(gnnrec_mask_excluded_f32(f16, 9, 3, 9, nullptr, nullptr, i16, nullptr) == GNNREC_EINVAL,
+        "mask null list");
+  CHECK(gnnrec_mask_excluded_f32(nullptr, 9, 0, 9, nullptr, nullptr, nullptr, nullptr) == GNNREC_OK,
+        "mask empty");
+  CHECK(gnnrec_topk_candidates_f32(i16, i16, 64, 3, nullptr, f16, 16, f16, 16, 16, nullptr,
+                                   nullptr, 65, f16, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("k must be"),
+        "candidates k > cap");
+  CHECK(gnnrec_topk_candidates_f32(i16, i16, 8192, 3, nullptr, f16, 16, f16, 16, 16, nullptr,
+                                   nullptr, 10, f16, l16, nullptr) == GNNREC_EINVAL,
+        "candidates cap");
+  CHECK(gnnrec_topk_candidates_f32(i16, i16, 64, 3, nullptr, f16, 18, f16, 18, 18, nullptr,
+                                   nullptr, 10, f16, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("d %"),
+        "candidates d");
+  CHECK(gnnrec_topk_candidates_f32(i16, i16, 64, 3, nullptr, f16, 16, f16, 16, 16, l16, nullptr,
+                                   10, f16, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("indptr without indices"),
+        "candidates exclusion");
+  CHECK(gnnrec_topk_candidates_f32(i16, i16, 64, 3, nullptr, reinterpret_cast<float*>(4), 16, f16,
+                                   16, 16, nullptr, nullptr, 10, f16, l16, nullptr) ==
+            GNNREC_EINVAL && err_has("aligned"),
+        "candidates alignment");
+  CHECK(gnnrec_topk_candidates_f32(nullptr, nullptr, 64, 0, nullptr, nullptr, 16, nullptr, 16, 16,
+                                   nullptr, nullptr, 10, nullptr, nullptr, nullptr) == GNNREC_OK,
+        "candidates empty");
 }
 
 // the fused sampler's planner: capacities grow as the docs say, and bad plans are refused

@@ -1,0 +1,556 @@
+// f1b — exact top-k recommendations without a score matrix: a bf16 MFMA prefilter, then the
+// library's own fp32 cosine on the few pairs it cannot rule out.
+//
+// score(u, v) is, by definition, the value gnnrec_sddmm_cos_f32 returns for the pair from the
+// raw fp32 tables (CosinePrediction's arithmetic, rows divided by max(|.|, 1e-12)), and the
+// ranking is (score desc, item id asc) with the user's excluded items removed — what
+// gnnrec_topk_rows_f32 gives over a full score row.  The kernels:
+//
+//   normalize_rows_bf16   û = x / max(|x|, 1e-12) in fp32, rounded to bf16 (nearest even),
+//                         rows padded with zeros to a multiple of 32 columns
+//   score_bf16            a(u, v) = sum_c bf16(û_c) bf16(v̂_c), fp32 accumulation on
+//                         v_mfma_f32_32x32x16_bf16; one main loop, two epilogues:
+//                           store   a as fp32 [B, m] (the sample that sets the thresholds)
+//                           filter  append item v to row u's candidate list where
+//                                   a >= tau_u - 2 eps
+//   mask_excluded         the sample's excluded columns to -inf, so that a plain top-k of
+//                         the sample gives tau (the k-th best non-excluded score there)
+//   topk_candidates       drop a row's excluded candidates, rescore the rest with the fp32
+//                         cosine (cos_score.hpp: the bits of gnnrec_sddmm_cos_f32), rank
+//
+// THE BOUND.  bf16 has unit roundoff 2^-8: |bf16(û) - û| <= 2^-8 |û| as vectors, and the same
+// for v̂.  With |û| = |v̂| = 1 (up to fp32 rounding) Cauchy-Schwarz gives
+//   |bf16(û).bf16(v̂) - û.v̂| <= |bf16(û) - û| |bf16(v̂)| + |û| |bf16(v̂) - v̂|
+//                             <= 2^-8 (1 + 2^-8) + 2^-8.
+// fp32 accumulation of d products of magnitude <= 1 and the fp32 rounding of the
+// normalisation add at most about d 2^-23, and score itself carries the same order of fp32
+// error against the real cosine: for d <= 2048 all of it is below 2^-11 - 2^-16, so
+//   |a(u, v) - score(u, v)| <= eps = 2^-7 + 2^-11.
+//
+// THE FILTER.  Let tau_r be ANY value such that at least k non-excluded items of row r have
+// a >= tau_r.  Those k items have score >= tau_r - eps, so the true k-th best score is
+// >= tau_r - eps, and every item of the true top k has a >= tau_r - 2 eps.  Items below
+// that are discarded; a looser tau_r only admits more candidates, never loses one.  (Ties in
+// score at the k-th place are covered too: a tied item's score is >= tau_r - eps as well.)
+#include "common.hpp"
+#include "cos_score.hpp"
+#include <algorithm>
+#include <cmath>
+
+namespace gnnrec {
+namespace {
+
+constexpr float kRecEps = 0.0078125f + 0.00048828125f;  // 2^-7 + 2^-11, derived above
+constexpr int kRecMaxD = 2048;                           // the bound's range of d
+constexpr int kCandMax = 4096;                           // candidate slots per row, at most
+constexpr int kExChunk = 2048;                           // exclusion ids staged per round
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));  // 16 B in flight
+
+// fp32 -> bf16 bits, round to nearest even (finite inputs; non-finite is outside the contract)
+__device__ __forceinline__ uint32_t bf16_rne(float x) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, x);
+  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+// ------------------------------------------------------------ normalise ----
+// One wave per row: sum of squares (16-B loads when the rows allow), xor-tree reduce, then
+// x / max(|x|, 1e-12) rounded to bf16; the second read of the row comes from L1.
+__global__ __launch_bounds__(256) void normalize_rows_bf16_kernel(
+    const float* __restrict__ X, int64_t ld, int64_t n, int d, const int64_t* __restrict__ map,
+    uint16_t* __restrict__ out, int dpad, bool vec) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;  // wave-uniform
+  const float* src = X + (map ? map[row] : row) * ld;
+  uint16_t* dst = out + row * dpad;
+  float ss = 0.f;
+  if (vec) {
+    for (int c = lane * 4; c < d; c += kWave * 4) {
+      const float4 v = *reinterpret_cast<const float4*>(src + c);
+      ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    }
+  } else {
+    for (int c = lane; c < d; c += kWave) ss += src[c] * src[c];
+  }
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) ss += __shfl_xor(ss, off);
+  const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+  if (vec) {  // d % 4 == 0: a group of four columns is all data or all pad
+    for (int c = lane * 4; c < dpad; c += kWave * 4) {
+      uint2 o = make_uint2(0u, 0u);
+      if (c < d) {
+        const float4 v = *reinterpret_cast<const float4*>(src + c);
+        o.x = bf16_rne(v.x / nrm) | (bf16_rne(v.y / nrm) << 16);
+        o.y = bf16_rne(v.z / nrm) | (bf16_rne(v.w / nrm) << 16);
+      }
+      *reinterpret_cast<uint2*>(dst + c) = o;
+    }
+  } else {
+    for (int c = lane; c < dpad; c += kWave)
+      dst[c] = c < d ? (uint16_t)bf16_rne(src[c] / nrm) : (uint16_t)0;
+  }
+}
+
+// ---------------------------------------------------------------- score ----
+// A 256-thread block scores a 128 x 128 (users x items) tile, each of its four waves a
+// 64 x 64 quarter as 2 x 2 MFMA tiles of 32 x 32 (64 accumulator registers per lane).  Both
+// tables are row-major with K contiguous, which is the operand layout of
+// v_mfma_f32_32x32x16_bf16 for A and for B alike: lane l holds row (l & 31), k = 8 (l >> 5)
+// .. + 7 of a k-step, one 16-B load straight from the table.  No LDS, no transpose; the user
+// batch is served by L2 (consecutive blocks walk the user tiles of one item slab).
+// Rows and items past the end read a clamped (valid) row and are masked in the epilogue:
+// they are never scored as zeros, which a negative threshold would pass.
+// C layout: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
+
+// A wave's 64 x 64 accumulators (rows r0.., columns c0..) to their destination, rows >= B
+// and columns >= n masked here, at the compare or the store.  The filter's 32 row thresholds
+// (tau - 2 eps, +inf for rows past the end) are fetched as one batch before the compares — a
+// load per row in front of its compare serialises 32 memory latencies per tile — from
+// thr_lds (the wave's 64 thresholds, staged with the user tile: four rows per 16-B read)
+// when given, else from tau.
+template <bool FILTER>
+__device__ __forceinline__ void score_epilogue(const f32x16 (&acc)[2][2], int64_t r0, int64_t c0,
+                                               int l31, int h, int64_t B, int64_t n,
+                                               float* __restrict__ out, int64_t ldo,
+                                               const float* __restrict__ tau,
+                                               const float* thr_lds, int* __restrict__ counts,
+                                               int* __restrict__ cand, int cap) {
+  if constexpr (FILTER) {
+    f32x4 thr[2][4];  // [i][g]: rows i 32 + 8 g + 4 h + (0..3), the registers 4 g .. 4 g + 3
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        if (thr_lds) {
+          thr[i][g] = *reinterpret_cast<const f32x4*>(thr_lds + i * 32 + 8 * g + 4 * h);
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int64_t row = r0 + i * 32 + 8 * g + 4 * h + q;
+            thr[i][g][q] = row < B ? tau[row] - 2.f * kRecEps : INFINITY;
+          }
+        }
+      }
+    const bool colok[2] = {c0 + l31 < n, c0 + 32 + l31 < n};
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          if (colok[j] && acc[i][j][reg] >= thr[i][reg >> 2][reg & 3]) {
+            // the counter keeps counting past cap (the overflow signal); a store happens
+            // only inside the row's cap slots
+            const int64_t row = r0 + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+            const int slot = atomicAdd(counts + row, 1);
+            if (slot >= 0 && slot < cap) cand[row * cap + slot] = (int)(c0 + j * 32 + l31);
+          }
+  } else {
+    // addresses split into a wave-uniform part (scalar registers) and one lane offset, so
+    // that the 32 rows' address arithmetic does not sit in vector registers
+    const int64_t lane_out = (int64_t)(4 * h) * ldo + l31;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int64_t urow = r0 + i * 32 + (reg & 3) + 8 * (reg >> 2);  // uniform
+        if (urow + 4 * h >= B) continue;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          if (c0 + j * 32 + l31 < n) (out + urow * ldo + c0 + j * 32)[lane_out] = acc[i][j][reg];
+      }
+  }
+}
+
+template <bool FILTER>
+__global__ __launch_bounds__(256) void score_bf16_kernel(
+    const uint16_t* __restrict__ U, int64_t B, const uint16_t* __restrict__ V, int64_t n,
+    int dpad, int64_t n_utiles, float* __restrict__ out, int64_t ldo,
+    const float* __restrict__ tau, int* __restrict__ counts, int* __restrict__ cand, int cap) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int l31 = lane & 31, h = lane >> 5;
+  const int64_t tile = blockIdx.x;
+  const int64_t r0 = (tile % n_utiles) * 128 + (wave >> 1) * 64;
+  const int64_t c0 = (tile / n_utiles) * 128 + (wave & 1) * 64;
+  if (r0 >= B || c0 >= n) return;  // wave-uniform; the kernel has no barrier
+  const uint16_t* pa[2];
+  const uint16_t* pb[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int64_t r = min(r0 + i * 32 + l31, B - 1);
+    const int64_t c = min(c0 + i * 32 + l31, n - 1);
+    pa[i] = U + r * dpad + 8 * h;
+    pb[i] = V + c * dpad + 8 * h;
+  }
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  for (int k0 = 0; k0 < dpad; k0 += 32) {  // dpad % 32 == 0: two k-steps, 8 loads in flight
+    bf16x8 a[2][2], b[2][2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        a[s][i] = *reinterpret_cast<const bf16x8*>(pa[i] + k0 + 16 * s);
+        b[s][i] = *reinterpret_cast<const bf16x8*>(pb[i] + k0 + 16 * s);
+      }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][i], b[s][j], acc[i][j], 0, 0, 0);
+  }
+  score_epilogue<FILTER>(acc, r0, c0, l31, h, B, n, out, ldo, tau, nullptr, counts, cand, cap);
+}
+
+// The same tile for dpad = 32, 64 and 128 (d <= 64 and 97..128; at 96 the registers of two
+// resident blocks do not hold the slab and a tile in flight without scratch), arranged so that every byte comes through a coalesced load:
+// a block owns a slab of 128 items for its whole life — each wave's 64 item rows, all of K,
+// stay in registers as B fragments (dpad / 16 x 2 fragments of 4 VGPRs, 64 at dpad = 128) —
+// and walks the batch's user tiles (every gridDim.y-th one).  A user tile (128 rows x dpad)
+// is staged into LDS with 16-B loads that cover whole rows (issued one tile ahead, into
+// registers, so that their latency runs under the MFMAs), and read back in the MFMA
+// layout (lane l: row l & 31, 16 B at k = 8 (l >> 5)); rows are padded by 16 B so that the
+// 16 lanes of a ds_read_b128 phase fall in distinct bank groups (row stride 272 B = 68
+// banks at dpad = 128).  Direct operand loads touch 32 rows per instruction for 32 B each;
+// this form moves the same bytes as full lines.
+template <int DPAD>
+__device__ __forceinline__ void fetch_user_tile(u32x4 (&pf)[DPAD / 16], const uint16_t* U,
+                                                int64_t B, int64_t ut, int tid) {
+  constexpr int CH = DPAD / 8;
+#pragma unroll
+  for (int p = 0; p < DPAD / 16; ++p) {
+    const int idx = tid + p * 256;
+    const int64_t r = min(ut * 128 + idx / CH, B - 1);  // past the end: a valid row, masked later
+    pf[p] = *reinterpret_cast<const u32x4*>(U + r * DPAD + (idx % CH) * 8);
+  }
+}
+
+template <int DPAD, bool FILTER>
+__global__ __launch_bounds__(256, 2) void score_bf16_slab_kernel(
+    const uint16_t* __restrict__ U, int64_t B, const uint16_t* __restrict__ V, int64_t n,
+    float* __restrict__ out, int64_t ldo, const float* __restrict__ tau,
+    int* __restrict__ counts, int* __restrict__ cand, int cap) {
+  constexpr int KS = DPAD / 16;        // k-steps
+  constexpr int CH = DPAD / 8;         // 16-B chunks per row
+  constexpr int ROWB = DPAD * 2 + 16;  // LDS bytes per staged row
+  __shared__ __attribute__((aligned(16))) unsigned char sA[128 * ROWB];
+  __shared__ __attribute__((aligned(16))) float sThr[128];  // the tile's tau - 2 eps (filter)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, h = lane >> 5;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int64_t c0 = (int64_t)blockIdx.x * 128 + wc * 64;
+  const bool has_items = c0 < n;  // wave-uniform; a wave without items still joins the barriers
+  bf16x8 bfr[2][KS];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int64_t c = min(c0 + j * 32 + l31, n - 1);
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+      bfr[j][ks] = *reinterpret_cast<const bf16x8*>(V + c * DPAD + ks * 16 + 8 * h);
+  }
+  const int64_t n_ut = (B + 127) / 128;
+  // the next user tile travels from L2 into registers while this one is multiplied
+  constexpr int PF = 128 * CH / 256;  // 16-B chunks per thread per tile
+  static_assert(128 * CH % 256 == 0, "a tile is a whole number of block-wide loads");
+  u32x4 pf[PF];
+  // (the filter pass only: the store pass scores the short sample, and its epilogue's
+  // addresses leave no room for the tile in flight at two blocks per CU)
+  constexpr bool kAhead = FILTER;
+  float tpf = INFINITY;  // thread t < 128: row t's threshold, +inf past the end (never passed)
+  auto fetch_thr = [&](int64_t ut) {
+    const int64_t r = ut * 128 + tid;
+    if (tid < 128) tpf = r < B ? tau[r] - 2.f * kRecEps : INFINITY;
+  };
+  if (kAhead && (int64_t)blockIdx.y < n_ut) {
+    fetch_user_tile<DPAD>(pf, U, B, blockIdx.y, tid);
+    fetch_thr(blockIdx.y);
+  }
+  for (int64_t ut = blockIdx.y; ut < n_ut; ut += gridDim.y) {  // block-uniform trip count
+    __syncthreads();  // the previous tile's reads are done
+    if constexpr (!kAhead) fetch_user_tile<DPAD>(pf, U, B, ut, tid);
+#pragma unroll
+    for (int p = 0; p < PF; ++p) {
+      const int idx = tid + p * 256;
+      *reinterpret_cast<u32x4*>(sA + (idx / CH) * ROWB + (idx % CH) * 16) = pf[p];
+    }
+    if (FILTER && tid < 128) sThr[tid] = tpf;
+    __syncthreads();
+    if (kAhead && ut + gridDim.y < n_ut) {
+      fetch_user_tile<DPAD>(pf, U, B, ut + gridDim.y, tid);
+      fetch_thr(ut + gridDim.y);
+    }
+    const int64_t r0 = ut * 128 + wr * 64;
+    if (!has_items || r0 >= B) continue;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      bf16x8 a[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        a[i] = *reinterpret_cast<const bf16x8*>(sA + (wr * 64 + i * 32 + l31) * ROWB + ks * 32 +
+                                                h * 16);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], bfr[j][ks], acc[i][j], 0, 0, 0);
+    }
+    score_epilogue<FILTER>(acc, r0, c0, l31, h, B, n, out, ldo, tau,
+                           FILTER ? sThr + wr * 64 : nullptr, counts, cand, cap);
+  }
+}
+
+template <bool FILTER>
+void launch_score(const uint16_t* U, int64_t B, const uint16_t* V, int64_t n, int dpad, float* out,
+                  int64_t ldo, const float* tau, int* counts, int* cand, int cap, hipStream_t s) {
+  const int64_t nu = (B + 127) / 128, ni = (n + 127) / 128;
+  if (dpad != 32 && dpad != 64 && dpad != 128) {
+    hipLaunchKernelGGL((score_bf16_kernel<FILTER>), dim3((unsigned)(nu * ni)), dim3(256), 0, s, U,
+                       B, V, n, dpad, nu, out, ldo, tau, counts, cand, cap);
+    return;
+  }
+  // enough blocks to fill the chip when the item range is short (the sample pass, small tables)
+  const int64_t gy = std::min<int64_t>(nu, std::max<int64_t>(1, (2048 + ni - 1) / ni));
+  const dim3 grid((unsigned)ni, (unsigned)gy), block(256);
+#define GNNREC_LAUNCH_SLAB(D)                                                                 \
+  hipLaunchKernelGGL((score_bf16_slab_kernel<D, FILTER>), grid, block, 0, s, U, B, V, n, out, \
+                     ldo, tau, counts, cand, cap)
+  if (dpad == 32) GNNREC_LAUNCH_SLAB(32);
+  else if (dpad == 64) GNNREC_LAUNCH_SLAB(64);
+  else GNNREC_LAUNCH_SLAB(128);
+#undef GNNREC_LAUNCH_SLAB
+}
+
+// ------------------------------------------------------------ mask ----
+// One wave per score row: the columns of the row's user's exclusion list become -inf, so a
+// plain top-k over the sample's scores yields tau (the k-th best NON-excluded score, -inf
+// when fewer than k columns are eligible).  Ids outside [0, n_cols) are skipped.
+__global__ __launch_bounds__(256) void mask_excluded_kernel(
+    float* __restrict__ S, int64_t ld, int64_t n_rows, int64_t n_cols,
+    const int64_t* __restrict__ user_rows, const int64_t* __restrict__ ex_ptr,
+    const int32_t* __restrict__ ex_idx) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n_rows) return;
+  const int64_t u = user_rows ? user_rows[row] : row;
+  const int64_t e1 = ex_ptr[u + 1];
+  for (int64_t e = ex_ptr[u] + (threadIdx.x & 63); e < e1; e += kWave) {
+    const int64_t c = ex_idx[e];
+    if (c >= 0 && c < n_cols) S[row * ld + c] = -INFINITY;
+  }
+}
+
+// ------------------------------------------------------------ candidates ----
+__device__ __forceinline__ bool better(float a, int ia, float b, int ib) {
+  return a > b || (a == b && ia < ib);
+}
+
+// One block per batch row: its min(count, cap) candidates into LDS, the excluded ones struck
+// (the exclusion list staged kExChunk ids at a time; rows are unsorted and candidates few, so
+// a scan), the rest scored by lane groups exactly as sddmm_cos_kernel<LPR, 4> scores an edge,
+// then each candidate's rank is the number of better candidates (ids are distinct, so the
+// order (score desc, id asc) is total and the ranks 0 .. n-1 are each taken once).
+template <int LPR>
+__global__ __launch_bounds__(256) void topk_candidates_kernel(
+    const int* __restrict__ counts, const int* __restrict__ cand, int cap,
+    const int64_t* __restrict__ user_rows, const float* __restrict__ Hu, int64_t ldu,
+    const float* __restrict__ Hi, int64_t ldi, int d, const int64_t* __restrict__ ex_ptr,
+    const int32_t* __restrict__ ex_idx, int k, float* __restrict__ out_v,
+    int64_t* __restrict__ out_i) {
+  __shared__ int ids[kCandMax];
+  __shared__ float sc[kCandMax];
+  __shared__ int ex[kExChunk];
+  __shared__ int n_valid;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int cnt = counts[b];
+  if (cnt > cap || cnt < 0) return;  // overflowed: nothing is emitted, the caller recomputes
+  const int n = cnt;
+  const int64_t urow = user_rows ? user_rows[b] : b;
+  for (int i = tid; i < n; i += 256) ids[i] = cand[b * cap + i];
+  if (tid == 0) n_valid = 0;
+  __syncthreads();
+  if (ex_ptr) {
+    const int64_t e0 = ex_ptr[urow], ne = ex_ptr[urow + 1] - e0;
+    for (int64_t base = 0; base < ne; base += kExChunk) {
+      const int m = (int)min<int64_t>(kExChunk, ne - base);
+      for (int j = tid; j < m; j += 256) ex[j] = ex_idx[e0 + base + j];
+      __syncthreads();
+      for (int i = tid; i < n; i += 256) {
+        const int c = ids[i];
+        if (c < 0) continue;
+        for (int j = 0; j < m; ++j)
+          if (ex[j] == c) { ids[i] = -1; break; }
+      }
+      __syncthreads();
+    }
+  }
+  constexpr int NPW = kWave / LPR;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int grp = lane / LPR, gl = lane % LPR;
+  const float* pu = Hu + urow * ldu;
+  for (int i0 = wave * NPW; i0 < n; i0 += 4 * NPW) {  // wave-uniform bound
+    const int i = i0 + grp;
+    const int c = i < n ? ids[i] : -1;
+    const bool ok = c >= 0;
+    const float r = cos_pair_vec4<LPR>(pu, Hi + (int64_t)(ok ? c : 0) * ldi, d, gl, ok);
+    if (gl == LPR - 1 && i < n) sc[i] = ok ? r : -INFINITY;
+  }
+  __syncthreads();
+  int mine = 0;
+  for (int i = tid; i < n; i += 256) {
+    const int c = ids[i];
+    if (c < 0) continue;
+    ++mine;
+    const float v = sc[i];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) {
+      const int cj = ids[j];
+      rank += (cj >= 0 && better(sc[j], cj, v, c)) ? 1 : 0;
+    }
+    if (rank < k) {
+      out_v[b * k + rank] = v;
+      out_i[b * k + rank] = c;
+    }
+  }
+  if (mine) atomicAdd(&n_valid, mine);
+  __syncthreads();
+  for (int r = n_valid + tid; r < k; r += 256) {
+    out_v[b * k + r] = -INFINITY;
+    out_i[b * k + r] = -1;
+  }
+}
+
+int check_score_args(const char* fn, const void* U, int64_t B, const void* V, int64_t n,
+                     int64_t dpad) {
+  GNNREC_REQUIRE(B >= 0 && n >= 0, "%s: negative size", fn);
+  GNNREC_REQUIRE(dpad >= 32 && dpad % 32 == 0 && dpad <= kRecMaxD,
+                 "%s: dpad must be a multiple of 32 in [32, %d] (got %lld)", fn, kRecMaxD,
+                 (long long)dpad);
+  GNNREC_REQUIRE(n < (int64_t(1) << 31), "%s: item ids must fit int32", fn);
+  if (B == 0 || n == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(U && V && aligned16(U) && aligned16(V), "%s: null or unaligned table", fn);
+  GNNREC_REQUIRE(((B + 127) / 128) * ((n + 127) / 128) < (int64_t(1) << 31),
+                 "%s: too many tiles for one launch", fn);
+  return GNNREC_OK;
+}
+
+}  // namespace
+}  // namespace gnnrec
+
+extern "C" int gnnrec_normalize_rows_bf16(const float* x, int64_t ld, int64_t n_rows, int64_t d,
+                                          const int64_t* row_map, void* out, int64_t dpad,
+                                          void* stream) {
+  using namespace gnnrec;
+  GNNREC_REQUIRE(n_rows >= 0 && d >= 1, "gnnrec_normalize_rows_bf16: bad size");
+  GNNREC_REQUIRE(dpad == (d + 31) / 32 * 32 && dpad <= (int64_t(1) << 20),
+                 "gnnrec_normalize_rows_bf16: dpad must be d rounded up to a multiple of 32 "
+                 "(d %lld, dpad %lld)", (long long)d, (long long)dpad);
+  if (n_rows == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(x && out && ld >= d, "gnnrec_normalize_rows_bf16: bad pointers / ld");
+  GNNREC_REQUIRE(aligned16(out), "gnnrec_normalize_rows_bf16: out must be 16-byte aligned");
+  GNNREC_REQUIRE((n_rows + 3) / 4 < (int64_t(1) << 31), "gnnrec_normalize_rows_bf16: too many rows");
+  const bool vec = d % 4 == 0 && ld % 4 == 0 && aligned16(x);
+  hipLaunchKernelGGL(normalize_rows_bf16_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0,
+                     as_stream(stream), x, ld, n_rows, (int)d, row_map,
+                     static_cast<uint16_t*>(out), (int)dpad, vec);
+  return check_launch("gnnrec_normalize_rows_bf16");
+}
+
+extern "C" int gnnrec_score_bf16_store(const void* users, int64_t n_users, const void* items,
+                                       int64_t n_items, int64_t dpad, float* out, int64_t ldo,
+                                       void* stream) {
+  using namespace gnnrec;
+  const int rc = check_score_args("gnnrec_score_bf16_store", users, n_users, items, n_items, dpad);
+  if (rc != GNNREC_OK || n_users == 0 || n_items == 0) return rc;
+  GNNREC_REQUIRE(out && ldo >= n_items, "gnnrec_score_bf16_store: bad out / ldo");
+  launch_score<false>(static_cast<const uint16_t*>(users), n_users,
+                      static_cast<const uint16_t*>(items), n_items, (int)dpad, out, ldo, nullptr,
+                      nullptr, nullptr, 0, as_stream(stream));
+  return check_launch("gnnrec_score_bf16_store");
+}
+
+extern "C" int gnnrec_score_bf16_filter(const void* users, int64_t n_users, const void* items,
+                                        int64_t n_items, int64_t dpad, const float* tau,
+                                        int32_t* counts, int32_t* cand_items, int64_t cap,
+                                        void* stream) {
+  using namespace gnnrec;
+  const int rc = check_score_args("gnnrec_score_bf16_filter", users, n_users, items, n_items, dpad);
+  if (rc != GNNREC_OK) return rc;
+  GNNREC_REQUIRE(cap >= 1 && cap <= kCandMax, "gnnrec_score_bf16_filter: cap must be in [1, %d] "
+                 "(got %lld)", kCandMax, (long long)cap);
+  if (n_users == 0 || n_items == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(tau && counts && cand_items, "gnnrec_score_bf16_filter: null pointer");
+  launch_score<true>(static_cast<const uint16_t*>(users), n_users,
+                     static_cast<const uint16_t*>(items), n_items, (int)dpad, nullptr, 0, tau,
+                     counts, cand_items, (int)cap, as_stream(stream));
+  return check_launch("gnnrec_score_bf16_filter");
+}
+
+extern "C" int gnnrec_mask_excluded_f32(float* scores, int64_t ld, int64_t n_rows, int64_t n_cols,
+                                       const int64_t* user_rows, const int64_t* exclude_indptr,
+                                       const int32_t* exclude_indices, void* stream) {
+  using namespace gnnrec;
+  GNNREC_REQUIRE(n_rows >= 0 && n_cols >= 0 && (n_rows + 3) / 4 < (int64_t(1) << 31),
+                 "gnnrec_mask_excluded_f32: bad size");
+  if (n_rows == 0 || n_cols == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(scores && ld >= n_cols, "gnnrec_mask_excluded_f32: bad scores / ld");
+  GNNREC_REQUIRE(exclude_indptr && exclude_indices,
+                 "gnnrec_mask_excluded_f32: null exclusion list");
+  hipLaunchKernelGGL(mask_excluded_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0,
+                     as_stream(stream), scores, ld, n_rows, n_cols, user_rows, exclude_indptr,
+                     exclude_indices);
+  return check_launch("gnnrec_mask_excluded_f32");
+}
+
+extern "C" int gnnrec_topk_candidates_f32(const int32_t* counts, const int32_t* cand_items,
+                                          int64_t cap, int64_t n_rows, const int64_t* user_rows,
+                                          const float* h_user, int64_t ldu, const float* h_item,
+                                          int64_t ldi, int64_t d, const int64_t* exclude_indptr,
+                                          const int32_t* exclude_indices, int64_t k,
+                                          float* out_vals, int64_t* out_idx, void* stream) {
+  using namespace gnnrec;
+  GNNREC_REQUIRE(n_rows >= 0 && n_rows < (int64_t(1) << 31),
+                 "gnnrec_topk_candidates_f32: bad row count");
+  GNNREC_REQUIRE(cap >= 1 && cap <= kCandMax, "gnnrec_topk_candidates_f32: cap must be in "
+                 "[1, %d] (got %lld)", kCandMax, (long long)cap);
+  GNNREC_REQUIRE(k >= 1 && k <= cap, "gnnrec_topk_candidates_f32: k must be in [1, cap] "
+                 "(got %lld)", (long long)k);
+  GNNREC_REQUIRE(d >= 4 && d % 4 == 0 && ldu % 4 == 0 && ldi % 4 == 0 && ldu >= d && ldi >= d,
+                 "gnnrec_topk_candidates_f32: needs d %% 4 == 0 and row strides that are "
+                 "multiples of 4 and >= d");
+  if (n_rows == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(counts && cand_items && h_user && h_item && out_vals && out_idx,
+                 "gnnrec_topk_candidates_f32: null pointer");
+  GNNREC_REQUIRE(aligned16(h_user) && aligned16(h_item),
+                 "gnnrec_topk_candidates_f32: tables must be 16-byte aligned");
+  GNNREC_REQUIRE(!exclude_indptr || exclude_indices,
+                 "gnnrec_topk_candidates_f32: exclusion indptr without indices");
+  hipStream_t s = as_stream(stream);
+  const dim3 grid((unsigned)n_rows), block(256);
+#define GNNREC_LAUNCH_CAND(LPR)                                                                 \
+  hipLaunchKernelGGL((topk_candidates_kernel<LPR>), grid, block, 0, s, counts, cand_items,      \
+                     (int)cap, user_rows, h_user, ldu, h_item, ldi, (int)d, exclude_indptr,     \
+                     exclude_indices, (int)k, out_vals, out_idx)
+  if (d <= 64) GNNREC_LAUNCH_CAND(16);  // the lane groups of gnnrec_sddmm_cos_f32
+  else if (d <= 128) GNNREC_LAUNCH_CAND(32);
+  else GNNREC_LAUNCH_CAND(64);
+#undef GNNREC_LAUNCH_CAND
+  return check_launch("gnnrec_topk_candidates_f32");
+}

@@ -623,6 +623,148 @@ void topk_rows(const Tensor& scores, int64_t k, const optional<Tensor>& exclude_
      "gnnrec_topk_rows_f32");
 }
 
+// ---------------------------------------------------------------- f1b bf16 prefilter
+void normalize_rows_bf16(const Tensor& x, const optional<Tensor>& row_map, Tensor& out) {
+  const OneDevice one_device_;
+  dev(x, "x", at::kFloat);
+  dev(row_map, "row_map", at::kLong);
+  dev(out, "out", at::kBFloat16);
+  const int64_t ldx = ld(x, "x"), d = x.size(1);
+  const int64_t n = has(row_map) ? row_map->numel() : x.size(0);
+  const int64_t dpad = (d + 31) / 32 * 32;
+  TORCH_CHECK_VALUE(d >= 1, "x must have at least one column");
+  TORCH_CHECK_VALUE(out.dim() == 2 && out.size(0) == n && out.size(1) == dpad &&
+                        out.is_contiguous(),
+                    "out must be a contiguous [", n, ", ", dpad, "] (dpad = d rounded up to 32), "
+                    "got ", out.sizes());
+  TORCH_CHECK_VALUE(!has(row_map) || row_map->is_contiguous(), "row_map must be contiguous");
+  if (meta(x)) return;
+  const c10::DeviceGuard g(x.device());
+  ck(gnnrec_normalize_rows_bf16(p<float>(x), ldx, n, d, p<int64_t>(row_map), out.data_ptr(), dpad,
+                                stream_of(x)),
+     "gnnrec_normalize_rows_bf16");
+}
+
+// the two bf16 tables of a scoring launch: [n, dpad] contiguous, one dpad, a multiple of 32
+int64_t score_tables(const Tensor& users, const Tensor& items) {
+  dev(users, "users", at::kBFloat16);
+  dev(items, "items", at::kBFloat16);
+  TORCH_CHECK_VALUE(users.dim() == 2 && items.dim() == 2 && users.is_contiguous() &&
+                        items.is_contiguous(),
+                    "users / items must be contiguous 2-D bf16 tables");
+  const int64_t dpad = users.size(1);
+  TORCH_CHECK_VALUE(items.size(1) == dpad && dpad >= 32 && dpad % 32 == 0 && dpad <= 2048,
+                    "users / items must share a dpad that is a multiple of 32 in [32, 2048], got ",
+                    users.size(1), " and ", items.size(1));
+  return dpad;
+}
+
+void score_bf16_store(const Tensor& users, const Tensor& items, Tensor& out) {
+  const OneDevice one_device_;
+  const int64_t dpad = score_tables(users, items);
+  dev(out, "out", at::kFloat);
+  const int64_t B = users.size(0), n = items.size(0);
+  const int64_t ldo = ld(out, "out");
+  TORCH_CHECK_VALUE(out.size(0) == B && out.size(1) == n, "out must be [", B, ", ", n, "], got ",
+                    out.sizes());
+  if (meta(users)) return;
+  const c10::DeviceGuard g(users.device());
+  ck(gnnrec_score_bf16_store(users.data_ptr(), B, items.data_ptr(), n, dpad, p<float>(out), ldo,
+                             stream_of(users)),
+     "gnnrec_score_bf16_store");
+}
+
+void score_bf16_filter(const Tensor& users, const Tensor& items, const Tensor& tau, Tensor& counts,
+                       Tensor& cand_items) {
+  const OneDevice one_device_;
+  const int64_t dpad = score_tables(users, items);
+  dev(tau, "tau", at::kFloat);
+  dev(counts, "counts", at::kInt);
+  dev(cand_items, "cand_items", at::kInt);
+  const int64_t B = users.size(0), n = items.size(0);
+  TORCH_CHECK_VALUE(tau.numel() == B && counts.numel() == B && tau.is_contiguous() &&
+                        counts.is_contiguous(),
+                    "tau / counts must be contiguous [", B, "]");
+  TORCH_CHECK_VALUE(cand_items.dim() == 2 && cand_items.size(0) == B && cand_items.is_contiguous(),
+                    "cand_items must be a contiguous [", B, ", cap], got ", cand_items.sizes());
+  const int64_t cap = cand_items.size(1);
+  TORCH_CHECK_VALUE(cap >= 1 && cap <= 4096, "cand_items: cap must be in [1, 4096], got ", cap);
+  if (meta(users)) return;
+  const c10::DeviceGuard g(users.device());
+  ck(gnnrec_score_bf16_filter(users.data_ptr(), B, items.data_ptr(), n, dpad, p<float>(tau),
+                              p<int32_t>(counts), p<int32_t>(cand_items), cap, stream_of(users)),
+     "gnnrec_score_bf16_filter");
+}
+
+void mask_excluded_f32(Tensor& scores, const optional<Tensor>& user_rows,
+                       const Tensor& exclude_indptr, const Tensor& exclude_indices) {
+  const OneDevice one_device_;
+  dev(scores, "scores", at::kFloat);
+  dev(user_rows, "user_rows", at::kLong);
+  dev(exclude_indptr, "exclude_indptr", at::kLong);
+  dev(exclude_indices, "exclude_indices", at::kInt);
+  const int64_t lds = ld(scores, "scores"), n_rows = scores.size(0);
+  TORCH_CHECK_VALUE(!has(user_rows) || (user_rows->numel() == n_rows && user_rows->is_contiguous()),
+                    "user_rows must be contiguous [", n_rows, "]");
+  TORCH_CHECK_VALUE(exclude_indptr.is_contiguous() && exclude_indices.is_contiguous() &&
+                        exclude_indptr.numel() >= 1 &&
+                        (has(user_rows) || exclude_indptr.numel() > n_rows),
+                    "exclude_indptr must be a contiguous indptr over the user rows");
+  if (meta(scores)) return;
+  const c10::DeviceGuard g(scores.device());
+  ck(gnnrec_mask_excluded_f32(p<float>(scores), lds, n_rows, scores.size(1), p<int64_t>(user_rows),
+                              p<int64_t>(exclude_indptr), p<int32_t>(exclude_indices),
+                              stream_of(scores)),
+     "gnnrec_mask_excluded_f32");
+}
+
+void topk_candidates_f32(const Tensor& counts, const Tensor& cand_items,
+                         const optional<Tensor>& user_rows, const Tensor& h_user,
+                         const Tensor& h_item, const optional<Tensor>& exclude_indptr,
+                         const optional<Tensor>& exclude_indices, int64_t k, Tensor& out_vals,
+                         Tensor& out_idx) {
+  const OneDevice one_device_;
+  dev(counts, "counts", at::kInt);
+  dev(cand_items, "cand_items", at::kInt);
+  dev(user_rows, "user_rows", at::kLong);
+  dev(h_user, "h_user", at::kFloat);
+  dev(h_item, "h_item", at::kFloat);
+  dev(exclude_indptr, "exclude_indptr", at::kLong);
+  dev(exclude_indices, "exclude_indices", at::kInt);
+  dev(out_vals, "out_vals", at::kFloat);
+  dev(out_idx, "out_idx", at::kLong);
+  const int64_t B = counts.numel();
+  TORCH_CHECK_VALUE(cand_items.dim() == 2 && cand_items.size(0) == B && cand_items.is_contiguous() &&
+                        counts.is_contiguous(),
+                    "cand_items must be a contiguous [", B, ", cap], got ", cand_items.sizes());
+  const int64_t cap = cand_items.size(1);
+  TORCH_CHECK_VALUE(cap >= 1 && cap <= 4096, "cand_items: cap must be in [1, 4096], got ", cap);
+  TORCH_CHECK_VALUE(k >= 1 && k <= cap, "k must be in [1, cap = ", cap, "], got ", k);
+  const int64_t ldu = ld(h_user, "h_user"), ldi = ld(h_item, "h_item"), d = h_user.size(1);
+  TORCH_CHECK_VALUE(h_item.size(1) == d && d >= 4 && d % 4 == 0 && ldu % 4 == 0 && ldi % 4 == 0,
+                    "h_user / h_item must share a feature size that is a multiple of 4 (and row "
+                    "strides too), got ", h_user.sizes(), " and ", h_item.sizes());
+  TORCH_CHECK_VALUE(!has(user_rows) || (user_rows->numel() == B && user_rows->is_contiguous()),
+                    "user_rows must be contiguous [", B, "]");
+  TORCH_CHECK_VALUE(has(user_rows) || h_user.size(0) >= B, "h_user has fewer rows than the batch");
+  TORCH_CHECK_VALUE(has(exclude_indptr) == has(exclude_indices),
+                    "exclude_indptr and exclude_indices come together");
+  TORCH_CHECK_VALUE(!has(exclude_indptr) ||
+                        (exclude_indptr->numel() == h_user.size(0) + 1 &&
+                         exclude_indptr->is_contiguous() && exclude_indices->is_contiguous()),
+                    "exclude_indptr must be a contiguous [n_user_rows + 1] over h_user's rows");
+  TORCH_CHECK_VALUE(out_vals.numel() == B * k && out_idx.numel() == B * k &&
+                        out_vals.is_contiguous() && out_idx.is_contiguous(),
+                    "out_vals / out_idx must be contiguous [", B, ", ", k, "]");
+  if (meta(counts)) return;
+  const c10::DeviceGuard g(counts.device());
+  ck(gnnrec_topk_candidates_f32(p<int32_t>(counts), p<int32_t>(cand_items), cap, B,
+                                p<int64_t>(user_rows), p<float>(h_user), ldu, p<float>(h_item), ldi,
+                                d, p<int64_t>(exclude_indptr), p<int32_t>(exclude_indices), k,
+                                p<float>(out_vals), p<int64_t>(out_idx), stream_of(counts)),
+     "gnnrec_topk_candidates_f32");
+}
+
 // ---------------------------------------------------------------- f2 training
 void gemm_tn(const Tensor& A, const Tensor& B, const optional<Tensor>& colsum, bool accumulate,
              Tensor& out, Tensor& ws, const optional<Tensor>& row_ptr) {
@@ -1580,6 +1722,15 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor(a!) out_first, Tensor(b!) out) -> ()");
   m.def("topk_rows(Tensor scores, int k, Tensor? exclude_indptr, Tensor? exclude_indices, "
         "Tensor(a!) out_vals, Tensor(b!) out_idx) -> ()");
+  m.def("normalize_rows_bf16(Tensor x, Tensor? row_map, Tensor(a!) out) -> ()");
+  m.def("score_bf16_store(Tensor users, Tensor items, Tensor(a!) out) -> ()");
+  m.def("score_bf16_filter(Tensor users, Tensor items, Tensor tau, Tensor(a!) counts, "
+        "Tensor(b!) cand_items) -> ()");
+  m.def("mask_excluded_f32(Tensor(a!) scores, Tensor? user_rows, Tensor exclude_indptr, "
+        "Tensor exclude_indices) -> ()");
+  m.def("topk_candidates_f32(Tensor counts, Tensor cand_items, Tensor? user_rows, Tensor h_user, "
+        "Tensor h_item, Tensor? exclude_indptr, Tensor? exclude_indices, int k, "
+        "Tensor(a!) out_vals, Tensor(b!) out_idx) -> ()");
   m.def("gemm_tn(Tensor A, Tensor B, Tensor(b!)? colsum, bool accumulate, Tensor(a!) out, "
         "Tensor(c!) workspace, Tensor? row_ptr=None) -> ()");
   m.def("act_backward(Tensor u, Tensor gz, int flags, Tensor(a!) out) -> ()");
@@ -1679,6 +1830,11 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("edge_mlp", &edge_mlp);                         \
   m.impl("edge_mlp_grouped", &edge_mlp_grouped);         \
   m.impl("topk_rows", &topk_rows);                       \
+  m.impl("normalize_rows_bf16", &normalize_rows_bf16);   \
+  m.impl("score_bf16_store", &score_bf16_store);         \
+  m.impl("score_bf16_filter", &score_bf16_filter);       \
+  m.impl("mask_excluded_f32", &mask_excluded_f32);       \
+  m.impl("topk_candidates_f32", &topk_candidates_f32);   \
   m.impl("gemm_tn", &gemm_tn);                           \
   m.impl("act_backward", &act_backward);                 \
   m.impl("act_backward_normed", &act_backward_normed);   \

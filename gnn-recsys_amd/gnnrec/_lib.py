@@ -148,6 +148,13 @@ SIGNATURES = {
     "gnnrec_set_prefix_pos": (_INT, [_P, _I64, _P, _P]),
     "gnnrec_clear_prefix_pos": (_INT, [_P, _I64, _P, _P]),
     "gnnrec_topk_rows_f32": (_INT, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
+    # exact top-k behind a bf16 prefilter (csrc/recommend.hip)
+    "gnnrec_normalize_rows_bf16": (_INT, [_P, _I64, _I64, _I64, _P, _P, _I64, _P]),
+    "gnnrec_score_bf16_store": (_INT, [_P, _I64, _P, _I64, _I64, _P, _I64, _P]),
+    "gnnrec_score_bf16_filter": (_INT, [_P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P]),
+    "gnnrec_mask_excluded_f32": (_INT, [_P, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "gnnrec_topk_candidates_f32": (_INT, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _I64, _I64, _P,
+                                          _P, _I64, _P, _P, _P]),
     "gnnrec_synth_edges": (_INT, [_U64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     "gnnrec_margin_loss_blocks": (_I64, [_I64]),
     "gnnrec_margin_loss_f32": (_INT, [_P, _P, _I64, _I64, _F32, _P, _P, _INT, _P, _P, _P, _I64,

@@ -1708,3 +1708,75 @@ try:
     _lib.torch_ops()
 except _lib.GnnrecLibraryError:
     pass
+
+
+# ---- f1b: exact top-k behind a bf16 MFMA prefilter (csrc/recommend.hip) ----
+def normalize_rows_bf16(x: torch.Tensor, row_map: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Rows of x (row_map[r] of x when given) divided by max(norm, 1e-12) and rounded to bf16
+    (nearest even) -> [n, dpad], dpad = d rounded up to a multiple of 32, the pad zero."""
+    _dev(x, "x", torch.float32)
+    _rowmajor(x, "x")
+    if row_map is not None:
+        _dev(row_map, "row_map", torch.int64)
+        row_map = row_map.contiguous()
+    n = x.shape[0] if row_map is None else row_map.numel()
+    out = torch.empty((n, (x.shape[1] + 31) // 32 * 32), dtype=torch.bfloat16, device=x.device)
+    _T().normalize_rows_bf16(x, row_map, out)
+    return out
+
+
+def score_bf16_store(users: torch.Tensor, items: torch.Tensor) -> torch.Tensor:
+    """Approximate cosines of two normalize_rows_bf16 tables, bf16 products accumulated in
+    fp32 on the MFMA -> fp32 [n_users, n_items]."""
+    _dev(users, "users", torch.bfloat16)
+    _dev(items, "items", torch.bfloat16)
+    out = torch.empty((users.shape[0], items.shape[0]), dtype=torch.float32, device=users.device)
+    _T().score_bf16_store(users, items, out)
+    return out
+
+
+def score_bf16_filter(users: torch.Tensor, items: torch.Tensor, tau: torch.Tensor,
+                      counts: torch.Tensor, cand_items: torch.Tensor) -> None:
+    """The same scores, none written: item v joins row u's list in cand_items [B, cap]
+    (int32) where the score is >= tau[u] - 2 eps; counts [B] (int32, zeroed by the caller)
+    counts every passing item, past cap too (counts[u] > cap: the row overflowed)."""
+    _dev(users, "users", torch.bfloat16)
+    _dev(items, "items", torch.bfloat16)
+    _dev(tau, "tau", torch.float32)
+    _dev(counts, "counts", torch.int32)
+    _dev(cand_items, "cand_items", torch.int32)
+    _T().score_bf16_filter(users, items, tau, counts, cand_items)
+
+
+def mask_excluded(scores: torch.Tensor, user_rows: Optional[torch.Tensor],
+                  exclude_indptr: torch.Tensor, exclude_indices: torch.Tensor) -> None:
+    """scores[r][c] = -inf, in place, for the items c of row r's user (user_rows[r], or r) in
+    the exclusion CSR (int64 indptr over user rows, int32 item ids) that are columns."""
+    _dev(scores, "scores", torch.float32)
+    _dev(exclude_indptr, "exclude_indptr", torch.int64)
+    _dev(exclude_indices, "exclude_indices", torch.int32)
+    _T().mask_excluded_f32(scores, user_rows, exclude_indptr, exclude_indices)
+
+
+def topk_candidates(counts: torch.Tensor, cand_items: torch.Tensor,
+                    user_rows: Optional[torch.Tensor], h_user: torch.Tensor,
+                    h_item: torch.Tensor, k: int, exclude_indptr: Optional[torch.Tensor] = None,
+                    exclude_indices: Optional[torch.Tensor] = None,
+                    out_vals: Optional[torch.Tensor] = None,
+                    out_idx: Optional[torch.Tensor] = None):
+    """Per batch row: its candidates minus the user's excluded items (a CSR over h_user's
+    rows, int32 ids), rescored with the fp32 cosine (bitwise sddmm_cos) and ranked by
+    (score desc, item asc) -> (vals [B, k], idx [B, k]), padded with (-inf, -1).  Rows with
+    counts > cap are left unwritten."""
+    _dev(counts, "counts", torch.int32)
+    _dev(cand_items, "cand_items", torch.int32)
+    _dev(h_user, "h_user", torch.float32)
+    _dev(h_item, "h_item", torch.float32)
+    B = counts.numel()
+    if out_vals is None:
+        out_vals = torch.empty((B, k), dtype=torch.float32, device=counts.device)
+    if out_idx is None:
+        out_idx = torch.empty((B, k), dtype=torch.int64, device=counts.device)
+    _T().topk_candidates_f32(counts, cand_items, user_rows, h_user, h_item, exclude_indptr,
+                             exclude_indices, int(k), out_vals, out_idx)
+    return out_vals, out_idx

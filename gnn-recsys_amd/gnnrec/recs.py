@@ -10,6 +10,11 @@ every item in one fp32 MFMA GEMM of L2-normalised embeddings (gnnrec_gemm_f32),
 or by the re-associated MLP head (gnnrec_edge_mlp_f32), and
 gnnrec_topk_rows_f32 selects the k best non-bought items per user on the
 device.  Only the [users, k] result leaves the GPU.
+
+`recommend` / `recommend_for_graph` / `recs_to_metrics_device` serve many users (the
+reference's `--user_ids all`) on device tensors: the same ranking for the cosine head, bit
+for bit, from a bf16 MFMA prefilter and an fp32 rescoring of the few items it cannot rule
+out, with no score matrix.
 """
 from __future__ import annotations
 
@@ -103,6 +108,190 @@ def get_recs(g, h, model, embed_dim, k, user_ids, already_bought_dict,
             row = top[r]
             recs[u] = row[row >= 0]
     return recs
+
+
+# ---- exact top-k behind a bf16 MFMA prefilter (csrc/recommend.hip) ----------
+# |a - score| <= REC_EPS for the approximate score a (bf16 operands, fp32 accumulation) of
+# two normalised rows with d <= REC_MAX_D; the derivation is in csrc/recommend.hip and
+# DESIGN.md §16.  The library holds the constant it filters with; this one is for callers.
+REC_EPS = 2.0 ** -7 + 2.0 ** -11
+REC_MAX_D = 2048
+REC_MAX_CAP = 4096
+
+
+def _rows_exact(h_user, h_item, k, rows, exclude, vals, idx, out_pos):
+    """The fallback, always exact: every item scored with the fp32 cosine for the user rows
+    `rows` (int64 device tensor), excluded items masked to -inf, topk_rows; results into
+    vals/idx at rows `out_pos`."""
+    n_items, dev = h_item.shape[0], h_item.device
+    if rows.numel() == 0:
+        return
+    if n_items == 0:
+        vals[out_pos] = float('-inf')
+        idx[out_pos] = -1
+        return
+    all_items = torch.arange(n_items, device=dev)
+    grouped = ops.cos_grouped_ok(h_user, h_item)
+    step = max(1, (1 << 26) // n_items)
+    for c0 in range(0, rows.numel(), step):
+        r = rows[c0:c0 + step].contiguous()
+        G = r.numel()
+        dst = all_items.repeat(G)
+        if grouped:
+            _, sc = ops.sddmm_cos_grouped(r, None, n_items, dst, h_user, h_item)
+        else:
+            sc = ops.sddmm_cos(r.repeat_interleave(n_items), dst, h_user, h_item)
+        sc = sc.view(G, n_items)
+        if exclude is not None:
+            ops.mask_excluded(sc, r, exclude[0], exclude[1])
+        v, i = topk_rows(sc, k)
+        i = torch.where(v == float('-inf'), torch.full_like(i, -1), i)  # masked or past the end
+        pos = out_pos[c0:c0 + step]
+        vals[pos] = v
+        idx[pos] = i
+
+
+def recommend(h_user, h_item, k, user_rows=None, exclude=None, *, batch_size=8192,
+              sample=65536, cand_cap=1024, return_stats=False):
+    """The k best items per user by (cosine desc, item id asc), excluded items removed —
+    the lists of an exhaustive fp32 ranking, bit for bit — on device tensors and without a
+    score matrix.
+
+    h_user [n_users, d], h_item [n_items, d]: fp32 device tables (raw embeddings; the cosine
+    divides by max(norm, 1e-12) as CosinePrediction does).  user_rows: int64 device tensor of
+    rows of h_user to serve (None: all of them, in order; repeats allowed).  exclude:
+    (indptr int64 [n_users + 1], indices int32) over h_user's rows, unsorted rows allowed —
+    the graph's g.in_csr('bought-by')[:2] — or None.
+    -> (idx int64 [U, k], vals fp32 [U, k]) [, stats]; rows with fewer than k eligible items
+    are padded with (-1, -inf).  vals are the values of ops.sddmm_cos for the pairs.
+
+    Per batch of `batch_size` users: both tables normalised and rounded to bf16, approximate
+    scores (bf16 MFMA, fp32 accumulation) of the item prefix [0, min(sample, n_items)) stored
+    and their k-th best non-excluded value taken as tau; one pass over all items keeps the
+    items with approximate score >= tau - 2 REC_EPS (a superset of the exact top k: |approx -
+    exact| <= REC_EPS), at most `cand_cap` per user; those are rescored in fp32 and ranked.
+    Rows that kept more than cand_cap items (and the whole call when k > cand_cap / 4,
+    d > REC_MAX_D or d % 4 != 0) are recomputed exhaustively with sddmm_cos + topk_rows, so
+    the result never depends on the filter.  The host reads the device once per call (the
+    per-row candidate counts, after the last batch).
+
+    Non-finite embeddings are outside the contract: a NaN or inf score has no place in the
+    ranking, and the filter's comparison drops it silently.
+
+    stats (return_stats=True): candidates_mean, candidates_max (kept items per row, counted
+    past the cap), overflow_rows, sample, cand_cap, fast_path."""
+    ops._dev(h_user, 'h_user', torch.float32)
+    ops._dev(h_item, 'h_item', torch.float32)
+    if h_user.dim() != 2 or h_item.dim() != 2 or h_user.shape[1] != h_item.shape[1]:
+        raise ValueError(f'h_user / h_item must be 2-D with one feature size, got '
+                         f'{tuple(h_user.shape)} and {tuple(h_item.shape)}')
+    k, batch_size, sample, cand_cap = int(k), int(batch_size), int(sample), int(cand_cap)
+    if k < 1 or batch_size < 1 or sample < 1 or not 1 <= cand_cap <= REC_MAX_CAP:
+        raise ValueError(f'recommend: k, batch_size and sample must be >= 1 and cand_cap in '
+                         f'[1, {REC_MAX_CAP}]')
+    dev = h_item.device
+    h_user, h_item = h_user.contiguous(), h_item.contiguous()
+    n_items, d = h_item.shape
+    if user_rows is None:
+        user_rows = torch.arange(h_user.shape[0], device=dev)
+    ops._dev(user_rows, 'user_rows', torch.int64)
+    user_rows = user_rows.reshape(-1).contiguous()
+    if exclude is not None:
+        ex_ptr, ex_idx = exclude
+        ops._dev(ex_ptr, 'exclude indptr', torch.int64)
+        ops._dev(ex_idx, 'exclude indices', torch.int32)
+        if ex_ptr.numel() != h_user.shape[0] + 1:
+            raise ValueError(f'exclude indptr must have n_users + 1 = {h_user.shape[0] + 1} '
+                             f'entries, got {ex_ptr.numel()}')
+        exclude = (ex_ptr.contiguous(), ex_idx.contiguous())
+    U = user_rows.numel()
+    vals = torch.empty((U, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((U, k), dtype=torch.int64, device=dev)
+    m = min(sample, n_items)
+    stats = {'candidates_mean': 0.0, 'candidates_max': 0, 'overflow_rows': 0, 'sample': m,
+             'cand_cap': cand_cap, 'fast_path': False}
+    fast = (k <= cand_cap // 4 and d <= REC_MAX_D and d % 4 == 0 and d >= 4 and n_items > 0
+            and U > 0)
+    if not fast:
+        _rows_exact(h_user, h_item, k, user_rows, exclude, vals, idx, torch.arange(U, device=dev))
+        return (idx, vals, stats) if return_stats else (idx, vals)
+    stats['fast_path'] = True
+    items_bf = ops.normalize_rows_bf16(h_item)      # converted once per call
+    prefix_bf = items_bf[:m]
+    counts = torch.zeros(U, dtype=torch.int32, device=dev)
+    for b0 in range(0, U, batch_size):
+        rows = user_rows[b0:b0 + batch_size]
+        B = rows.numel()
+        users_bf = ops.normalize_rows_bf16(h_user, rows)
+        s = ops.score_bf16_store(users_bf, prefix_bf)
+        if exclude is not None:
+            ops.mask_excluded(s, rows, exclude[0], exclude[1])
+        tau = topk_rows(s, k)[0][:, k - 1].contiguous()  # -inf: fewer than k eligible there
+        del s
+        cand = torch.empty((B, cand_cap), dtype=torch.int32, device=dev)
+        ops.score_bf16_filter(users_bf, items_bf, tau, counts[b0:b0 + B], cand)
+        ops.topk_candidates(counts[b0:b0 + B], cand, rows, h_user, h_item, k,
+                            None if exclude is None else exclude[0],
+                            None if exclude is None else exclude[1],
+                            vals[b0:b0 + B], idx[b0:b0 + B])
+    cnt = counts.cpu().numpy()                       # the call's one readback
+    over = np.nonzero(cnt > cand_cap)[0]
+    if over.size:
+        pos = torch.from_numpy(over).to(dev)
+        _rows_exact(h_user, h_item, k, user_rows[pos], exclude, vals, idx, pos)
+    stats.update(candidates_mean=float(cnt.mean()), candidates_max=int(cnt.max()),
+                 overflow_rows=int(over.size))
+    return (idx, vals, stats) if return_stats else (idx, vals)
+
+
+def recommend_for_graph(g, h, k, user_ids=None, etype='bought-by', **kw):
+    """recommend() for the users of a graph, the items each has an `etype` edge from
+    removed: the exclusion lists are the graph's own dst-major CSR of
+    ('item', etype, 'user') (indptr over users, int32 item ids), already on the device.
+    h: {'user': ..., 'item': ...} embeddings; user_ids: ids to serve (None: every user)."""
+    dev = h['item'].device
+    ex_ptr, ex_idx = g.in_csr(etype)[:2]
+    exclude = (ex_ptr.to(dev), ex_idx.to(dev))
+    if user_ids is not None:
+        user_ids = torch.as_tensor(user_ids, dtype=torch.int64, device=dev)
+    return recommend(h['user'], h['item'], k, user_ids, exclude, **kw)
+
+
+def recs_to_metrics_device(idx, user_rows, gt_indptr, gt_indices, n_items):
+    """precision / recall / coverage of recs_to_metrics (reference src/metrics.py:81-107)
+    from device tensors: idx [U, k] the lists of recommend() (-1 = no item), user_rows [U]
+    their users (None: row r is user r; each user once, as in the reference's dict),
+    (gt_indptr int64 [n_users + 1], gt_indices) the ground-truth items per user, duplicates
+    kept.  precision: recommended items found in the user's ground truth / recommended
+    items; recall: ground-truth edges (with multiplicity) of the served users whose item is
+    in the user's list / those edges; coverage: distinct recommended items / n_items."""
+    dev = idx.device
+    U, k = idx.shape
+    n_users = gt_indptr.numel() - 1
+    if user_rows is None:
+        user_rows = torch.arange(U, device=dev)
+    user_rows = user_rows.to(dev).reshape(-1)
+    gt_indptr = gt_indptr.to(dev)
+    gt_items = gt_indices.to(dev).to(torch.int64)
+    E = gt_items.numel()
+    deg = gt_indptr[1:] - gt_indptr[:-1]
+    gt_users = torch.repeat_interleave(torch.arange(n_users, device=dev), deg, output_size=E)
+    ok = idx >= 0
+    rec_items = idx[ok]
+    rec_users = user_rows.unsqueeze(1).expand(U, k)[ok]
+    # precision: (item -> user) membership in the ground truth
+    ip, ix = ops.membership_csr(gt_items, gt_users, n_items, n_users)
+    hit = ops.has_edges(ip, ix, n_items, rec_items, rec_users)
+    precision = int(hit.sum()) / int(rec_items.numel())
+    # recall: ground-truth edges of the served users found in the lists
+    served = torch.zeros(n_users, dtype=torch.bool, device=dev)
+    served[user_rows] = True
+    e_ok = served[gt_users]
+    ip, ix = ops.membership_csr(rec_items, rec_users, n_items, n_users)
+    found = ops.has_edges(ip, ix, n_items, gt_items[e_ok], gt_users[e_ok])
+    recall = int(found.sum()) / int(e_ok.sum())
+    coverage = int(torch.unique(rec_items).numel()) / n_items
+    return precision, recall, coverage
 
 
 def recs_to_metrics(recs, ground_truth_dict, g):

@@ -646,6 +646,52 @@ int gnnrec_topk_rows_f32(const float* scores, int64_t ld, int64_t n_rows, int64_
                          int64_t k, const int64_t* exclude_indptr, const int64_t* exclude_indices,
                          float* out_vals, int64_t* out_idx, void* stream);
 
+/* ---- f1b: exact top-k with a bf16 MFMA prefilter ---------------------------
+ * The ranking of gnnrec_topk_rows_f32 over score(u, v) = the value of
+ * gnnrec_sddmm_cos_f32 for the pair, without writing the score matrix
+ * (csrc/recommend.hip holds the error bound and the filter's proof).
+ *
+ * out[n_rows, dpad] (bf16, 16-byte aligned) = rows of x[.., d] (row r of the
+ * output is row row_map[r] of x, or row r when row_map is NULL) divided by
+ * max(norm, 1e-12) in fp32 and rounded to nearest even; dpad = d rounded up
+ * to a multiple of 32, the pad columns zero. */
+int gnnrec_normalize_rows_bf16(const float* x, int64_t ld, int64_t n_rows, int64_t d,
+                               const int64_t* row_map, void* out, int64_t dpad, void* stream);
+/* a(u, v) = sum_c users[u][c] items[v][c] (bf16 operands [n, dpad] from
+ * gnnrec_normalize_rows_bf16, fp32 accumulation, dpad a multiple of 32 up to
+ * 2048) for every pair, written as fp32 out[n_users, n_items] (row stride ldo). */
+int gnnrec_score_bf16_store(const void* users, int64_t n_users, const void* items,
+                            int64_t n_items, int64_t dpad, float* out, int64_t ldo,
+                            void* stream);
+/* scores[r][c] = -inf for every c in exclude_indices[exclude_indptr[u] .. exclude_indptr[u+1])
+ * with 0 <= c < n_cols (u = user_rows[r], or r when user_rows is NULL; the CSR of
+ * gnnrec_topk_candidates_f32): a plain top-k over the masked rows then ranks the eligible
+ * columns only, and its k-th value is -inf where fewer than k are eligible. */
+int gnnrec_mask_excluded_f32(float* scores, int64_t ld, int64_t n_rows, int64_t n_cols,
+                             const int64_t* user_rows, const int64_t* exclude_indptr,
+                             const int32_t* exclude_indices, void* stream);
+/* The same scores, none written: item v is appended to row u's candidate list where
+ * a(u, v) >= tau[u] - 2 eps (eps = 2^-7 + 2^-11 bounds |a - score|).  counts[n_users]
+ * (int32, zero before the first call) takes one increment per passing item and keeps
+ * counting past cap — counts[u] > cap marks an overflowed row — while ids are stored
+ * only into the row's cap slots of cand_items[n_users, cap] (int32, in no fixed order).
+ * cap <= 4096. */
+int gnnrec_score_bf16_filter(const void* users, int64_t n_users, const void* items,
+                             int64_t n_items, int64_t dpad, const float* tau, int32_t* counts,
+                             int32_t* cand_items, int64_t cap, void* stream);
+/* Per batch row r with counts[r] <= cap: its candidates minus the items in
+ * exclude_indices[exclude_indptr[u] .. exclude_indptr[u+1]) (u = user_rows[r], or r when
+ * user_rows is NULL; a CSR over the rows of h_user with int32 item ids, unsorted; both
+ * pointers may be NULL), rescored with the fp32 cosine of h_user[u] and h_item[v] (bitwise
+ * gnnrec_sddmm_cos_f32; d % 4 == 0, 16-byte aligned rows) and ranked by (score desc, item
+ * asc): out_vals / out_idx [n_rows, k], padded with (-inf, -1).  Rows with counts[r] > cap
+ * are left unwritten.  1 <= k <= cap <= 4096. */
+int gnnrec_topk_candidates_f32(const int32_t* counts, const int32_t* cand_items, int64_t cap,
+                               int64_t n_rows, const int64_t* user_rows, const float* h_user,
+                               int64_t ldu, const float* h_item, int64_t ldi, int64_t d,
+                               const int64_t* exclude_indptr, const int32_t* exclude_indices,
+                               int64_t k, float* out_vals, int64_t* out_idx, void* stream);
+
 /* ---- f2: projection backward (training step) -----------------------------
  * Replace torch autograd of the reference's nn.Linear layers and the
  * relu/normalise epilogue when train_model calls loss.backward()
