@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "gather.hpp"
 
 namespace gnnrec {
 
@@ -46,4 +47,44 @@ __host__ __device__ inline bool drop_keep(uint64_t word, int c, uint32_t T) {
   return (uint32_t)((word >> (16 * (c & 3))) & 0xFFFFu) >= T;
 }
 
+// what a kernel that masks needs (dropout.hip's row kernel, spmm.hip's gathers)
+struct DropArgs {
+  const uint64_t* keys;  // device: one key per stream of the forward call
+  int index;             // this launch's stream
+  uint32_t T;
+  float scale;
+  int Q;  // words per row: ceil(d / 4)
+};
+
+namespace {
+
+// zero the dropped columns of the fragment at column col of a row whose word is `word`
+// (VEC == 4: col % 4 == 0, the word's four draws are the fragment's columns)
+template <int VEC>
+__device__ __forceinline__ void drop_frag(Frag<VEC>& f, uint64_t word, int col, uint32_t T) {
+  if constexpr (VEC == 4) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+      if (!drop_keep(word, v, T)) f.v[v] = 0.f;
+  } else {
+    if (!drop_keep(word, col, T)) f.v[0] = 0.f;
+  }
+}
+
+// gather_range's hook (gather.hpp): the mask of each gathered source row
+struct DropSrcMask {
+  static constexpr bool kOn = true;
+  uint64_t key;
+  uint32_t T;
+  int Q;
+  __device__ __forceinline__ uint64_t word(int src, int col) const {
+    return drop_word(key, src, Q, col >> 2);
+  }
+  template <int VEC>
+  __device__ __forceinline__ void apply(Frag<VEC>& f, uint64_t w, int col) const {
+    drop_frag<VEC>(f, w, col, T);
+  }
+};
+
+}  // namespace
 }  // namespace gnnrec

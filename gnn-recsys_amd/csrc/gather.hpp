@@ -1,6 +1,7 @@
-// Shared device helpers of the neighbour gather (a1): used by the plain
-// aggregation kernels (spmm.hip) and the fused aggregate+project kernel
-// (spmm_project.hip), so both reduce every row in the same fixed order.
+// Shared device helpers of the neighbour gather (a1): used by the aggregation
+// kernels (spmm.hip: dense, packed and dropout-masked source rows) and the fused
+// aggregate+project kernels (spmm_project.hip, spmm_pair_mfma.hip), so all reduce
+// every row in the same fixed order.
 #pragma once
 #include "common.hpp"
 #include "pack_rows.hpp"
@@ -65,16 +66,25 @@ __device__ __forceinline__ float combine(float a, float b) {
   return REDUCE == GNNREC_REDUCE_MAX ? fmaxf(a, b) : a + b;
 }
 
+// A gather's per-source-row hook: none.  One that is kOn (dropout.hpp's DropSrcMask) gives
+// word(src, col), a value of the source row alone, and apply(frag, word, col).
+struct NoSrcHook {
+  static constexpr bool kOn = false;
+};
+
 // Per-lane partial reduction of edges [beg, end) (lane group grp takes k % NPI == grp).
 // PRE: the first 64 indices of the range were loaded by the caller (lane k holds
 // indices[beg + k]) — a row kernel prefetches them for row i+1 while row i gathers.
-template <int LPR, int VEC, int REDUCE, bool WEIGHTED, int UNROLL, bool PRE = false>
+// hook: applied to every gathered fragment; its words depend on the broadcast indices only,
+// so they are computed after a step's UNROLL loads are issued, while those are in flight.
+template <int LPR, int VEC, int REDUCE, bool WEIGHTED, int UNROLL, bool PRE = false,
+          class Hook = NoSrcHook>
 __device__ __forceinline__ void gather_range(int64_t beg, int64_t end,
                                              const int32_t* __restrict__ indices,
                                              const float* __restrict__ ew,
                                              const float* __restrict__ X, int64_t ldx, int col,
                                              bool colok, int lane, int grp, Frag<VEC>& acc,
-                                             int pre_idx = 0) {
+                                             int pre_idx = 0, const Hook& hook = {}) {
   constexpr int NPI = kWave / LPR;
   for (int64_t base = beg; base < end; base += 64) {
     const int cnt = (int)((end - base) < 64 ? (end - base) : 64);
@@ -86,22 +96,29 @@ __device__ __forceinline__ void gather_range(int64_t beg, int64_t end,
     for (int j = 0; j < cnt; j += NPI * UNROLL) {
       Frag<VEC> val[UNROLL];
       bool ok[UNROLL];
+      int src[UNROLL];
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
         const int k = j + u * NPI + grp;
         ok[u] = (k < cnt) && colok;
-        const int src = edge_bcast<NPI>(myidx, j + u * NPI, grp);
+        src[u] = edge_bcast<NPI>(myidx, j + u * NPI, grp);
         if (ok[u]) {
-          load_frag<VEC>(val[u], X + (int64_t)src * ldx + col);
+          load_frag<VEC>(val[u], X + (int64_t)src[u] * ldx + col);
         } else {
 #pragma unroll
           for (int v = 0; v < VEC; ++v) val[u].v[v] = 0.f;
         }
       }
+      [[maybe_unused]] uint64_t word[UNROLL];
+      if constexpr (Hook::kOn) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) word[u] = hook.word(src[u], col);
+      }
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
         float w = 1.f;
         if constexpr (WEIGHTED) w = edge_bcast<NPI>(myw, j + u * NPI, grp);
+        if constexpr (Hook::kOn) hook.apply(val[u], word[u], col);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
           const float m = WEIGHTED ? val[u].v[v] * w : val[u].v[v];

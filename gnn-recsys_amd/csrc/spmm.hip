@@ -20,7 +20,16 @@
 // Heavy rows (deg > split, e.g. Zipf-popular items) are skipped by the row
 // kernel and reduced instead by one wave per `split`-edge chunk into a
 // workspace, then combined per row in chunk order (deterministic two-phase).
+//
+// One kernel family — spmm_csr_kernel (rows), spmm_chunk_kernel and spmm_combine_kernel
+// (heavy rows) and group_rows (a lane group per low-degree row) — under a compile-time
+// policy (below): a dense source table (gnnrec_spmm_csr_f32 and its split / planned / live
+// forms), a packed one (gnnrec_spmm_csr_packed_f32, pack_rows.hpp), and the dense table
+// with the training dropout mask inside (gnnrec_spmm_csr_dropout_live_f32 and its planned
+// form, dropout.hpp).  The reduction order is written once, so every form gives the same
+// bits for the same rows.  spmm_csr2_kernel walks two relations with the same row code.
 #include "common.hpp"
+#include "dropout.hpp"
 #include "gather.hpp"
 #include "rowq.hpp"
 #include <cmath>
@@ -42,6 +51,9 @@ constexpr int64_t kRqTicketEdges = 512;
 // 444 µs queued vs 472 static (tools/micro/spmm_one.py, profiles/r03_spmm_rowq.txt).
 constexpr int64_t kRqMinRowsPerWave = 32;
 constexpr int kRowChunk = 0;
+// Mean degree up to which the group form takes a d <= 64 CSR (the row kernel's group_deg
+// argument: as a constant in the kernel it costs the LPR 16 sum kernel a wave per SIMD).
+constexpr int64_t kGroupMaxAvgDeg = 16;
 
 // rows per ticket: about kRqTicketEdges edges, but at least 4 tickets per wave of the grid.
 // A minibatch block (100k rows at 10 edges) at 51 rows per ticket fed 1960 of the grid's
@@ -54,6 +66,227 @@ __device__ __forceinline__ int ticket_rows(int64_t avg_deg, int64_t n_dst, int64
   return (int)(c < 1 ? 1 : c > 64 ? 64 : c);
 }
 
+// The heavy-row plan of a launch: rows of more than `split` edges, cut into chunks of `split`
+// edges.  Host-built: the arrays and their exact sizes.  Device-built (`counts` set): one
+// buffer {n_heavy, n_chunks | heavy_rows[cap_h] | chunk_ptr[cap_h + 1] | chunk_row[cap_c]};
+// n_heavy / n_chunks are then the capacities the grids cover, the real counts are counts[0..1].
+struct HeavyPlan {
+  int64_t split;
+  const int64_t* heavy_rows;
+  int64_t n_heavy;
+  const int64_t* chunk_ptr;
+  const int64_t* chunk_row;
+  int64_t n_chunks;
+  const int64_t* counts;
+
+  static HeavyPlan on_device(int64_t split, const int64_t* plan, int64_t cap_h, int64_t cap_c) {
+    return {split, plan + 2, cap_h, plan + 2 + cap_h, plan + 3 + 2 * cap_h, cap_c, plan};
+  }
+  __device__ int64_t rows() const { return counts ? counts[0] : n_heavy; }   // < 0: overflowed
+  __device__ int64_t chunks() const { return counts ? counts[1] : n_chunks; }  // 0 then
+  // chunk c -> its heavy row's output row and the chunk's edges [beg, end)
+  __device__ __forceinline__ int64_t range(int64_t c, const int64_t* __restrict__ indptr,
+                                           int64_t& beg, int64_t& end) const {
+    const int64_t h = chunk_row[c];
+    const int64_t row = heavy_rows[h];
+    const int64_t rbeg = indptr[row], rend = indptr[row + 1];
+    beg = rbeg + (c - chunk_ptr[h]) * split;
+    end = (beg + split < rend) ? beg + split : rend;
+    return row;
+  }
+};
+
+// ---- the policy of a kernel family ---------------------------------------------------------
+// The row, chunk and combine kernels and the group form below are written once; a policy P,
+// passed to the kernel by value, says
+//   * how edges [beg, end) are gathered into a lane's partial: P::gather<PRE>;
+//   * how a finished row is written: P::Finish, p.fin(acc, &out[row, col], flags, row, deg,
+//     col), which also owns a mask of the gathered rows (src_mask(): gather_range's hook) and
+//     what begin() loads once per kernel; the combine kernel ends with the same finish;
+//   * what is compiled in: kQueue (the row queue's walk), kLive (a device row count),
+//     kGroup (the group form), kStageWords (LDS words per wave for the gather).
+
+// plain: finalize, accumulate into what the table holds (GNNREC_SPMM_ACCUM), store
+template <int VEC_, int REDUCE_>
+struct StoreRow {
+  static constexpr int VEC = VEC_, REDUCE = REDUCE_;
+  __device__ __forceinline__ void begin() {}
+  __device__ __forceinline__ NoSrcHook src_mask() const { return {}; }
+  // acc: the reduced row `row` (deg edges) at column col -> o = &out[row, col]
+  __device__ __forceinline__ void operator()(Frag<VEC>& acc, float* __restrict__ o, int flags,
+                                             int64_t, int64_t deg, int) const {
+    finalize<VEC, REDUCE>(acc, deg, flags & GNNREC_SPMM_EMPTY_NEGINF);
+    if (flags & GNNREC_SPMM_ACCUM) accumulate_into<VEC, REDUCE>(acc, o);
+    store_frag<VEC>(o, acc);
+  }
+};
+
+// dropout (sum / mean): the mean's division, the output row's mask (WHERE == OUT), the scale,
+// then the accumulate and the store; WHERE == SRC masks every gathered row instead
+template <int VEC_, int REDUCE_, int WHERE>
+struct DropStoreRow {
+  static constexpr int VEC = VEC_, REDUCE = REDUCE_;
+  DropArgs da;
+  uint64_t key;
+  __device__ __forceinline__ void begin() { key = da.keys[da.index]; }
+  __device__ __forceinline__ auto src_mask() const {
+    if constexpr (WHERE == GNNREC_DROPOUT_SRC) return DropSrcMask{key, da.T, da.Q};
+    else return NoSrcHook{};
+  }
+  __device__ __forceinline__ void operator()(Frag<VEC>& acc, float* __restrict__ o, int flags,
+                                             int64_t row, int64_t deg, int col) const {
+    finalize<VEC, REDUCE>(acc, deg, 0);
+    if constexpr (WHERE == GNNREC_DROPOUT_OUT)
+      drop_frag<VEC>(acc, drop_word(key, row, da.Q, col >> 2), col, da.T);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc.v[v] *= da.scale;
+    if (flags & GNNREC_SPMM_ACCUM) accumulate_into<VEC, REDUCE>(acc, o);
+    store_frag<VEC>(o, acc);
+  }
+};
+
+// a dense source table X (optionally edge weights): gather_range
+template <int LPR_, int VEC_, int REDUCE_, bool WEIGHTED_, int UNROLL_, class Finish_, bool QUEUE>
+struct DenseAgg {
+  static constexpr int LPR = LPR_, VEC = VEC_, REDUCE = REDUCE_, UNROLL = UNROLL_;
+  static constexpr bool WEIGHTED = WEIGHTED_;
+  // the group form at d in (16, 64]; at LPR 4 its 16 partials cost occupancy
+  static constexpr bool kQueue = QUEUE, kLive = true, kGroup = VEC == 4 && (LPR == 8 || LPR == 16);
+  static constexpr int kStageWords = 0;
+  using Finish = Finish_;
+  const float* ew;
+  const float* X;
+  int64_t ldx;
+  Finish fin;
+  __device__ __forceinline__ void begin() { fin.begin(); }
+  template <bool PRE>
+  __device__ __forceinline__ void gather(int64_t beg, int64_t end,
+                                         const int32_t* __restrict__ indices, int col, bool colok,
+                                         int lane, int grp, Frag<VEC>& acc, int idx,
+                                         uint32_t*) const {
+    gather_range<LPR, VEC, REDUCE, WEIGHTED, UNROLL, PRE>(beg, end, indices, ew, X, ldx, col,
+                                                          colok, lane, grp, acc, idx,
+                                                          fin.src_mask());
+  }
+};
+// inference: the row queue; training under dropout: the static schedule only (the queue's
+// walk would cost drop rows at LPR 32 a wave per SIMD)
+template <int LPR, int VEC, int REDUCE, bool WEIGHTED, int UNROLL>
+using PlainAgg = DenseAgg<LPR, VEC, REDUCE, WEIGHTED, UNROLL, StoreRow<VEC, REDUCE>, true>;
+template <int LPR, int VEC, int REDUCE, bool WEIGHTED, int UNROLL, int WHERE>
+using DropAgg =
+    DenseAgg<LPR, VEC, REDUCE, WEIGHTED, UNROLL, DropStoreRow<VEC, REDUCE, WHERE>, false>;
+
+// a packed source table (pack_rows.hpp): d = 128, sum / mean, unweighted.  gather_range_packed
+// adds the same rows in the same order as gather_range, so every output is bitwise what the
+// dense policy writes from X.  A table whose packed_ok is 0 (too many rows that do not fit)
+// is read through the dense loop.
+template <int REDUCE_, int UNROLL_>
+struct PackedAgg {
+  static constexpr int LPR = 32, VEC = 4, REDUCE = REDUCE_, UNROLL = UNROLL_;
+  static constexpr bool WEIGHTED = false;
+  static constexpr bool kQueue = true, kLive = false, kGroup = false;
+  static constexpr int kStageWords = UNROLL * 2 * kPackWords;  // a step's UNROLL row pairs
+  using Finish = StoreRow<4, REDUCE>;
+  const uint32_t* P;
+  const int* pstatus;
+  const float* X;
+  int64_t ldx;
+  Finish fin;
+  bool packed;
+  __device__ __forceinline__ void begin() { packed = pstatus[0] != 0; }  // uniform
+  template <bool PRE>
+  __device__ __forceinline__ void gather(int64_t beg, int64_t end,
+                                         const int32_t* __restrict__ indices, int col, bool,
+                                         int lane, int grp, Frag<4>& acc, int idx,
+                                         uint32_t* stage) const {
+    if (packed)
+      gather_range_packed<UNROLL, PRE>(beg, end, indices, P, X, ldx, lane, grp, acc, stage, idx);
+    else
+      gather_range<32, 4, REDUCE, false, UNROLL, PRE>(beg, end, indices, nullptr, X, ldx, col,
+                                                      true, lane, grp, acc, idx);
+  }
+};
+
+template <class P>
+__device__ __forceinline__ Frag<P::VEC> init_frag() {
+  Frag<P::VEC> acc;
+#pragma unroll
+  for (int v = 0; v < P::VEC; ++v) acc.v[v] = (P::REDUCE == GNNREC_REDUCE_MAX) ? -INFINITY : 0.f;
+  return acc;
+}
+
+// this wave's slice of the block's gather stage (none: nullptr, and no LDS is allocated)
+#define GNNREC_WAVE_STAGE(P, stage)                                         \
+  __shared__ __attribute__((aligned(16)))                                   \
+  uint32_t stage##_all[4][P::kStageWords > 0 ? P::kStageWords : 1];         \
+  uint32_t* stage = nullptr;                                                \
+  if constexpr (P::kStageWords > 0) stage = stage##_all[threadIdx.x >> 6]
+
+// one destination row by one wave; idx: the range's first 64 indices when PRE
+template <bool PRE, class P>
+__device__ __forceinline__ void reduce_row(const P& p, const int32_t* __restrict__ indices,
+                                           float* __restrict__ out, int64_t ldo, int flags,
+                                           int64_t row, int64_t beg, int64_t end, int idx,
+                                           int lane, int grp, int col, bool colok,
+                                           uint32_t* stage) {
+  Frag<P::VEC> acc = init_frag<P>();
+  p.template gather<PRE>(beg, end, indices, col, colok, lane, grp, acc, idx, stage);
+  combine_groups<P::LPR, P::VEC, P::REDUCE>(acc);
+  if (grp == 0 && colok) p.fin(acc, out + row * ldo + col, flags, row, end - beg, col);
+}
+
+// Rows [r0, r1) of a queue ticket (at most 64): f(row, beg, end, idx) per row.  The rows'
+// bounds come from one coalesced indptr load, and the next row's first 64 indices (idx) are
+// requested before the current row gathers: of the indptr -> indices -> source-row chain
+// only the last link stays exposed at a row boundary.
+template <class F>
+__device__ __forceinline__ void ticket_walk(const int64_t* __restrict__ indptr,
+                                            const int32_t* __restrict__ indices, int64_t r0,
+                                            int64_t r1, int lane, F&& f) {
+  const int nr = (int)(r1 - r0);
+  const int64_t ipl = lane < nr ? ld_stream(indptr + r0 + lane) : 0;
+  const int64_t ip_end = indptr[r1];
+  auto bound = [&](int k) { return k < nr ? __shfl(ipl, k) : ip_end; };
+  int64_t beg = bound(0), end = bound(1);
+  int nidx = lane < end - beg ? ld_stream(indices + beg + lane) : 0;
+  for (int k = 0; k < nr; ++k) {
+    const int idx = nidx;
+    const int64_t nbeg = end, nend = k + 1 < nr ? bound(k + 2) : end;
+    if (k + 1 < nr) nidx = lane < nend - nbeg ? ld_stream(indices + nbeg + lane) : 0;
+    f(r0 + k, beg, end, idx);
+    beg = nbeg;
+    end = nend;
+  }
+}
+
+// What a row kernel settles before its rows.  A device-built plan that overflowed its
+// capacities (plan_chunks_kernel: n_heavy < 0) covers no row: every row, heavy or not, is
+// reduced by the row kernel.  Rows from a device count `live` on (a static block's padding
+// and dump rows) are empty rows: 0 (sum / mean), no gathers; left as they are under ACCUM
+// (+= 0).  False: no row is left.
+template <bool LIVE>
+__device__ __forceinline__ bool row_prologue(int64_t& n_dst, int64_t& max_deg, int d,
+                                             float* __restrict__ out, int64_t ldo, int flags,
+                                             const int64_t* __restrict__ live,
+                                             const int64_t* __restrict__ plan_counts) {
+  if (plan_counts != nullptr && plan_counts[0] < 0) max_deg = INT64_MAX;
+  if constexpr (LIVE) {
+    if (live != nullptr) {
+      const int64_t l = *live;
+      const int64_t n_rows = l < 0 ? 0 : (l < n_dst ? l : n_dst);
+      if (!(flags & GNNREC_SPMM_ACCUM) && blockIdx.y == 0) {
+        const int64_t nw = (int64_t)gridDim.x * 4;
+        for (int64_t r = n_rows + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n_dst; r += nw)
+          for (int c = threadIdx.x & 63; c < d; c += 64) out[r * ldo + c] = 0.f;
+      }
+      n_dst = n_rows;
+      return n_dst > 0;
+    }
+  }
+  return true;
+}
+
 // Low-degree rows, d <= LPR * VEC: one group of LPR lanes per row, NPI = 64 / LPR rows per
 // wave.  A wave-per-row launch over a 1M-row CSR at 2-3 edges per row (a K = 2500
 // minibatch's transposed blocks) is a chain of indptr -> indices -> source-row loads per row
@@ -62,18 +295,18 @@ __device__ __forceinline__ int ticket_rows(int64_t avg_deg, int64_t n_dst, int64
 // a row goes to partial (k - beg) % NPI in increasing k, and the partials are combined by
 // the same pairwise tree as combine_groups -- bitwise the same rows (tests/test_gpu_parity).
 // No cross-lane traffic: each lane loads the (group-uniform) index and weight itself.
-template <int LPR, int VEC, int REDUCE, bool WEIGHTED>
-__device__ __forceinline__ void group_rows(
-    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
-    const float* __restrict__ ew, const float* __restrict__ X, int64_t ldx, int64_t n_dst, int d,
-    float* __restrict__ out, int64_t ldo, int flags, int64_t max_deg) {
+template <class P>
+__device__ __forceinline__ void group_rows(const P& p, const int64_t* __restrict__ indptr,
+                                           const int32_t* __restrict__ indices, int64_t n_dst,
+                                           int d, float* __restrict__ out, int64_t ldo,
+                                           int flags, int64_t max_deg) {
+  constexpr int LPR = P::LPR, VEC = P::VEC, REDUCE = P::REDUCE;
   constexpr int NPI = kWave / LPR;
   constexpr int U = NPI >= 8 ? NPI : 8;  // neighbours in flight per group; a multiple of NPI
-  const int empty_neginf = flags & GNNREC_SPMM_EMPTY_NEGINF;
+  const auto mask = p.fin.src_mask();
   const int lane = threadIdx.x & 63;
   const int col = (lane % LPR) * VEC;
   const bool colok = col < d;
-  const float init = (REDUCE == GNNREC_REDUCE_MAX) ? -INFINITY : 0.f;
   const int64_t stride = (int64_t)gridDim.x * 4 * NPI;
   int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * NPI + lane / LPR;
   int64_t beg = 0, end = 0;
@@ -90,11 +323,9 @@ __device__ __forceinline__ void group_rows(
       nend = ld_stream(indptr + nrow + 1);
     }
     if (end - beg <= max_deg) {  // heavy rows: reduced by the chunk kernels
-      Frag<VEC> p[NPI];
+      Frag<VEC> part[NPI];
 #pragma unroll
-      for (int i = 0; i < NPI; ++i)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) p[i].v[v] = init;
+      for (int i = 0; i < NPI; ++i) part[i] = init_frag<P>();
       for (int64_t k = beg; k < end; k += U) {
         const int cnt = (int)(end - k < U ? end - k : U);
         int src[U];
@@ -102,13 +333,13 @@ __device__ __forceinline__ void group_rows(
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           src[u] = u < cnt ? ld_stream(indices + k + u) : 0;
-          if constexpr (WEIGHTED) w[u] = u < cnt ? ld_stream(ew + k + u) : 0.f;
+          if constexpr (P::WEIGHTED) w[u] = u < cnt ? ld_stream(p.ew + k + u) : 0.f;
         }
         Frag<VEC> val[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           if (u < cnt && colok) {
-            load_frag<VEC>(val[u], X + (int64_t)src[u] * ldx + col);
+            load_frag<VEC>(val[u], p.X + (int64_t)src[u] * p.ldx + col);
           } else {
 #pragma unroll
             for (int v = 0; v < VEC; ++v) val[u].v[v] = 0.f;
@@ -117,11 +348,11 @@ __device__ __forceinline__ void group_rows(
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           if (u < cnt) {
+            if constexpr (decltype(mask)::kOn) mask.apply(val[u], mask.word(src[u], col), col);
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
-              const float m = WEIGHTED ? val[u].v[v] * w[u] : val[u].v[v];
-              if constexpr (REDUCE == GNNREC_REDUCE_MAX) p[u % NPI].v[v] = fmaxf(p[u % NPI].v[v], m);
-              else p[u % NPI].v[v] += m;
+              const float m = P::WEIGHTED ? val[u].v[v] * w[u] : val[u].v[v];
+              part[u % NPI].v[v] = combine<REDUCE>(part[u % NPI].v[v], m);
             }
           }
         }
@@ -131,376 +362,135 @@ __device__ __forceinline__ void group_rows(
 #pragma unroll
         for (int i = 0; i < NPI; i += 2 * s)
 #pragma unroll
-          for (int v = 0; v < VEC; ++v) p[i].v[v] = combine<REDUCE>(p[i].v[v], p[i + s].v[v]);
-      finalize<VEC, REDUCE>(p[0], end - beg, empty_neginf);
-      if (colok) {
-        if (flags & GNNREC_SPMM_ACCUM) accumulate_into<VEC, REDUCE>(p[0], out + row * ldo + col);
-        store_frag<VEC>(out + row * ldo + col, p[0]);
-      }
+          for (int v = 0; v < VEC; ++v)
+            part[i].v[v] = combine<REDUCE>(part[i].v[v], part[i + s].v[v]);
+      if (colok) p.fin(part[0], out + row * ldo + col, flags, row, end - beg, col);
     }
     beg = nbeg;
     end = nend;
   }
 }
 
-// Mean degree up to which the group kernel takes a d <= 64 CSR.
-constexpr int64_t kGroupMaxAvgDeg = 16;
-
-template <int LPR, int VEC, int REDUCE, bool WEIGHTED, int UNROLL>
+// the row kernel: one wave per destination row of at most max_deg edges — grid-stride, or
+// through the row queue `rq` (P::kQueue; one column slice: the launcher checks gridDim.y == 1)
+template <class P>
 __global__ __launch_bounds__(256) void spmm_csr_kernel(
-    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
-    const float* __restrict__ ew, const float* __restrict__ X, int64_t ldx, int64_t n_dst, int d,
-    float* __restrict__ out, int64_t ldo, int flags, int64_t max_deg, unsigned* rq,
-    int rq_ch, int64_t group_deg, const int64_t* __restrict__ live,
-    const int64_t* __restrict__ plan_counts) {
-  // a device-built plan that overflowed its capacities (plan_chunks_kernel: n_heavy < 0)
-  // covers no row: every row, heavy or not, is reduced here instead
-  if (plan_counts != nullptr && plan_counts[0] < 0) max_deg = INT64_MAX;
-  if (live != nullptr) {
-    // rows from the device count on (a static block's padding and dump rows): the empty
-    // row's value (0: sum / mean), no gathers; left as they are under ACCUM (+= 0)
-    const int64_t l = *live;
-    const int64_t n_rows = l < 0 ? 0 : (l < n_dst ? l : n_dst);
-    if (!(flags & GNNREC_SPMM_ACCUM) && blockIdx.y == 0) {
-      const int64_t nw = (int64_t)gridDim.x * 4;
-      for (int64_t r = n_rows + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n_dst; r += nw)
-        for (int c = threadIdx.x & 63; c < d; c += 64) out[r * ldo + c] = 0.f;
-    }
-    n_dst = n_rows;
-    if (n_dst == 0) {
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_dst, int d,
+    float* __restrict__ out, int64_t ldo, int flags, int64_t max_deg, unsigned* rq, int rq_ch,
+    int64_t group_deg, const int64_t* __restrict__ live,
+    const int64_t* __restrict__ plan_counts, P p) {
+  constexpr int LPR = P::LPR, VEC = P::VEC;
+  GNNREC_WAVE_STAGE(P, stage);
+  auto done = [&] {
+    if constexpr (P::kQueue)
       if (rq != nullptr) rq_finish(rq);
-      return;
-    }
-  }
-  if constexpr (VEC == 4 && (LPR == 8 || LPR == 16)) {  // d in (16, 64]; at LPR 4 the 16
-                                                        // partials cost occupancy
+  };
+  if (!row_prologue<P::kLive>(n_dst, max_deg, d, out, ldo, flags, live, plan_counts))
+    return done();
+  p.begin();
+  if constexpr (P::kGroup) {
     // low mean degree: one lane group per row (the choice needs the CSR's edge count,
     // which only the device holds)
     if (group_deg > 0 && indptr[n_dst] - indptr[0] <= group_deg * n_dst) {
-      group_rows<LPR, VEC, REDUCE, WEIGHTED>(indptr, indices, ew, X, ldx, n_dst, d, out, ldo,
-                                             flags, max_deg);
-      if (rq != nullptr) rq_finish(rq);
-      return;
+      group_rows(p, indptr, indices, n_dst, d, out, ldo, flags, max_deg);
+      return done();
     }
   }
-  const int empty_neginf = flags & GNNREC_SPMM_EMPTY_NEGINF;
   const int lane = threadIdx.x & 63;
   const int grp = lane / LPR;
   const int col = blockIdx.y * (LPR * VEC) + (lane % LPR) * VEC;
   const bool colok = col < d;
-  const float init = (REDUCE == GNNREC_REDUCE_MAX) ? -INFINITY : 0.f;
-  auto one_row = [&](int64_t row) {
-    const int64_t beg = indptr[row];
-    const int64_t end = indptr[row + 1];
-    if (end - beg > max_deg) return;  // heavy row: reduced by the chunk kernels
-    Frag<VEC> acc;
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) acc.v[v] = init;
-    gather_range<LPR, VEC, REDUCE, WEIGHTED, UNROLL>(beg, end, indices, ew, X, ldx, col, colok,
-                                                     lane, grp, acc);
-    combine_groups<LPR, VEC, REDUCE>(acc);
-    finalize<VEC, REDUCE>(acc, end - beg, empty_neginf);
-    if (grp == 0 && colok) {
-      if (flags & GNNREC_SPMM_ACCUM) accumulate_into<VEC, REDUCE>(acc, out + row * ldo + col);
-      store_frag<VEC>(out + row * ldo + col, acc);
-    }
-  };
-  if (rq != nullptr) {  // queued rows (one column slice: the launcher checks gridDim.y == 1)
-    if (rq_ch <= 0) {
-      const int64_t avg = (indptr[n_dst] - indptr[0]) / n_dst;
-      rq_ch = ticket_rows(avg, n_dst, gridDim.x * 4);
-    }
-    // a ticket's row bounds come from one coalesced indptr load, and the next row's first
-    // 64 indices are requested before the current row gathers: of the indptr -> indices ->
-    // source-row chain only the last link stays exposed at a row boundary
-    rq_for_each(rq, n_dst, rq_ch, [&](int64_t r0, int64_t r1) {
-      const int nr = (int)(r1 - r0);  // <= 64
-      const int64_t ipl = lane < nr ? ld_stream(indptr + r0 + lane) : 0;
-      const int64_t ip_end = indptr[r1];
-      auto bound = [&](int k) { return k < nr ? __shfl(ipl, k) : ip_end; };
-      int64_t beg = bound(0), end = bound(1);
-      int nidx = lane < end - beg ? ld_stream(indices + beg + lane) : 0;
-      for (int k = 0; k < nr; ++k) {
-        const int idx = nidx;
-        const int64_t nbeg = end, nend = k + 1 < nr ? bound(k + 2) : end;
-        if (k + 1 < nr) nidx = lane < nend - nbeg ? ld_stream(indices + nbeg + lane) : 0;
-        if (end - beg <= max_deg) {  // heavy rows: reduced by the chunk kernels
-          Frag<VEC> acc;
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) acc.v[v] = init;
-          gather_range<LPR, VEC, REDUCE, WEIGHTED, UNROLL, true>(
-              beg, end, indices, ew, X, ldx, col, colok, lane, grp, acc, idx);
-          combine_groups<LPR, VEC, REDUCE>(acc);
-          finalize<VEC, REDUCE>(acc, end - beg, empty_neginf);
-          const int64_t row = r0 + k;
-          if (grp == 0 && colok) {
-            if (flags & GNNREC_SPMM_ACCUM) accumulate_into<VEC, REDUCE>(acc, out + row * ldo + col);
-            store_frag<VEC>(out + row * ldo + col, acc);
-          }
-        }
-        beg = nbeg;
-        end = nend;
+  if constexpr (P::kQueue) {
+    if (rq != nullptr) {
+      if (rq_ch <= 0) {
+        const int64_t avg = (indptr[n_dst] - indptr[0]) / n_dst;
+        rq_ch = ticket_rows(avg, n_dst, gridDim.x * 4);
       }
-    });
-    rq_finish(rq);
-    return;
-  }
-  const int64_t wstride = (int64_t)gridDim.x * 4;
-  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n_dst; row += wstride)
-    one_row(row);
-}
-
-// phase 1 of heavy rows: one wave per chunk of `split` edges -> raw partial in ws[chunk]
-template <int LPR, int VEC, int REDUCE, bool WEIGHTED, int UNROLL>
-__global__ __launch_bounds__(256) void spmm_chunk_kernel(
-    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
-    const float* __restrict__ ew, const float* __restrict__ X, int64_t ldx, int d,
-    int64_t split, const int64_t* __restrict__ heavy_rows, const int64_t* __restrict__ chunk_ptr,
-    const int64_t* __restrict__ chunk_row, int64_t n_chunks, const int64_t* __restrict__ counts,
-    float* __restrict__ ws) {
-  const int lane = threadIdx.x & 63;
-  const int grp = lane / LPR;
-  const int col = blockIdx.y * (LPR * VEC) + (lane % LPR) * VEC;
-  const bool colok = col < d;
-  const float init = (REDUCE == GNNREC_REDUCE_MAX) ? -INFINITY : 0.f;
-  const int64_t wstride = (int64_t)gridDim.x * 4;
-  if (counts) n_chunks = counts[1];  // device-built plan: the grid covers its capacity
-                                     // (0 when it overflowed)
-  for (int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); c < n_chunks; c += wstride) {
-    const int64_t h = chunk_row[c];
-    const int64_t row = heavy_rows[h];
-    const int64_t rbeg = indptr[row], rend = indptr[row + 1];
-    const int64_t beg = rbeg + (c - chunk_ptr[h]) * split;
-    const int64_t end = (beg + split < rend) ? beg + split : rend;
-    Frag<VEC> acc;
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) acc.v[v] = init;
-    gather_range<LPR, VEC, REDUCE, WEIGHTED, UNROLL>(beg, end, indices, ew, X, ldx, col, colok,
-                                                     lane, grp, acc);
-    combine_groups<LPR, VEC, REDUCE>(acc);
-    if (grp == 0 && colok) store_frag<VEC>(ws + c * (int64_t)d + col, acc);
-  }
-}
-
-// phase 2 of heavy rows: one wave per heavy row, partials combined in chunk order
-template <int VEC, int REDUCE>
-__global__ __launch_bounds__(256) void spmm_combine_kernel(
-    const int64_t* __restrict__ indptr, int d, const int64_t* __restrict__ heavy_rows,
-    int64_t n_heavy, const int64_t* __restrict__ chunk_ptr, const float* __restrict__ ws,
-    float* __restrict__ out, int64_t ldo, int flags, const int64_t* __restrict__ counts) {
-  const int empty_neginf = flags & GNNREC_SPMM_EMPTY_NEGINF;
-  const int lane = threadIdx.x & 63;
-  const float init = (REDUCE == GNNREC_REDUCE_MAX) ? -INFINITY : 0.f;
-  const int64_t wstride = (int64_t)gridDim.x * 4;
-  if (counts) n_heavy = counts[0];  // < 0: an overflowed plan (the row kernel took them)
-  for (int64_t h = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); h < n_heavy; h += wstride) {
-    const int64_t row = heavy_rows[h];
-    const int64_t deg = indptr[row + 1] - indptr[row];
-    for (int col = blockIdx.y * 64 * VEC + lane * VEC; col < d; col += gridDim.y * 64 * VEC) {
-      Frag<VEC> acc;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) acc.v[v] = init;
-      // chunk partials in chunk order; 16 loads in flight ahead of the (ordered) adds: a
-      // Zipf head row has thousands of chunks per tile, and one load per add made its
-      // combine a 0.87 ms latency chain (C4 --zipf 1.0, 16 launches per pass)
-      const int64_t c_end = chunk_ptr[h + 1];
-      int64_t c = chunk_ptr[h];
-      for (; c + 16 <= c_end; c += 16) {
-        Frag<VEC> p[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) load_frag<VEC>(p[u], ws + (c + u) * (int64_t)d + col);
-#pragma unroll
-        for (int u = 0; u < 16; ++u)
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) acc.v[v] = combine<REDUCE>(acc.v[v], p[u].v[v]);
-      }
-      for (; c < c_end; ++c) {
-        Frag<VEC> p;
-        load_frag<VEC>(p, ws + c * (int64_t)d + col);
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc.v[v] = combine<REDUCE>(acc.v[v], p.v[v]);
-      }
-      finalize<VEC, REDUCE>(acc, deg, empty_neginf);
-      if (flags & GNNREC_SPMM_ACCUM) accumulate_into<VEC, REDUCE>(acc, out + row * ldo + col);
-      store_frag<VEC>(out + row * ldo + col, acc);
+      rq_for_each(rq, n_dst, rq_ch, [&](int64_t r0, int64_t r1) {
+        ticket_walk(indptr, indices, r0, r1, lane, [&](int64_t row, int64_t beg, int64_t end, int idx) {
+          if (end - beg <= max_deg)  // heavy rows: reduced by the chunk kernels
+            reduce_row<true>(p, indices, out, ldo, flags, row, beg, end, idx, lane, grp, col, colok,
+                             stage);
+        });
+      });
+      return done();
     }
-  }
-}
-
-// ---- a packed source table (pack_rows.hpp): d = 128, sum / mean, unweighted ------------
-// The row and chunk kernels above with gather_range_packed as their gather: the same rows,
-// schedules (static grid-stride or the row queue), heavy-row split and accumulate-into-
-// partial, so every output is bitwise what they write from the dense table X.  A table
-// whose packed_ok is 0 (too many rows that do not fit) is read through the dense loop.
-template <int REDUCE, int UNROLL>
-__global__ __launch_bounds__(256) void spmm_csr_packed_kernel(
-    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
-    const uint32_t* __restrict__ P, const int* __restrict__ pstatus, const float* __restrict__ X,
-    int64_t ldx, int64_t n_dst, float* __restrict__ out, int64_t ldo, int flags, int64_t max_deg,
-    unsigned* rq, int rq_ch, const int64_t* __restrict__ plan_counts) {
-  __shared__ __attribute__((aligned(16))) uint32_t stage_all[4][UNROLL * 2 * kPackWords];
-  if (plan_counts != nullptr && plan_counts[0] < 0) max_deg = INT64_MAX;
-  const bool packed = pstatus[0] != 0;  // uniform
-  const int lane = threadIdx.x & 63;
-  const int grp = lane >> 5;
-  const int col = (lane & 31) * 4;
-  uint32_t* stage = stage_all[threadIdx.x >> 6];
-  // one destination row; idx: the range's first 64 indices when the caller prefetched them
-  auto reduce_row = [&](int64_t row, int64_t beg, int64_t end, auto pre, int idx) {
-    constexpr bool PRE = decltype(pre)::value;
-    Frag<4> acc;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) acc.v[v] = 0.f;
-    if (packed)
-      gather_range_packed<UNROLL, PRE>(beg, end, indices, P, X, ldx, lane, grp, acc, stage, idx);
-    else
-      gather_range<32, 4, REDUCE, false, UNROLL, PRE>(beg, end, indices, nullptr, X, ldx, col,
-                                                      true, lane, grp, acc, idx);
-    combine_groups<32, 4, REDUCE>(acc);
-    finalize<4, REDUCE>(acc, end - beg, 0);
-    if (grp == 0) {
-      if (flags & GNNREC_SPMM_ACCUM) accumulate_into<4, REDUCE>(acc, out + row * ldo + col);
-      store_frag<4>(out + row * ldo + col, acc);
-    }
-  };
-  if (rq != nullptr) {  // the queued row loop of spmm_csr_kernel
-    if (rq_ch <= 0) {
-      const int64_t avg = (indptr[n_dst] - indptr[0]) / n_dst;
-      rq_ch = ticket_rows(avg, n_dst, gridDim.x * 4);
-    }
-    rq_for_each(rq, n_dst, rq_ch, [&](int64_t r0, int64_t r1) {
-      const int nr = (int)(r1 - r0);  // <= 64
-      const int64_t ipl = lane < nr ? ld_stream(indptr + r0 + lane) : 0;
-      const int64_t ip_end = indptr[r1];
-      auto bound = [&](int k) { return k < nr ? __shfl(ipl, k) : ip_end; };
-      int64_t beg = bound(0), end = bound(1);
-      int nidx = lane < end - beg ? ld_stream(indices + beg + lane) : 0;
-      for (int k = 0; k < nr; ++k) {
-        const int idx = nidx;
-        const int64_t nbeg = end, nend = k + 1 < nr ? bound(k + 2) : end;
-        if (k + 1 < nr) nidx = lane < nend - nbeg ? ld_stream(indices + nbeg + lane) : 0;
-        if (end - beg <= max_deg) reduce_row(r0 + k, beg, end, std::true_type{}, idx);
-        beg = nbeg;
-        end = nend;
-      }
-    });
-    rq_finish(rq);
-    return;
   }
   const int64_t wstride = (int64_t)gridDim.x * 4;
   for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n_dst; row += wstride) {
     const int64_t beg = indptr[row], end = indptr[row + 1];
-    if (end - beg <= max_deg) reduce_row(row, beg, end, std::false_type{}, 0);
+    if (end - beg <= max_deg)
+      reduce_row<false>(p, indices, out, ldo, flags, row, beg, end, 0, lane, grp, col, colok,
+                        stage);
   }
 }
 
-template <int REDUCE, int UNROLL>
-__global__ __launch_bounds__(256) void spmm_chunk_packed_kernel(
-    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
-    const uint32_t* __restrict__ P, const int* __restrict__ pstatus, const float* __restrict__ X,
-    int64_t ldx, int64_t split, const int64_t* __restrict__ heavy_rows,
-    const int64_t* __restrict__ chunk_ptr, const int64_t* __restrict__ chunk_row, int64_t n_chunks,
-    const int64_t* __restrict__ counts, float* __restrict__ ws) {
-  __shared__ __attribute__((aligned(16))) uint32_t stage_all[4][UNROLL * 2 * kPackWords];
-  const bool packed = pstatus[0] != 0;
+// phase 1 of heavy rows: one wave per chunk of `split` edges -> raw partial in ws[chunk]
+template <class P>
+__global__ __launch_bounds__(256) void spmm_chunk_kernel(const int64_t* __restrict__ indptr,
+                                                         const int32_t* __restrict__ indices,
+                                                         int d, HeavyPlan hp,
+                                                         float* __restrict__ ws, P p) {
+  constexpr int LPR = P::LPR, VEC = P::VEC;
+  GNNREC_WAVE_STAGE(P, stage);
+  p.begin();
   const int lane = threadIdx.x & 63;
-  const int grp = lane >> 5;
-  const int col = (lane & 31) * 4;
-  uint32_t* stage = stage_all[threadIdx.x >> 6];
+  const int grp = lane / LPR;
+  const int col = blockIdx.y * (LPR * VEC) + (lane % LPR) * VEC;
+  const bool colok = col < d;
   const int64_t wstride = (int64_t)gridDim.x * 4;
-  if (counts) n_chunks = counts[1];
+  const int64_t n_chunks = hp.chunks();
   for (int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); c < n_chunks; c += wstride) {
-    const int64_t h = chunk_row[c];
-    const int64_t row = heavy_rows[h];
-    const int64_t rbeg = indptr[row], rend = indptr[row + 1];
-    const int64_t beg = rbeg + (c - chunk_ptr[h]) * split;
-    const int64_t end = (beg + split < rend) ? beg + split : rend;
-    Frag<4> acc;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) acc.v[v] = 0.f;
-    if (packed)
-      gather_range_packed<UNROLL>(beg, end, indices, P, X, ldx, lane, grp, acc, stage);
-    else
-      gather_range<32, 4, REDUCE, false, UNROLL>(beg, end, indices, nullptr, X, ldx, col, true,
-                                                 lane, grp, acc);
-    combine_groups<32, 4, REDUCE>(acc);
-    if (grp == 0) store_frag<4>(ws + c * (int64_t)kPackD + col, acc);
+    int64_t beg, end;
+    hp.range(c, indptr, beg, end);
+    Frag<VEC> acc = init_frag<P>();
+    p.template gather<false>(beg, end, indices, col, colok, lane, grp, acc, 0, stage);
+    combine_groups<LPR, VEC, P::REDUCE>(acc);
+    if (grp == 0 && colok) store_frag<VEC>(ws + c * (int64_t)d + col, acc);
   }
 }
 
-struct SpmmArgs {
-  const int64_t* indptr; const int32_t* indices; const float* ew; const float* X; int64_t ldx;
-  int64_t n_dst; int d; float* out; int64_t ldo; int flags;
-  int64_t split; const int64_t* heavy_rows; int64_t n_heavy; const int64_t* chunk_ptr;
-  const int64_t* chunk_row; int64_t n_chunks; float* ws;
-  const int64_t* counts;  // device-built plan: {n_heavy, n_chunks}; n_heavy/n_chunks above
-                          // are then the plan's capacities (grid sizes)
-  const int64_t* live;    // device row count (nullable): rows from it on are empty rows
-  const uint32_t* P;      // packed copy of X (nullable; pack_rows.hpp) and its status words:
-  const int* pstatus;     // the gathers then read P, and X only for rows P does not hold
-};
-
-// Resident 256-thread blocks per CU the row kernels occupy (grid-stride beyond): every wave
-// slot of a CU (CUs kept for concurrent kernels come off through gnnrec_set_concurrency).
-constexpr int64_t kBlocksPerCu = 8;
-
-inline unsigned grid_waves(int64_t units) {
-  int64_t blocks = (units + 3) / 4;
-  // CUs reserved for concurrent kernels (gnnrec_set_concurrency) come off the grid
-  const int cus = device_cus() - cu_reserve();
-  const int64_t max_blocks = (int64_t)(cus > 8 ? cus : 8) * kBlocksPerCu;
-  if (blocks > max_blocks) blocks = max_blocks;
-  return (unsigned)(blocks < 1 ? 1 : blocks);
-}
-
-constexpr int kSpmmUnroll = 4;  // wave-instructions in flight per lane (6, 8: the same)
-template <int LPR, int VEC, int REDUCE, bool WEIGHTED>
-int launch_all(const SpmmArgs& a, hipStream_t s) {
-  constexpr int UNROLL = (VEC == 4) ? kSpmmUnroll : 2;
-  const int cols_per_slice = LPR * VEC;
-  const unsigned slices = (unsigned)((a.d + cols_per_slice - 1) / cols_per_slice);
-  const int eni = a.flags & (GNNREC_SPMM_EMPTY_NEGINF | GNNREC_SPMM_ACCUM);
-  const int64_t max_deg = a.n_heavy > 0 ? a.split : INT64_MAX;
-  const unsigned grid = grid_waves(a.n_dst);
-  // the queue pays off on long launches only (≥ kRqMinRowsPerWave rows per wave of the grid)
-  int ticket = -1;
-  unsigned* rq = slices == 1 && a.n_dst >= (int64_t)grid * 4 * kRqMinRowsPerWave
-                     ? rowq_slot(s, &ticket)
-                     : nullptr;
-  if constexpr (LPR == 32 && VEC == 4 && REDUCE != GNNREC_REDUCE_MAX && !WEIGHTED) {
-    if (a.P != nullptr) {  // (spmm_entry: d = 128, so one column slice)
-      hipLaunchKernelGGL((spmm_csr_packed_kernel<REDUCE, UNROLL>), dim3(grid), dim3(256), 0, s,
-                         a.indptr, a.indices, a.P, a.pstatus, a.X, a.ldx, a.n_dst, a.out, a.ldo,
-                         eni, max_deg, rq, kRowChunk, a.counts);
-      rowq_launched(ticket, s);
-      if (a.n_heavy > 0) {
-        hipLaunchKernelGGL((spmm_chunk_packed_kernel<REDUCE, UNROLL>),
-                           dim3(grid_waves(a.n_chunks)), dim3(256), 0, s, a.indptr, a.indices, a.P,
-                           a.pstatus, a.X, a.ldx, a.split, a.heavy_rows, a.chunk_ptr, a.chunk_row,
-                           a.n_chunks, a.counts, a.ws);
-        hipLaunchKernelGGL((spmm_combine_kernel<VEC, REDUCE>), dim3(grid_waves(a.n_heavy), 1),
-                           dim3(256), 0, s, a.indptr, a.d, a.heavy_rows, a.n_heavy, a.chunk_ptr,
-                           a.ws, a.out, a.ldo, eni, a.counts);
+// phase 2 of heavy rows: one wave per heavy row, partials combined in chunk order, then the
+// row's finish
+template <class Finish>
+__global__ __launch_bounds__(256) void spmm_combine_kernel(const int64_t* __restrict__ indptr,
+                                                           int d, HeavyPlan hp,
+                                                           const float* __restrict__ ws,
+                                                           float* __restrict__ out, int64_t ldo,
+                                                           int flags, Finish fin) {
+  constexpr int VEC = Finish::VEC, REDUCE = Finish::REDUCE;
+  const int lane = threadIdx.x & 63;
+  const int64_t wstride = (int64_t)gridDim.x * 4;
+  const int64_t n_heavy = hp.rows();  // < 0: an overflowed plan (the row kernel took them)
+  fin.begin();
+  for (int64_t h = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); h < n_heavy; h += wstride) {
+    const int64_t row = hp.heavy_rows[h];
+    const int64_t deg = indptr[row + 1] - indptr[row];
+    for (int col = blockIdx.y * 64 * VEC + lane * VEC; col < d; col += gridDim.y * 64 * VEC) {
+      Frag<VEC> acc = init_frag<Finish>();
+      // chunk partials in chunk order; 16 loads in flight ahead of the (ordered) adds: a
+      // Zipf head row has thousands of chunks per tile, and one load per add made its
+      // combine a 0.87 ms latency chain (C4 --zipf 1.0, 16 launches per pass)
+      const int64_t c_end = hp.chunk_ptr[h + 1];
+      int64_t c = hp.chunk_ptr[h];
+      for (; c + 16 <= c_end; c += 16) {
+        Frag<VEC> part[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) load_frag<VEC>(part[u], ws + (c + u) * (int64_t)d + col);
+#pragma unroll
+        for (int u = 0; u < 16; ++u)
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) acc.v[v] = combine<REDUCE>(acc.v[v], part[u].v[v]);
       }
-      return check_launch("gnnrec_spmm_csr_packed_f32");
+      for (; c < c_end; ++c) {
+        Frag<VEC> part;
+        load_frag<VEC>(part, ws + c * (int64_t)d + col);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc.v[v] = combine<REDUCE>(acc.v[v], part.v[v]);
+      }
+      fin(acc, out + row * ldo + col, flags, row, deg, col);
     }
   }
-  hipLaunchKernelGGL((spmm_csr_kernel<LPR, VEC, REDUCE, WEIGHTED, UNROLL>),
-                     dim3(grid, slices), dim3(256), 0, s, a.indptr, a.indices, a.ew,
-                     a.X, a.ldx, a.n_dst, a.d, a.out, a.ldo, eni, max_deg, rq, kRowChunk,
-                     kGroupMaxAvgDeg, a.live, a.counts);
-  rowq_launched(ticket, s);
-  if (a.n_heavy > 0) {
-    hipLaunchKernelGGL((spmm_chunk_kernel<LPR, VEC, REDUCE, WEIGHTED, UNROLL>),
-                       dim3(grid_waves(a.n_chunks), slices), dim3(256), 0, s, a.indptr, a.indices,
-                       a.ew, a.X, a.ldx, a.d, a.split, a.heavy_rows, a.chunk_ptr, a.chunk_row,
-                       a.n_chunks, a.counts, a.ws);
-    const unsigned cslices = (unsigned)((a.d + 64 * VEC - 1) / (64 * VEC));
-    hipLaunchKernelGGL((spmm_combine_kernel<VEC, REDUCE>), dim3(grid_waves(a.n_heavy), cslices),
-                       dim3(256), 0, s, a.indptr, a.d, a.heavy_rows, a.n_heavy, a.chunk_ptr, a.ws,
-                       a.out, a.ldo, eni, a.counts);
-  }
-  return check_launch("gnnrec_spmm_csr_f32");
 }
 
 // ---- two relations into one destination type, one launch ----------------------------
@@ -523,41 +513,19 @@ __global__ __launch_bounds__(256) void spmm_csr2_kernel(Csr2 c, const float* __r
                                                         int64_t ldx, int64_t n_dst, int d,
                                                         int64_t ldo, int flags, unsigned* rq,
                                                         int rq_ch) {
-  const int empty_neginf = flags & GNNREC_SPMM_EMPTY_NEGINF;
   const int lane = threadIdx.x & 63;
   const int grp = lane / LPR;
   const int col = (lane % LPR) * VEC;
   const bool colok = col < d;
-  const float init = (REDUCE == GNNREC_REDUCE_MAX) ? -INFINITY : 0.f;
-  // rows [r0, r1) of relation rel: the queued row loop of spmm_csr_kernel
+  // rows [r0, r1) of relation A, then of relation B
   auto rows = [&](const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
                   const float* __restrict__ ew, float* __restrict__ out, int64_t r0,
                   int64_t r1) __attribute__((always_inline)) {
-    const int nr = (int)(r1 - r0);  // <= 64
-    const int64_t ipl = lane < nr ? ld_stream(indptr + r0 + lane) : 0;
-    const int64_t ip_end = indptr[r1];
-    auto bound = [&](int k) { return k < nr ? __shfl(ipl, k) : ip_end; };
-    int64_t beg = bound(0), end = bound(1);
-    int nidx = lane < end - beg ? ld_stream(indices + beg + lane) : 0;
-    for (int k = 0; k < nr; ++k) {
-      const int idx = nidx;
-      const int64_t nbeg = end, nend = k + 1 < nr ? bound(k + 2) : end;
-      if (k + 1 < nr) nidx = lane < nend - nbeg ? ld_stream(indices + nbeg + lane) : 0;
-      Frag<VEC> acc;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) acc.v[v] = init;
-      gather_range<LPR, VEC, REDUCE, WEIGHTED, UNROLL, true>(beg, end, indices, ew, X, ldx, col,
-                                                             colok, lane, grp, acc, idx);
-      combine_groups<LPR, VEC, REDUCE>(acc);
-      finalize<VEC, REDUCE>(acc, end - beg, empty_neginf);
-      const int64_t row = r0 + k;
-      if (grp == 0 && colok) {
-        if (flags & GNNREC_SPMM_ACCUM) accumulate_into<VEC, REDUCE>(acc, out + row * ldo + col);
-        store_frag<VEC>(out + row * ldo + col, acc);
-      }
-      beg = nbeg;
-      end = nend;
-    }
+    const PlainAgg<LPR, VEC, REDUCE, WEIGHTED, UNROLL> p{ew, X, ldx, {}};
+    ticket_walk(indptr, indices, r0, r1, lane, [&](int64_t row, int64_t beg, int64_t end, int idx) {
+      reduce_row<true>(p, indices, out, ldo, flags, row, beg, end, idx, lane, grp, col, colok,
+                       nullptr);
+    });
   };
   auto both = [&](int64_t r0, int64_t r1) __attribute__((always_inline)) {
     rows(c.indptr[0], c.indices[0], c.ew[0], c.out[0], r0, r1);
@@ -577,6 +545,112 @@ __global__ __launch_bounds__(256) void spmm_csr2_kernel(Csr2 c, const float* __r
     both(row, row + 1);
 }
 
+// ---- host side -------------------------------------------------------------------------
+struct DropCall {  // the dropout entry points' own arguments
+  const uint64_t* keys;
+  int64_t key_index;
+  double p;
+  int where;
+};
+
+struct SpmmArgs {
+  const char* name;  // the entry point, as its errors name it
+  const int64_t* indptr; const int32_t* indices; const float* ew; const float* X; int64_t ldx;
+  int64_t n_dst; float* out; int64_t ldo; int flags;
+  HeavyPlan hp;            // n_heavy == 0: no plan
+  float* ws;               // chunk partials [n_chunks, d]
+  const int64_t* live;     // device row count (nullable): rows from it on are empty rows
+  const uint32_t* P;       // packed copy of X (nullable; pack_rows.hpp) and its status words:
+  const int* pstatus;      // the gathers then read P, and X only for rows P does not hold
+  const DropCall* drop;    // nullable: the mask inside (sum / mean)
+  int d;
+  DropArgs da;
+};
+
+SpmmArgs spmm_args(const char* name, const int64_t* indptr, const int32_t* indices,
+                   const float* ew, const float* X, int64_t ldx, int64_t n_dst, float* out,
+                   int64_t ldo, int flags) {
+  SpmmArgs a{};
+  a.name = name;
+  a.indptr = indptr; a.indices = indices; a.ew = ew; a.X = X; a.ldx = ldx;
+  a.n_dst = n_dst; a.out = out; a.ldo = ldo; a.flags = flags;
+  return a;
+}
+
+// Resident 256-thread blocks per CU the row kernels occupy (grid-stride beyond): every wave
+// slot of a CU (CUs kept for concurrent kernels come off through gnnrec_set_concurrency).
+constexpr int64_t kBlocksPerCu = 8;
+
+inline unsigned grid_waves(int64_t units) {
+  int64_t blocks = (units + 3) / 4;
+  // CUs reserved for concurrent kernels (gnnrec_set_concurrency) come off the grid
+  const int cus = device_cus() - cu_reserve();
+  const int64_t max_blocks = (int64_t)(cus > 8 ? cus : 8) * kBlocksPerCu;
+  if (blocks > max_blocks) blocks = max_blocks;
+  return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
+// the family's launches: rows under policy P, then (a plan) chunks under policy C and the
+// combine with P's finish
+template <class P, class C>
+int launch_family(const SpmmArgs& a, hipStream_t s, const P& p, const C& c, const char* what) {
+  const int cols_per_slice = P::LPR * P::VEC;
+  const unsigned slices = (unsigned)((a.d + cols_per_slice - 1) / cols_per_slice);
+  const int64_t max_deg = a.hp.n_heavy > 0 ? a.hp.split : INT64_MAX;
+  const unsigned grid = grid_waves(a.n_dst);
+  const int flags = a.flags & (GNNREC_SPMM_EMPTY_NEGINF | GNNREC_SPMM_ACCUM);
+  // the queue pays off on long launches only (≥ kRqMinRowsPerWave rows per wave of the grid)
+  int ticket = -1;
+  unsigned* rq = nullptr;
+  if constexpr (P::kQueue)
+    if (slices == 1 && a.n_dst >= (int64_t)grid * 4 * kRqMinRowsPerWave) rq = rowq_slot(s, &ticket);
+  hipLaunchKernelGGL((spmm_csr_kernel<P>), dim3(grid, slices), dim3(256), 0, s, a.indptr,
+                     a.indices, a.n_dst, a.d, a.out, a.ldo, flags, max_deg, rq, kRowChunk,
+                     kGroupMaxAvgDeg, P::kLive ? a.live : nullptr, a.hp.counts, p);
+  if constexpr (P::kQueue) rowq_launched(ticket, s);
+  if (a.hp.n_heavy > 0) {
+    hipLaunchKernelGGL((spmm_chunk_kernel<C>), dim3(grid_waves(a.hp.n_chunks), slices), dim3(256),
+                       0, s, a.indptr, a.indices, a.d, a.hp, a.ws, c);
+    const unsigned cslices = (unsigned)((a.d + 64 * P::VEC - 1) / (64 * P::VEC));
+    hipLaunchKernelGGL((spmm_combine_kernel<typename P::Finish>),
+                       dim3(grid_waves(a.hp.n_heavy), cslices), dim3(256), 0, s, a.indptr, a.d,
+                       a.hp, a.ws, a.out, a.ldo, flags, p.fin);
+  }
+  return check_launch(what);
+}
+
+constexpr int kSpmmUnroll = 4;  // wave-instructions in flight per lane (6, 8: the same)
+template <int LPR, int VEC, int REDUCE, bool WEIGHTED>
+int launch_all(const SpmmArgs& a, hipStream_t s) {
+  constexpr int UNROLL = (VEC == 4) ? kSpmmUnroll : 2;
+  if constexpr (REDUCE != GNNREC_REDUCE_MAX) {
+    if (a.drop != nullptr) {
+      // chunk partials are raw sums: the mask of the gathered rows (SRC) or none (OUT)
+      constexpr int SUM = GNNREC_REDUCE_SUM;
+      if (a.drop->where == GNNREC_DROPOUT_SRC) {
+        constexpr int SRC = GNNREC_DROPOUT_SRC;
+        const DropAgg<LPR, VEC, REDUCE, WEIGHTED, UNROLL, SRC> p{
+            a.ew, a.X, a.ldx, {a.da, 0}};
+        const DropAgg<LPR, VEC, SUM, WEIGHTED, UNROLL, SRC> c{
+            a.ew, a.X, a.ldx, {a.da, 0}};
+        return launch_family(a, s, p, c, a.name);
+      }
+      const DropAgg<LPR, VEC, REDUCE, WEIGHTED, UNROLL, GNNREC_DROPOUT_OUT> p{
+          a.ew, a.X, a.ldx, {a.da, 0}};
+      const PlainAgg<LPR, VEC, SUM, WEIGHTED, UNROLL> c{a.ew, a.X, a.ldx, {}};
+      return launch_family(a, s, p, c, a.name);
+    }
+    if constexpr (LPR == 32 && VEC == 4 && !WEIGHTED) {
+      if (a.P != nullptr) {  // (spmm_entry: d = 128, so one column slice)
+        const PackedAgg<REDUCE, UNROLL> p{a.P, a.pstatus, a.X, a.ldx, {}, false};
+        return launch_family(a, s, p, p, "gnnrec_spmm_csr_packed_f32");
+      }
+    }
+  }
+  const PlainAgg<LPR, VEC, REDUCE, WEIGHTED, UNROLL> p{a.ew, a.X, a.ldx, {}};
+  return launch_family(a, s, p, p, a.name);
+}
+
 template <int LPR, int REDUCE, bool WEIGHTED>
 int launch_csr2(const Csr2& c, const float* X, int64_t ldx, int64_t n_dst, int d, int64_t ldo,
                 int flags, hipStream_t s) {
@@ -590,6 +664,7 @@ int launch_csr2(const Csr2& c, const float* X, int64_t ldx, int64_t n_dst, int d
   return check_launch("gnnrec_spmm_csr2_f32");
 }
 
+// the one dispatch ladder: (vec4, lpr) x reduce x weighted -> launch_all
 template <int VEC, int REDUCE, bool WEIGHTED>
 int dispatch_lpr(int lpr, const SpmmArgs& a, hipStream_t s) {
   if constexpr (VEC == 1) {
@@ -621,18 +696,31 @@ int dispatch_reduce(int reduce, int lpr, const SpmmArgs& a, hipStream_t s) {
   }
 }
 
+// every entry point of the family: the size, stride and plan checks, the vec4 / lpr choice
 int spmm_entry(SpmmArgs a, int64_t d, int reduce, void* stream) {
-  GNNREC_REQUIRE(a.n_dst >= 0 && d >= 0, "gnnrec_spmm_csr_f32: negative size");
+  const char* n = a.name;
+  GNNREC_REQUIRE(a.n_dst >= 0 && d >= 0, "%s: negative size", n);
+  if (a.drop != nullptr) {
+    GNNREC_REQUIRE(reduce == GNNREC_REDUCE_SUM || reduce == GNNREC_REDUCE_MEAN,
+                   "%s: sum or mean, got reduce %d", n, reduce);
+    GNNREC_REQUIRE(a.drop->where == GNNREC_DROPOUT_SRC || a.drop->where == GNNREC_DROPOUT_OUT,
+                   "%s: unknown mask side %d", n, a.drop->where);
+    GNNREC_REQUIRE(a.drop->p >= 0.0 && a.drop->p <= 1.0, "%s: p=%g outside [0, 1]", n, a.drop->p);
+  }
   GNNREC_REQUIRE(reduce == GNNREC_REDUCE_SUM || reduce == GNNREC_REDUCE_MEAN ||
                      reduce == GNNREC_REDUCE_MAX,
-                 "gnnrec_spmm_csr_f32: unknown reduce %d", reduce);
-  GNNREC_REQUIRE(d <= (1 << 20), "gnnrec_spmm_csr_f32: d=%lld too large", (long long)d);
+                 "%s: unknown reduce %d", n, reduce);
+  GNNREC_REQUIRE(d <= (1 << 20), "%s: d=%lld too large", n, (long long)d);
+  GNNREC_REQUIRE(a.drop == nullptr || (a.drop->key_index >= 0 && a.drop->key_index < (1 << 30)),
+                 "%s: bad key index", n);
   if (a.n_dst == 0 || d == 0) return GNNREC_OK;
-  GNNREC_REQUIRE(a.indptr && a.out, "gnnrec_spmm_csr_f32: null indptr/out");
-  GNNREC_REQUIRE(a.ldx >= d && a.ldo >= d, "gnnrec_spmm_csr_f32: leading dimension < d");
-  GNNREC_REQUIRE(a.n_heavy == 0 || (a.split > 0 && a.heavy_rows && a.chunk_ptr && a.chunk_row &&
-                                    a.ws && a.n_chunks > 0),
-                 "gnnrec_spmm_csr_split_f32: incomplete heavy-row plan");
+  GNNREC_REQUIRE(a.indptr && a.out && (a.drop == nullptr || a.drop->keys),
+                 a.drop ? "%s: null indptr/out/keys" : "%s: null indptr/out", n);
+  GNNREC_REQUIRE(a.ldx >= d && a.ldo >= d, "%s: leading dimension < d", n);
+  GNNREC_REQUIRE(a.hp.n_heavy == 0 || (a.hp.split > 0 && a.hp.heavy_rows && a.hp.chunk_ptr &&
+                                       a.hp.chunk_row && a.ws && a.hp.n_chunks > 0),
+                 "%s: incomplete heavy-row plan",
+                 a.drop ? "gnnrec_spmm_csr_planned_dropout_f32" : "gnnrec_spmm_csr_split_f32");
   GNNREC_REQUIRE(a.live == nullptr || reduce != GNNREC_REDUCE_MAX,
                  "gnnrec_spmm_csr_live_f32: a device row count needs sum or mean");
   a.d = (int)d;
@@ -640,11 +728,17 @@ int spmm_entry(SpmmArgs a, int64_t d, int reduce, void* stream) {
     GNNREC_REQUIRE(d == kPackD && reduce != GNNREC_REDUCE_MAX && a.ew == nullptr &&
                        a.live == nullptr && a.pstatus != nullptr && a.ldx % 4 == 0 &&
                        a.ldo % 4 == 0 && aligned16(a.X) && aligned16(a.out) && aligned16(a.P) &&
-                       (a.n_heavy == 0 || aligned16(a.ws)),
+                       (a.hp.n_heavy == 0 || aligned16(a.ws)),
                    "gnnrec_spmm_csr_packed_f32: needs d = %d, sum or mean, no edge weights, no "
                    "device row count and 16-B aligned rows", kPackD);
+  if (a.drop != nullptr) {
+    const DropParams dp = drop_params(a.drop->p);
+    a.da = DropArgs{a.drop->keys, (int)a.drop->key_index, dp.T, dp.scale, (int)((d + 3) / 4)};
+  }
+  // 16-B fragments (LPR lanes cover a row: the power of two from 4 up that holds d / 4, at
+  // most 64) when every row of X, out and the partials is 16-B aligned; else one column a lane
   const bool vec4 = (d % 4 == 0) && (a.ldx % 4 == 0) && (a.ldo % 4 == 0) && aligned16(a.X) &&
-                    aligned16(a.out) && (a.n_heavy == 0 || aligned16(a.ws));
+                    aligned16(a.out) && (a.hp.n_heavy == 0 || aligned16(a.ws));
   int lpr = 64;
   if (vec4) {
     const int64_t lanes = d / 4;
@@ -661,9 +755,8 @@ int spmm_entry(SpmmArgs a, int64_t d, int reduce, void* stream) {
 extern "C" int gnnrec_spmm_csr_f32(const int64_t* indptr, const int32_t* indices, const float* ew,
                                    const float* X, int64_t ldx, int64_t n_dst, int64_t d,
                                    int reduce, int flags, float* out, int64_t ldo, void* stream) {
-  gnnrec::SpmmArgs a{indptr, indices, ew, X, ldx, n_dst, 0, out, ldo, flags,
-                     0, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
-  return gnnrec::spmm_entry(a, d, reduce, stream);
+  return gnnrec_spmm_csr_live_f32(indptr, indices, ew, X, ldx, n_dst, d, reduce, flags, out, ldo,
+                                  nullptr, stream);
 }
 
 extern "C" int gnnrec_spmm_csr_packed_f32(const int64_t* indptr, const int32_t* indices,
@@ -675,9 +768,12 @@ extern "C" int gnnrec_spmm_csr_packed_f32(const int64_t* indptr, const int32_t* 
                                           const int64_t* chunk_row, int64_t n_chunks,
                                           float* workspace, const int64_t* counts, void* stream) {
   GNNREC_REQUIRE(packed && status && X, "gnnrec_spmm_csr_packed_f32: null table");
-  gnnrec::SpmmArgs a{indptr, indices, nullptr, X, ldx, n_dst, 0, out, ldo, flags,
-                     split, heavy_rows, n_heavy, chunk_ptr, chunk_row, n_chunks, workspace,
-                     counts, nullptr, static_cast<const uint32_t*>(packed), status};
+  gnnrec::SpmmArgs a = gnnrec::spmm_args("gnnrec_spmm_csr_f32", indptr, indices, nullptr, X, ldx,
+                                         n_dst, out, ldo, flags);
+  a.hp = {split, heavy_rows, n_heavy, chunk_ptr, chunk_row, n_chunks, counts};
+  a.ws = workspace;
+  a.P = static_cast<const uint32_t*>(packed);
+  a.pstatus = status;
   return gnnrec::spmm_entry(a, d, reduce, stream);
 }
 
@@ -686,8 +782,9 @@ extern "C" int gnnrec_spmm_csr_live_f32(const int64_t* indptr, const int32_t* in
                                         int64_t n_dst, int64_t d, int reduce, int flags,
                                         float* out, int64_t ldo, const int64_t* live,
                                         void* stream) {
-  gnnrec::SpmmArgs a{indptr, indices, ew, X, ldx, n_dst, 0, out, ldo, flags,
-                     0, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, live};
+  gnnrec::SpmmArgs a = gnnrec::spmm_args("gnnrec_spmm_csr_f32", indptr, indices, ew, X, ldx,
+                                         n_dst, out, ldo, flags);
+  a.live = live;
   return gnnrec::spmm_entry(a, d, reduce, stream);
 }
 
@@ -698,9 +795,10 @@ extern "C" int gnnrec_spmm_csr_split_f32(const int64_t* indptr, const int32_t* i
                                          const int64_t* heavy_rows, int64_t n_heavy,
                                          const int64_t* chunk_ptr, const int64_t* chunk_row,
                                          int64_t n_chunks, float* workspace, void* stream) {
-  gnnrec::SpmmArgs a{indptr, indices, ew, X, ldx, n_dst, 0, out, ldo, flags,
-                     split, heavy_rows, n_heavy, chunk_ptr, chunk_row, n_chunks, workspace,
-                     nullptr, nullptr};
+  gnnrec::SpmmArgs a = gnnrec::spmm_args("gnnrec_spmm_csr_f32", indptr, indices, ew, X, ldx,
+                                         n_dst, out, ldo, flags);
+  a.hp = {split, heavy_rows, n_heavy, chunk_ptr, chunk_row, n_chunks, nullptr};
+  a.ws = workspace;
   return gnnrec::spmm_entry(a, d, reduce, stream);
 }
 
@@ -841,9 +939,11 @@ extern "C" int gnnrec_spmm_csr_planned_live_f32(const int64_t* indptr, const int
                                                 int64_t cap_c, float* workspace,
                                                 const int64_t* live, void* stream) {
   GNNREC_REQUIRE(plan && cap_h > 0 && cap_c > 0, "gnnrec_spmm_csr_planned_f32: empty plan");
-  gnnrec::SpmmArgs a{indptr, indices, ew, X, ldx, n_dst, 0, out, ldo, flags,
-                     split, plan + 2, cap_h, plan + 2 + cap_h, plan + 3 + 2 * cap_h, cap_c,
-                     workspace, plan, live};
+  gnnrec::SpmmArgs a = gnnrec::spmm_args("gnnrec_spmm_csr_f32", indptr, indices, ew, X, ldx,
+                                         n_dst, out, ldo, flags);
+  a.hp = gnnrec::HeavyPlan::on_device(split, plan, cap_h, cap_c);
+  a.ws = workspace;
+  a.live = live;
   return gnnrec::spmm_entry(a, d, reduce, stream);
 }
 
@@ -856,6 +956,39 @@ extern "C" int gnnrec_spmm_csr_planned_f32(const int64_t* indptr, const int32_t*
   return gnnrec_spmm_csr_planned_live_f32(indptr, indices, ew, X, ldx, n_dst, d, reduce, flags,
                                           out, ldo, split, plan, cap_h, cap_c, workspace,
                                           nullptr, stream);
+}
+
+// the sum / mean gathers with the dropout mask inside (dropout.hpp; where: the mask of the
+// gathered rows, or of the output row at its store)
+extern "C" int gnnrec_spmm_csr_dropout_live_f32(const int64_t* indptr, const int32_t* indices,
+                                                const float* ew, const float* X, int64_t ldx,
+                                                int64_t n_dst, int64_t d, int reduce, int flags,
+                                                float* out, int64_t ldo, const int64_t* live,
+                                                const uint64_t* keys, int64_t key_index,
+                                                double p, int where, void* stream) {
+  const gnnrec::DropCall drop{keys, key_index, p, where};
+  gnnrec::SpmmArgs a = gnnrec::spmm_args("gnnrec_spmm_csr_dropout_f32", indptr, indices, ew, X,
+                                         ldx, n_dst, out, ldo, flags);
+  a.live = live;
+  a.drop = &drop;
+  return gnnrec::spmm_entry(a, d, reduce, stream);
+}
+
+extern "C" int gnnrec_spmm_csr_planned_dropout_live_f32(
+    const int64_t* indptr, const int32_t* indices, const float* ew, const float* X, int64_t ldx,
+    int64_t n_dst, int64_t d, int reduce, int flags, float* out, int64_t ldo, int64_t split,
+    const int64_t* plan, int64_t cap_h, int64_t cap_c, float* workspace, const int64_t* live,
+    const uint64_t* keys, int64_t key_index, double p, int where, void* stream) {
+  GNNREC_REQUIRE(plan && cap_h > 0 && cap_c > 0,
+                 "gnnrec_spmm_csr_planned_dropout_f32: empty plan");
+  const gnnrec::DropCall drop{keys, key_index, p, where};
+  gnnrec::SpmmArgs a = gnnrec::spmm_args("gnnrec_spmm_csr_dropout_f32", indptr, indices, ew, X,
+                                         ldx, n_dst, out, ldo, flags);
+  a.hp = gnnrec::HeavyPlan::on_device(split, plan, cap_h, cap_c);
+  a.ws = workspace;
+  a.live = live;
+  a.drop = &drop;
+  return gnnrec::spmm_entry(a, d, reduce, stream);
 }
 
 // ---------------------------------------------------------------- backward --
