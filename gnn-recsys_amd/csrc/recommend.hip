@@ -26,6 +26,10 @@
 // normalisation add at most about d 2^-23, and score itself carries the same order of fp32
 // error against the real cosine: for d <= 2048 all of it is below 2^-11 - 2^-16, so
 //   |a(u, v) - score(u, v)| <= eps = 2^-7 + 2^-11.
+// The derivation assumes row norms (and the squares they are summed from) in fp32's normal
+// range and away from the 1e-12 guard, or exactly zero: where the squares underflow, or the
+// guard applies to one computed norm and not to the other, a and score divide by different
+// norms and the derivation says nothing.
 //
 // THE FILTER.  Let tau_r be ANY value such that at least k non-excluded items of row r have
 // a >= tau_r.  Those k items have score >= tau_r - eps, so the true k-th best score is

@@ -172,7 +172,8 @@ def recommend(h_user, h_item, k, user_rows=None, exclude=None, *, batch_size=819
     exact| <= REC_EPS), at most `cand_cap` per user; those are rescored in fp32 and ranked.
     Rows that kept more than cand_cap items (and the whole call when k > cand_cap / 4,
     d > REC_MAX_D or d % 4 != 0) are recomputed exhaustively with sddmm_cos + topk_rows, so
-    the result never depends on the filter.  The host reads the device once per call (the
+    the result never depends on the filter.  The bound REC_EPS is derived for rows whose norm
+    lies in fp32's normal range and away from the 1e-12 guard (or is exactly zero).  The host reads the device once per call (the
     per-row candidate counts, after the last batch).
 
     Non-finite embeddings are outside the contract: a NaN or inf score has no place in the

@@ -73,16 +73,18 @@ def test_normalize_rows_bf16(d):
         assert (got[5 if m is None else 1] == 0).all()
 
 
-@pytest.mark.parametrize("d", [16, 128, 160])
+@pytest.mark.parametrize("d", [16, 64, 80, 128, 160])
 def test_store_mode_matches_bf16_matmul(d):
     """Every ragged edge of the 128 x 128 block tile, the 64 x 64 wave tile and the 32 x 32
-    MFMA tile; d = 160 (dpad > 128) takes the kernel that loads its operands directly."""
+    MFMA tile (129: one row or column in a second block tile), in every form of the kernel:
+    the slab kernel at dpad 32, 64 and 128, and the one that loads its operands directly at
+    dpad 96 (d = 80) and dpad > 128 (d = 160)."""
     from gnnrec import ops
     hu, hi = rc.tables("normal", d, 130, 4097, seed=3)
     ub, vb = ops.normalize_rows_bf16(_cu(hu)), ops.normalize_rows_bf16(_cu(hi))
     uf, vf = ub.float().cpu(), vb.float().cpu()
-    for B in (1, 33, 130):
-        for n in (1, 31, 1000, 4097):
+    for B in (1, 33, 129, 130):
+        for n in (1, 31, 129, 1000, 4097):
             got = ops.score_bf16_store(ub[:B].contiguous(), vb[:n].contiguous()).cpu()
             torch.testing.assert_close(got, uf[:B] @ vf[:n].T, rtol=1e-5, atol=1e-6)
 

@@ -23,11 +23,7 @@ def _approx(hu, hi):
     return (_unit_bf16(hu).float() @ _unit_bf16(hi).float().T).numpy()
 
 
-def _cosine64(hu, hi):
-    hu, hi = hu.astype(np.float64), hi.astype(np.float64)
-    nu = np.maximum(np.linalg.norm(hu, axis=1, keepdims=True), 1e-12)
-    ni = np.maximum(np.linalg.norm(hi, axis=1, keepdims=True), 1e-12)
-    return (hu / nu) @ (hi / ni).T
+_cosine64 = rc.cosine64
 
 
 def test_eps_is_the_documented_constant():
@@ -36,13 +32,26 @@ def test_eps_is_the_documented_constant():
     assert recs.REC_MAX_D == 2048
 
 
-@pytest.mark.parametrize("d", [16, 64, 128, 100])
+@pytest.mark.parametrize("d", [16, 64, 128, 100] + sorted(set(rc.BOUND_DIMS) - {16, 64, 128, 100}))
 @pytest.mark.parametrize("kind", ["normal", "relu", "lowrank", "midpoint"])
 def test_bound(kind, d):
-    """|a - s| <= eps, s the float64 cosine."""
-    hu, hi = rc.tables(kind, d, 64, 2000)
+    """|a - s| <= eps, s the float64 cosine, at every d that
+    tests/test_gpu_recommend_kernels.py::test_device_bound runs on the device (the figures of
+    both are in profiles/recommend_device_bound.md)."""
+    hu, hi = rc.bound_tables(kind, d)
     err = np.abs(_approx(hu, hi) - _cosine64(hu, hi)).max()
-    print(f"{kind} d={d}: max |a - s| = {err:.3e} (eps {EPS:.3e})")
+    print(f"{kind} d={d} scale=1: max |a - s| = {err:.3e} (eps {EPS:.3e})")
+    assert err <= EPS
+
+
+@pytest.mark.parametrize("d,scale", rc.BOUND_SCALED)
+@pytest.mark.parametrize("kind", ["normal", "relu", "lowrank", "midpoint"])
+def test_bound_scaled(kind, d, scale):
+    """The same with both tables times 2^-20 and 2^20 (exact in fp32, the squares far inside
+    the normal range); the reference comes from the scaled tables."""
+    hu, hi = rc.bound_tables(kind, d, scale)
+    err = np.abs(_approx(hu, hi) - _cosine64(hu, hi)).max()
+    print(f"{kind} d={d} scale={scale:g}: max |a - s| = {err:.3e} (eps {EPS:.3e})")
     assert err <= EPS
 
 
@@ -93,6 +102,95 @@ def test_filter_at_200k_items():
     _, counts = _filter_counts(hu, hi, indptr, indices, 64, 65536)
     print(f"largest count {counts.max()}")
     assert counts.max() <= 1024
+
+
+# ------------------------------------------- what the device kernel tests lean on
+@pytest.mark.parametrize("d", rc.NORMALIZE_DIMS)
+def test_normalize_reference_decides_nearly_every_entry(d):
+    """rc.normalize_expected: the two admissible bf16 patterns are neighbours or equal, equal
+    wherever the quotient is DECIDED away from a rounding midpoint, and equal for more than
+    99% of the entries, so the device test pins nearly every output to one value.  (The
+    DECIDED entries alone are about 91%: the band of 2 x 2^-12 relative lies in a bf16
+    spacing of 2^-8 .. 2^-7 relative.  The bracket of the norm, 2^-20, is what decides.)
+    The host restatement itself passes the check it sets for the device."""
+    x = rc.normalize_source(d)
+    a, b, decided = rc.normalize_expected(x)
+    assert (np.abs(a.astype(np.int32) - b.astype(np.int32)) <= 1).all()
+    assert (a == b)[decided].all()
+    print(f"d={d}: one admissible value for {(a == b).mean():.4%} of the entries, "
+          f"{decided.mean():.2%} at least 2^-12 from a midpoint")
+    assert (a == b).mean() > 0.99
+    got = rc.bf16_bits(rc.unit_bf16(x))
+    assert ((got == a) | (got == b)).all()
+
+
+def test_normalize_reference_midpoint_table():
+    hu, _ = rc.tables("midpoint", 100, 37, 1)
+    a, b, _ = rc.normalize_expected(hu)
+    assert (a == b).mean() > 0.99
+    got = rc.bf16_bits(rc.unit_bf16(hu))
+    assert ((got == a) | (got == b)).all()
+
+
+def test_tie_rows_round_to_even():
+    """rc.tie_rows: the fp32 norm is 512 exactly, the first quotient an exact midpoint; the
+    expected pattern is the even neighbour, which truncation and round-half-up both miss
+    for half of the rows."""
+    x = rc.tie_rows()
+    assert (np.sqrt((x * x).sum(1, dtype=np.float32)) == 512).all()
+    q = x[:, 0] / np.float32(512)
+    want = rc.bf16_bits(q)
+    assert (want & 1 == 0).all()
+    lo = q.view(np.uint32) >> 16            # truncation
+    assert ((q.view(np.uint32) & 0xFFFF) == 0x8000).all()
+    assert (want != lo).sum() == 64 and (want != lo + 1).sum() == 64
+    np.testing.assert_array_equal(rc.bf16_bits(rc.unit_bf16(x)), rc.bf16_bits(x / np.float32(512)))
+
+
+def test_truncating_conversion_breaks_the_bound_and_the_bits():
+    """The mutation a device test must catch, tried on the host: bf16 by truncation exceeds
+    eps at small d (at d = 16 on the relu and lowrank tables, not on the normal one; from
+    d = 128 on it stays under eps everywhere), and misses the admissible patterns of
+    normalize_expected at every d."""
+    def trunc(x):
+        x = np.asarray(x, np.float32)
+        ss = (x * x).sum(1, keepdims=True, dtype=np.float32)
+        nrm = np.maximum(np.sqrt(ss), np.float32(1e-12))
+        return ((x / nrm).view(np.uint32) >> 16).astype(np.uint16)
+    hu, hi = rc.bound_tables("lowrank", 16)
+    a = rc.bf16_value(trunc(hu)).astype(np.float64) @ rc.bf16_value(trunc(hi)).astype(np.float64).T
+    assert np.abs(a - _cosine64(hu, hi)).max() > EPS
+    x = rc.normalize_source(32)
+    lo, hi_, _ = rc.normalize_expected(x)
+    got = trunc(x)
+    assert ((got != lo) & (got != hi_)).mean() > 0.25
+
+
+@pytest.mark.parametrize("d", rc.FILTER_DIMS)
+def test_filter_band_is_thin(d):
+    """The inputs of test_filter_keeps_exactly_the_expected_set: fewer than 0.1% of a case's
+    pairs lie within FILTER_BAND of their row's threshold, where the fp32 accumulation order
+    may decide."""
+    hu, hi = rc.filter_tables(d)
+    a64 = rc.unit_bf16(hu).astype(np.float64) @ rc.unit_bf16(hi).astype(np.float64).T
+    for B in rc.FILTER_BS:
+        for n in rc.FILTER_NS:
+            keep, band = rc.filter_expected(a64[:B, :n], rc.filter_tau(d, B))
+            assert band.mean() < rc.FILTER_BAND_SHARE, (B, n, band.sum())
+            assert keep[0].all() and (B == 1 or not keep[-1].any())
+            assert keep.sum(1).max() <= rc.FILTER_CAP
+
+
+@pytest.mark.parametrize("name", sorted(rc.FALLBACKS))
+def test_fallback_inputs(name):
+    """The small cases of test_recommend_other_paths: where the fast path must run without
+    overflow (d = 2048), the restated filter keeps every count under the cap."""
+    hu, hi, (ip, ix), k, kw, fast = rc.fallback_case(name)
+    if fast:
+        _, counts = _filter_counts(hu, hi, ip, ix, k, kw.get("sample", rc.SAMPLE))
+        assert counts.max() <= rc.CAND_CAP
+    else:
+        assert hi.shape[0] <= 600 and hu.shape[0] <= 16
 
 
 # ---------------------------------------------------------------- Meta kernels
