@@ -150,6 +150,49 @@ static void validation() {
   CHECK(gnnrec_topk_candidates_f32(nullptr, nullptr, 64, 0, nullptr, nullptr, 16, nullptr, 16, 16,
                                    nullptr, nullptr, 10, nullptr, nullptr, nullptr) == GNNREC_OK,
         "candidates empty");
+  // edge removal (csr_filter.hip): every refusal comes before the first memset or launch;
+  // an empty problem still writes the status and indptr', so its host side is the
+  // workspace query, which must give room for them
+  CHECK(gnnrec_csr_remove_edges_workspace_bytes(0, 0) > 0 &&
+            gnnrec_csr_remove_edges_workspace_bytes(-5, 3) ==
+                gnnrec_csr_remove_edges_workspace_bytes(0, 3),
+        "remove_edges empty workspace");
+  CHECK(gnnrec_csr_remove_edges_workspace_bytes(33, 4) >=
+            2 * 4 * 2 + 8 * 3 + 8 + 4 + 8 * 2,  // 2 mark words, their counts and ranks, 1 chunk
+        "remove_edges workspace covers its parts");
+  CHECK(gnnrec_csr_remove_edges_workspace_bytes((int64_t)500000000, 1000000) < 500000000,
+        "remove_edges workspace below a byte per edge");
+  const size_t rws = gnnrec_csr_remove_edges_workspace_bytes(100, 7);
+#define RM_EDGES(E, n_dst, rm, R, ws, wsb, iout, st)                                          \
+  gnnrec_csr_remove_edges(l16, l16, l16, i16, l16, E, n_dst, rm, R, ws, wsb, l16, l16, l16, iout, \
+                          i16, l16, st, nullptr)
+  CHECK(RM_EDGES(-1, 7, l16, 1, p16, rws, l16, l16) == GNNREC_EINVAL && err_has("negative"),
+        "remove_edges negative E");
+  CHECK(RM_EDGES(100, 7, l16, -1, p16, rws, l16, l16) == GNNREC_EINVAL, "remove_edges negative R");
+  CHECK(RM_EDGES((int64_t)1 << 31, 7, l16, 1, p16, rws, l16, l16) == GNNREC_EINVAL &&
+            err_has("int32"),
+        "remove_edges E range");
+  CHECK(RM_EDGES(100, 0, l16, 1, p16, rws, l16, l16) == GNNREC_EINVAL && err_has("0 rows"),
+        "remove_edges edges without rows");
+  CHECK(RM_EDGES(100, 7, l16, 1, p16, rws, l16, nullptr) == GNNREC_EINVAL && err_has("status"),
+        "remove_edges null status");
+  CHECK(RM_EDGES(0, 0, nullptr, 0, nullptr, 0, l16, l16) == GNNREC_EINVAL && err_has("workspace"),
+        "remove_edges empty problem without workspace");
+  CHECK(RM_EDGES(100, 7, nullptr, 3, p16, rws, l16, l16) == GNNREC_EINVAL &&
+            err_has("removal list"),
+        "remove_edges null list");
+  CHECK(RM_EDGES(100, 7, l16, 1, p16, rws - 1, l16, l16) == GNNREC_EINVAL &&
+            err_has("workspace"),
+        "remove_edges short workspace");
+  CHECK(gnnrec_csr_remove_edges(l16, nullptr, l16, i16, l16, 100, 7, l16, 1, p16, rws, l16, l16,
+                                l16, l16, i16, l16, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "remove_edges null dst");
+  CHECK(gnnrec_csr_remove_edges(l16, l16, l16, nullptr, l16, 100, 7, l16, 1, p16, rws, l16, l16,
+                                l16, l16, i16, l16, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("null CSR"),
+        "remove_edges null indices with a CSR asked for");
+#undef RM_EDGES
 }
 
 // the fused sampler's planner: capacities grow as the docs say, and bad plans are refused

@@ -881,6 +881,58 @@ void csr_build(const Tensor& src, const Tensor& dst, int64_t n_dst, Tensor& ws, 
      "gnnrec_csr_build");
 }
 
+// remove_edges of one relation: the masked COO and the compacted CSR (csr_filter.hip)
+void csr_remove_edges(const Tensor& src, const Tensor& dst, const Tensor& indptr,
+                      const Tensor& indices, const Tensor& eids, const Tensor& rm, Tensor& ws,
+                      Tensor& src_out, Tensor& dst_out, Tensor& kept_eids, Tensor& indptr_out,
+                      Tensor& indices_out, Tensor& eids_out, Tensor& status) {
+  const OneDevice one_device_;
+  dev(src, "src", at::kLong);
+  dev(dst, "dst", at::kLong);
+  dev(indptr, "indptr", at::kLong);
+  dev(indices, "indices", at::kInt);
+  dev(eids, "eids", at::kLong);
+  dev(rm, "rm", at::kLong);
+  dev(ws, "workspace", at::kByte);
+  dev(src_out, "src_out", at::kLong);
+  dev(dst_out, "dst_out", at::kLong);
+  dev(kept_eids, "kept_eids", at::kLong);
+  dev(indptr_out, "indptr_out", at::kLong);
+  dev(indices_out, "indices_out", at::kInt);
+  dev(eids_out, "eids_out", at::kLong);
+  dev(status, "status", at::kLong);
+  // an EMPTY indptr (a CSR has at least one entry): the relation's CSR is not built, the COO
+  // alone is compacted and every CSR operand must be empty
+  const bool csr = indptr.numel() > 0;
+  const int64_t E = dst.numel(), n_dst = csr ? indptr.numel() - 1 : 0, Ec = csr ? E : 0;
+  TORCH_CHECK_VALUE(src.dim() == 1 && dst.dim() == 1 && src.numel() == E &&
+                        src.is_contiguous() && dst.is_contiguous(),
+                    "csr_remove_edges: src and dst must be contiguous 1-D tensors of one length");
+  TORCH_CHECK_VALUE(indices.numel() == Ec && eids.numel() == Ec && indptr.is_contiguous() &&
+                        indices.is_contiguous() && eids.is_contiguous(),
+                    "csr_remove_edges: the CSR must be indptr [n_dst+1], indices [E], eids [E], "
+                    "contiguous (or all empty)");
+  TORCH_CHECK_VALUE(rm.dim() == 1 && rm.is_contiguous(),
+                    "csr_remove_edges: rm must be a contiguous 1-D tensor");
+  TORCH_CHECK_VALUE(src_out.numel() == E && dst_out.numel() == E && kept_eids.numel() == E &&
+                        indptr_out.numel() == indptr.numel() && indices_out.numel() == Ec &&
+                        eids_out.numel() == Ec && status.numel() == 2 &&
+                        src_out.is_contiguous() && dst_out.is_contiguous() &&
+                        kept_eids.is_contiguous() && indptr_out.is_contiguous() &&
+                        indices_out.is_contiguous() && eids_out.is_contiguous() &&
+                        status.is_contiguous(),
+                    "csr_remove_edges: output sizes");
+  if (meta(dst)) return;
+  const c10::DeviceGuard g(dst.device());
+  ck(gnnrec_csr_remove_edges(p<int64_t>(src), p<int64_t>(dst), csr ? p<int64_t>(indptr) : nullptr,
+                             p<int32_t>(indices), p<int64_t>(eids), E, n_dst, p<int64_t>(rm),
+                             rm.numel(), ws.data_ptr(), ws.nbytes(), p<int64_t>(src_out),
+                             p<int64_t>(dst_out), p<int64_t>(kept_eids),
+                             csr ? p<int64_t>(indptr_out) : nullptr, p<int32_t>(indices_out),
+                             p<int64_t>(eids_out), p<int64_t>(status), stream_of(dst)),
+     "gnnrec_csr_remove_edges");
+}
+
 // ---------------------------------------------------------------- f2 fused relation
 // One ConvLayer relation of a TRAINING step (sum / mean aggregation), forward and backward
 // each as ONE dispatcher call that issues every launch from C++ (gnnrec/autograd.py
@@ -1656,6 +1708,9 @@ int64_t csr_build_workspace_bytes(int64_t E, int64_t n_dst) {
   const OneDevice one_device_;
   return (int64_t)gnnrec_csr_build_workspace_bytes(E, n_dst);
 }
+int64_t csr_remove_edges_workspace_bytes(int64_t E, int64_t n_dst) {
+  return (int64_t)gnnrec_csr_remove_edges_workspace_bytes(E, n_dst);
+}
 int64_t sddmm_cos_backward_workspace_bytes(int64_t E, int64_t n_src, int64_t n_dst, int64_t d,
                                            int64_t groups, int64_t K) {
   if (groups > 0)
@@ -1743,6 +1798,10 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor(c!) perm) -> ()");
   m.def("csr_build(Tensor src, Tensor dst, int n_dst, Tensor(a!) workspace, Tensor(b!) indptr, "
         "Tensor(c!) indices, Tensor(d!) eids) -> ()");
+  m.def("csr_remove_edges(Tensor src, Tensor dst, Tensor indptr, Tensor indices, Tensor eids, "
+        "Tensor rm, Tensor(a!) workspace, Tensor(b!) src_out, Tensor(c!) dst_out, "
+        "Tensor(d!) kept_eids, Tensor(e!) indptr_out, Tensor(f!) indices_out, "
+        "Tensor(g!) eids_out, Tensor(h!) status) -> ()");
   m.def("add_(Tensor(a!) a, Tensor b) -> ()");
   m.def("tree_sum_(Tensor(a!) a, Tensor[] rest) -> ()");
   m.def("lstm_step(Tensor P, Tensor indptr, Tensor indices, Tensor order, int t, int n_act, "
@@ -1805,6 +1864,8 @@ TORCH_LIBRARY(gnnrec, m) {
   m.def("csr_from_keys_workspace_bytes(int n_edges, int n_rows) -> int",
         &csr_from_keys_workspace_bytes);
   m.def("csr_build_workspace_bytes(int n_edges, int n_dst) -> int", &csr_build_workspace_bytes);
+  m.def("csr_remove_edges_workspace_bytes(int n_edges, int n_dst) -> int",
+        &csr_remove_edges_workspace_bytes);
   m.def("sddmm_cos_backward_workspace_bytes(int n_edges, int n_src, int n_dst, int d, "
         "int groups=0, int K=0) -> int", &sddmm_cos_backward_workspace_bytes);
   m.def("margin_loss_blocks(int n_pos) -> int", &margin_loss_blocks);
@@ -1841,6 +1902,7 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("csr_transpose", &csr_transpose);               \
   m.impl("csr_from_keys", &csr_from_keys);               \
   m.impl("csr_build", &csr_build);                       \
+  m.impl("csr_remove_edges", &csr_remove_edges);         \
   m.impl("add_", &add_);                                 \
   m.impl("tree_sum_", &tree_sum_);                       \
   m.impl("lstm_step", &lstm_step);                       \

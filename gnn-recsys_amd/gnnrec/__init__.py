@@ -10,10 +10,12 @@ from . import _lib
 from .graph import Block, HeteroGraph, PairGraph, RelGraph, NID, EID, create_graph  # noqa: F401
 from .nn import (ConvLayer, ConvModel, CosinePrediction, HeteroGraphConv,  # noqa: F401
                  NodeEmbedding, PredictingLayer, PredictingModule, max_margin_loss)
+from .sampling import generate_dataloaders, train_valid_split  # noqa: F401
 
 __all__ = ["ConvLayer", "ConvModel", "CosinePrediction", "HeteroGraphConv", "NodeEmbedding",
            "PredictingLayer", "PredictingModule", "max_margin_loss", "HeteroGraph", "Block",
-           "PairGraph", "RelGraph", "NID", "EID", "create_graph"]
+           "PairGraph", "RelGraph", "NID", "EID", "create_graph", "train_valid_split",
+           "generate_dataloaders"]
 
 __version__ = "0.1.0"
 

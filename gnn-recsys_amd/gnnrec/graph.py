@@ -223,6 +223,7 @@ class HeteroGraph:
         self._ndata = {nt: _FrameDict() for nt in self.ntypes}
         self._edata = {ce: _FrameDict() for ce in self.canonical_etypes}
         self._csr = {}
+        self._out_csr = {}
         self._csr_edata = {}
         self._edge_rec = {}
         self.nodes = _TypeAccessor(self._ndata, lambda k: k)
@@ -365,6 +366,139 @@ class HeteroGraph:
             return torch.zeros_like(q, dtype=torch.bool)
         pos = torch.searchsorted(key, q).clamp(max=key.numel() - 1)
         return (key[pos] == q) & ok
+
+    def out_csr(self, etype):
+        """(indptr int64, dst ids int32, eids int64) of the SOURCE-major CSR, in-row order =
+        edge id: build_csr of the reversed relation, cached (remove_edges drops it)."""
+        ce = self.to_canonical_etype(etype)
+        if ce not in self._out_csr:
+            s, d = self._coo[ce]
+            self._out_csr[ce] = build_csr(d, s, self._num_nodes[ce[0]])
+        return self._out_csr[ce]
+
+    def _expand_rows(self, csr, nodes, n_rows: int, what: str):
+        """Every CSR row named in `nodes`, in the order given (repeats and empty rows
+        allowed): (the node repeated per edge, the row's other endpoints, the edge ids)."""
+        indptr, indices, eids = csr
+        nodes = torch.as_tensor(nodes, dtype=torch.int64, device=indptr.device).reshape(-1)
+        if nodes.numel() and (int(nodes.min()) < 0 or int(nodes.max()) >= n_rows):
+            raise ValueError(f"{what}: node ids outside [0, {n_rows})")
+        if indptr.is_cuda:  # the full-neighbourhood sampler's count / scan / fill
+            o_ip, other, eid = ops.sample_neighbors(indptr, indices, eids, nodes.contiguous(), -1)
+            cnt = o_ip[1:] - o_ip[:-1]
+        else:
+            start = indptr[nodes]
+            cnt = indptr[nodes + 1] - start
+            first = torch.cumsum(cnt, 0) - cnt
+            pos = torch.arange(int(cnt.sum()), dtype=torch.int64) + \
+                torch.repeat_interleave(start - first, cnt)
+            other, eid = indices[pos].to(torch.int64), eids[pos]
+        return torch.repeat_interleave(nodes, cnt, output_size=eid.numel()), other, eid
+
+    @staticmethod
+    def _edge_form(u, v, eid, form: str):
+        if form == "uv":
+            return u, v
+        if form == "eid":
+            return eid
+        if form == "all":
+            return u, v, eid
+        raise ValueError(f"form={form!r}: 'uv', 'eid' or 'all'")
+
+    def in_edges(self, v, form="uv", etype=None):
+        """DGL's in_edges: the edges into every node of v, node by node in the order given,
+        ascending edge id within a node (ranges of the cached in-CSR, expanded on a HIP device
+        by the full-neighbourhood sampler's kernels)."""
+        ce = self.to_canonical_etype(etype if etype is not None else self.canonical_etypes[0])
+        self._edge_form(None, None, None, form)
+        dst, src, eid = self._expand_rows(self.in_csr(ce), v, self._num_nodes[ce[2]], "in_edges")
+        return self._edge_form(src, dst, eid, form)
+
+    def out_edges(self, u, form="uv", etype=None):
+        """DGL's out_edges (reference main_inference.py:98, the already-bought lists): the
+        edges out of every node of u, node by node in the order given, ascending edge id
+        within a node — in_edges over the source-major CSR (out_csr)."""
+        ce = self.to_canonical_etype(etype if etype is not None else self.canonical_etypes[0])
+        self._edge_form(None, None, None, form)
+        src, dst, eid = self._expand_rows(self.out_csr(ce), u, self._num_nodes[ce[0]], "out_edges")
+        return self._edge_form(src, dst, eid, form)
+
+    # ---- mutation -------------------------------------------------------
+    def clone(self) -> "HeteroGraph":
+        """DGL's clone: a graph with the same relations, node counts and frames.  Tensors are
+        shared, containers are new — adding or replacing data, or removing edges, in one graph
+        never shows in the other.  The caches already built (CSRs, edge data in CSR order,
+        edge records, membership CSR) are kept by reference."""
+        g = object.__new__(HeteroGraph)
+        g._coo = dict(self._coo)
+        g.canonical_etypes = list(self.canonical_etypes)
+        g._num_nodes = dict(self._num_nodes)
+        g.ntypes, g.etypes = list(self.ntypes), list(self.etypes)
+        g._ndata = {nt: _FrameDict(f.lazy_items()) for nt, f in self._ndata.items()}
+        g._edata = {ce: _FrameDict(f.lazy_items()) for ce, f in self._edata.items()}
+        g._csr, g._out_csr = dict(self._csr), dict(self._out_csr)
+        g._csr_edata = {k: dict(v) for k, v in self._csr_edata.items()}
+        g._edge_rec = dict(self._edge_rec)
+        g.nodes = _TypeAccessor(g._ndata, lambda k: k)
+        g.edges = _TypeAccessor(g._edata, g.to_canonical_etype)
+        g.device = self.device
+        return g
+
+    def remove_edges(self, eids, etype=None) -> None:
+        """DGL's remove_edges, in place: the edges `eids` (any order, duplicates allowed) of
+        relation `etype` leave the graph; its surviving edges keep their order and are
+        renumbered 0..E'-1, and every edge-data tensor of the relation is compacted alike.
+        Node data and the other relations (a reverse relation included) are untouched.  An id
+        outside [0, E) raises ValueError and leaves the graph as it was.
+
+        On a HIP device the COO — and the relation's in-CSR when it is cached — are compacted
+        by gnnrec_csr_remove_edges (no sort; the new CSR is bitwise what build_csr gives on
+        the surviving edges); a CSR that is not cached is built on first use as before.  A
+        graph in host memory does the same with host tensor ops.  The relation's edge data in
+        CSR order, its packed edge records, its membership CSR and its source-major CSR are
+        dropped and rebuilt on next use.
+
+        Loaders and samplers built on this graph BEFORE the call hold edge ids and per-edge
+        scratch of the old numbering: build them after the last removal."""
+        if etype is None and len(self.canonical_etypes) != 1:
+            raise ValueError("remove_edges: etype is needed on a graph with several relations")
+        ce = self.to_canonical_etype(etype if etype is not None else self.canonical_etypes[0])
+        s, d = self._coo[ce]
+        E = int(s.numel())
+        rm = torch.as_tensor(eids, dtype=torch.int64, device=s.device).reshape(-1)
+        if rm.numel() == 0:
+            return
+        csr = self._csr.get(ce)
+        if s.is_cuda:
+            s2, d2, kept, csr2 = ops.csr_remove_edges(s, d, rm, csr)
+            edata = {k: ops.gather_rows(v, kept) for k, v in self._edata[ce].items()}
+        else:
+            if int(rm.min()) < 0 or int(rm.max()) >= E:
+                raise ValueError(f"remove_edges: an edge id lies outside [0, {E})")
+            keep = torch.ones(E, dtype=torch.bool)
+            keep[rm] = False
+            kept = torch.nonzero(keep).reshape(-1)
+            s2, d2 = s[kept], d[kept]
+            edata = {k: v[kept] for k, v in self._edata[ce].items()}
+            csr2 = None
+            if csr is not None:  # the same compaction: kept slots, renumbered ids
+                indptr, indices, ids = csr
+                slot = keep[ids]
+                new_id = torch.cumsum(keep, 0) - 1
+                before = torch.zeros(E + 1, dtype=torch.int64)
+                torch.cumsum(slot, 0, out=before[1:])
+                csr2 = (before[indptr], indices[slot], new_id[ids[slot]])
+        self._coo[ce] = (s2, d2)
+        for k, v in edata.items():
+            self._edata[ce][k] = v
+        if csr2 is not None:
+            self._csr[ce] = csr2
+        else:
+            self._csr.pop(ce, None)
+        self._out_csr.pop(ce, None)
+        self._csr_edata.pop(ce, None)
+        self._csr_edata.pop(("_member",) + ce, None)
+        self._edge_rec.pop(ce, None)
 
     def to(self, device):
         g = HeteroGraph({ce: (s.to(device), d.to(device)) for ce, (s, d) in self._coo.items()},

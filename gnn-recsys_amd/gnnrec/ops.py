@@ -304,6 +304,57 @@ def csr_build(src: torch.Tensor, dst: torch.Tensor, n_dst: int):
     return indptr, indices, eids
 
 
+def csr_remove_edges(src: torch.Tensor, dst: torch.Tensor, rm: torch.Tensor, csr=None):
+    """DGL's remove_edges on one relation, COO and dst-major CSR together
+    (gnnrec_csr_remove_edges: a stream compaction, no sort).  (src, dst) the COO in edge-id
+    order, csr = (indptr, indices, eids) its csr_build (None: the COO alone), rm int64 edge
+    ids in any order (duplicates allowed).  -> (src', dst', kept_eids, csr'): the
+    boolean-masked COO, the old id of every new edge, and (indptr', indices', eids') of the
+    surviving edges in their new numbering — bit for bit csr_build(src', dst', n_dst) — or None.
+    An id outside [0, E) raises ValueError (the one readback of the call: two status words)."""
+    T = _T()
+    dev, E = dst.device, dst.numel()
+    if csr is None:
+        csr = (torch.empty(0, dtype=torch.int64, device=dev),
+               torch.empty(0, dtype=torch.int32, device=dev),
+               torch.empty(0, dtype=torch.int64, device=dev))
+        Ec = 0
+    else:
+        Ec = E
+        if csr[0].numel() < 1:
+            raise ValueError("csr_remove_edges: indptr must have n_dst + 1 entries")
+    indptr, indices, eids = csr
+    for t, n, dt in ((src, "src", torch.int64), (dst, "dst", torch.int64),
+                     (indptr, "indptr", torch.int64), (indices, "indices", torch.int32),
+                     (eids, "eids", torch.int64), (rm, "rm", torch.int64)):
+        _dev(t, n, dt)
+    if src.shape != dst.shape or src.dim() != 1:
+        raise ValueError("csr_remove_edges: src and dst must be 1-D tensors of one length")
+    if indices.numel() != Ec or eids.numel() != Ec:
+        raise ValueError("csr_remove_edges: the CSR does not match the COO's edge count")
+    src, dst, rm = src.contiguous(), dst.contiguous(), rm.reshape(-1).contiguous()
+    indptr, indices, eids = indptr.contiguous(), indices.contiguous(), eids.contiguous()
+    src_o, dst_o, kept = (torch.empty(E, dtype=torch.int64, device=dev) for _ in range(3))
+    indptr_o, indices_o, eids_o = (torch.empty_like(t) for t in (indptr, indices, eids))
+    status = torch.empty(2, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(int(T.csr_remove_edges_workspace_bytes(E, max(indptr.numel() - 1, 0))),
+                         1), dtype=torch.uint8, device=dev)
+    T.csr_remove_edges(src, dst, indptr, indices, eids, rm, ws, src_o, dst_o, kept, indptr_o,
+                       indices_o, eids_o, status)
+    n_new = E
+    if dev.type != "meta":
+        n_new, bad = status.tolist()
+        if bad:
+            raise ValueError(f"csr_remove_edges: an edge id lies outside [0, {E})")
+    def fit(t):  # the valid prefix; copied out when most of the old-size buffer would idle
+        return t[:n_new].clone() if 2 * n_new < E else t[:n_new]
+    new_csr = None
+    if indptr.numel():
+        indptr_o._gnnrec_nnz = n_new
+        new_csr = (indptr_o, fit(indices_o), fit(eids_o))
+    return fit(src_o), fit(dst_o), fit(kept), new_csr
+
+
 def membership_csr(src: torch.Tensor, dst: torch.Tensor, n_src: int, n_dst: int):
     """The dst-major CSR of (src, dst) with every row's source ids ascending — what
     has_edges searches.  Two stable radix sorts of the library (gnnrec_csr_build): by source

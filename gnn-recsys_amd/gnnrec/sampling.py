@@ -952,3 +952,177 @@ class EdgeDataLoader:
             # them with the grouped launch
             neg_g.src_repeats_pos = self.negative_sampler.k
         return input_nodes, pos_g, neg_g, blocks
+
+
+# ---- the reference's split and loader wiring (src/sampling.py:5-114, :117-243) ----
+_BUYS = ('user', 'buys', 'item')
+_CLICKS = ('user', 'clicks', 'item')
+
+
+def _unique_ids(ids: torch.Tensor, n_nodes: int) -> torch.Tensor:
+    """The distinct ids, ascending.  On a HIP device by the relabel ops (mark the ids in a
+    table over the node type, scan, compact the marked ids); a host tensor by torch.unique."""
+    if not ids.is_cuda:
+        return torch.unique(ids)
+    empty = torch.zeros(0, dtype=torch.int64, device=ids.device)
+    nodes, _ = ops.Relabeler(n_nodes, ids.device).relabel(empty, [ids.contiguous()])
+    return nodes
+
+
+def _tail(ids: torch.Tensor, share) -> torch.Tensor:
+    """The last `share` of ids (the most recent edges): ids[int(n (1 - share)):]."""
+    return ids[int(ids.numel() * (1 - share)):]
+
+
+def train_valid_split(valid_graph: HeteroGraph, ground_truth_test, etypes, subtrain_size,
+                      valid_size, reverse_etype, train_on_clicks, remove_train_eids,
+                      clicks_sample=1, purchases_sample=1, *, device_out: bool = False):
+    """Drop-in for the reference's train_valid_split (src/sampling.py:5-114): same arguments,
+    same ten return values in the same order.
+
+    Per relation of `etypes` the last `valid_size` share of the edge ids is the validation
+    set; their endpoints, over every relation of `etypes`, are ground_truth_valid.  The train
+    graph is a clone() of valid_graph from which the validation edges of the trained
+    relations (buys; clicks when train_on_clicks) and of their `reverse_etype` relations are
+    removed (HeteroGraph.remove_edges: on the device a stream compaction); the train ids are
+    all its remaining edges, cut to their most recent purchases_sample / clicks_sample share
+    (the validation ids alike).  remove_train_eids removes the train ids of the LAST relation
+    of `etypes` (and its reverse) from the train graph, as the reference does — a KeyError
+    when that relation is not a trained one.  The subtrain users are
+    np.random.seed(11); np.random.choice(unique train users of etypes[0],
+    int(n subtrain_size), replace=False) — drawn on the host from the user-sized unique list,
+    identical to the reference's — and the subtrain edges are the train edges whose source is
+    one of them: a mark table over the users gathered by the edges' sources, not a Python loop
+    over edges.  Ground truths list relations in `etypes` order, edge-id order inside one.
+
+    device_out=False returns numpy int64 arrays as the reference does; True returns int64
+    tensors on the graph's device and copies no edge-sized array to the host."""
+    import numpy as np
+    g = valid_graph
+    dev = g.device
+    etypes = [tuple(e) for e in etypes]
+
+    def trained(et):
+        return et == _BUYS or (et == _CLICKS and train_on_clicks)
+
+    def cat(parts):
+        return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64, device=dev)
+
+    n_src = max([g.num_nodes(et[0]) for et in etypes] or [0])
+    all_eids_dict, valid_eids_dict, train_eids_dict = {}, {}, {}
+    valid_u, valid_i = [], []
+    for et in etypes:
+        all_eids = torch.arange(g.num_edges(et), dtype=torch.int64, device=dev)
+        valid_eids = _tail(all_eids, valid_size)
+        u, i = g.find_edges(valid_eids, etype=et)
+        valid_u.append(u)
+        valid_i.append(i)
+        all_eids_dict[et] = all_eids
+        if trained(et):
+            valid_eids_dict[et] = valid_eids
+    ground_truth_valid = (cat(valid_u), cat(valid_i))
+    valid_uids = _unique_ids(ground_truth_valid[0], n_src)
+
+    train_graph = g.clone()
+    for et in etypes:
+        if trained(et):
+            train_graph.remove_edges(valid_eids_dict[et], etype=et)
+            train_graph.remove_edges(valid_eids_dict[et], etype=reverse_etype[et])
+            train_eids_dict[et] = torch.arange(train_graph.num_edges(et), dtype=torch.int64,
+                                               device=dev)
+    if purchases_sample != 1:
+        train_eids_dict[_BUYS] = _tail(train_eids_dict[_BUYS], purchases_sample)
+        valid_eids_dict[_BUYS] = _tail(valid_eids_dict[_BUYS], purchases_sample)
+    if clicks_sample != 1 and _CLICKS in train_eids_dict:
+        train_eids_dict[_CLICKS] = _tail(train_eids_dict[_CLICKS], clicks_sample)
+        valid_eids_dict[_CLICKS] = _tail(valid_eids_dict[_CLICKS], clicks_sample)
+    if remove_train_eids:
+        last = etypes[-1]  # the reference's loop variable after its loop: the last relation
+        train_graph.remove_edges(train_eids_dict[last], etype=last)
+        train_graph.remove_edges(train_eids_dict[last], etype=reverse_etype[last])
+
+    # subtrain: users drawn from the first relation's train users (a user-sized host array)
+    np.random.seed(11)
+    first_u, _ = g.find_edges(train_eids_dict[etypes[0]], etype=etypes[0])
+    unique_train = _unique_ids(first_u, n_src).cpu().numpy()
+    chosen = np.random.choice(unique_train, int(len(unique_train) * subtrain_size), replace=False)
+    members = torch.from_numpy(np.asarray(chosen, dtype=np.int64)).to(dev)
+    sub_u, sub_i = [], []
+    for et, train_eids in train_eids_dict.items():
+        u, i = g.find_edges(train_eids, etype=et)
+        mark = torch.zeros(max(n_src, 1), dtype=torch.uint8, device=dev)
+        mark[members] = 1
+        hit = ops.gather_rows(mark, u.contiguous()) if u.is_cuda else mark[u]
+        pick = torch.nonzero(hit).reshape(-1)
+        sub_u.append(u[pick])
+        sub_i.append(i[pick])
+        members = sub_u[-1]  # the reference tests the next relation against these sources
+    ground_truth_subtrain = (cat(sub_u), cat(sub_i))
+    subtrain_uids = _unique_ids(ground_truth_subtrain[0], n_src)
+
+    test_uids = torch.unique(torch.as_tensor(np.asarray(ground_truth_test[0])
+                                             if not torch.is_tensor(ground_truth_test[0])
+                                             else ground_truth_test[0]).to(dev))
+    all_iids = torch.arange(g.num_nodes('item'), dtype=torch.int64, device=dev)
+
+    def out(x):
+        if isinstance(x, dict):
+            return {k: out(v) for k, v in x.items()}
+        if isinstance(x, tuple):
+            return tuple(out(v) for v in x)
+        return x if device_out else x.cpu().numpy()
+
+    return (train_graph, out(train_eids_dict), out(valid_eids_dict), out(subtrain_uids),
+            out(valid_uids), out(test_uids), out(all_iids), out(ground_truth_subtrain),
+            out(ground_truth_valid), out(all_eids_dict))
+
+
+def generate_dataloaders(valid_graph, train_graph, train_eids_dict, valid_eids_dict,
+                         subtrain_uids, valid_uids, test_uids, all_iids, fixed_params,
+                         num_workers, all_sids=None, embedding_layer: bool = True, **params):
+    """Drop-in for the reference's generate_dataloaders (src/sampling.py:117-243) over this
+    package's loaders: -> (edgeloader_train, edgeloader_valid, nodeloader_subtrain,
+    nodeloader_valid, nodeloader_test).
+
+    The blocks have params['n_layers'] layers, one fewer under an explicit embedding layer;
+    fixed_params.neighbor_sampler 'full' takes every neighbour, 'partial' one per layer of
+    three, anything else is a KeyError.  Negatives: Uniform(params['neg_sample_size']).  The
+    train loader batches train_eids_dict over valid_graph and samples from train_graph when
+    fixed_params.remove_train_eids is set; otherwise it batches and samples train_graph and
+    excludes each batch's edges and their reverse-type edges from its blocks.  The validation
+    loader batches valid_eids_dict over valid_graph and samples from train_graph.  The node
+    loaders embed the subtrain and validation users with every item over train_graph, and the
+    test users with every item (and every sport, when the graph has that type) over
+    valid_graph."""
+    n_layers = params['n_layers'] - (1 if embedding_layer else 0)
+    if fixed_params.neighbor_sampler == 'full':
+        sampler = MultiLayerFullNeighborSampler(n_layers)
+    elif fixed_params.neighbor_sampler == 'partial':
+        sampler = MultiLayerNeighborSampler([1, 1, 1], replace=False)
+    else:
+        raise KeyError('Neighbor sampler {} not recognized.'.format(fixed_params.neighbor_sampler))
+    negatives = negative_sampler.Uniform(params['neg_sample_size'])
+    edge_kw = dict(negative_sampler=negatives, batch_size=fixed_params.edge_batch_size,
+                   shuffle=True, drop_last=False, pin_memory=True, num_workers=num_workers)
+    node_kw = dict(batch_size=fixed_params.node_batch_size, shuffle=True, drop_last=False,
+                   num_workers=num_workers)
+    if fixed_params.remove_train_eids:
+        edgeloader_train = EdgeDataLoader(valid_graph, train_eids_dict, sampler,
+                                          g_sampling=train_graph, **edge_kw)
+    else:
+        edgeloader_train = EdgeDataLoader(
+            train_graph, train_eids_dict, sampler, exclude='reverse_types',
+            reverse_etypes={'buys': 'bought-by', 'bought-by': 'buys',
+                            'clicks': 'clicked-by', 'clicked-by': 'clicks'}, **edge_kw)
+    edgeloader_valid = EdgeDataLoader(valid_graph, valid_eids_dict, sampler,
+                                      g_sampling=train_graph, **edge_kw)
+    nodeloader_subtrain = NodeDataLoader(train_graph, {'user': subtrain_uids, 'item': all_iids},
+                                         sampler, **node_kw)
+    nodeloader_valid = NodeDataLoader(train_graph, {'user': valid_uids, 'item': all_iids},
+                                      sampler, **node_kw)
+    test_node_ids = {'user': test_uids, 'item': all_iids}
+    if 'sport' in valid_graph.ntypes:
+        test_node_ids['sport'] = all_sids
+    nodeloader_test = NodeDataLoader(valid_graph, test_node_ids, sampler, **node_kw)
+    return (edgeloader_train, edgeloader_valid, nodeloader_subtrain, nodeloader_valid,
+            nodeloader_test)

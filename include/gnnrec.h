@@ -763,6 +763,28 @@ int gnnrec_csr_build(const int64_t* src, const int64_t* dst, int64_t n_edges, in
                      void* workspace, size_t workspace_bytes, int64_t* indptr, int32_t* indices,
                      int64_t* eids, void* stream);
 
+/* DGLGraph.remove_edges on one relation (the reference's train_valid_split,
+ * src/sampling.py:5-114, takes the validation edges and their reverses out of a clone of the
+ * graph): the surviving edges keep their order and are renumbered 0..E'-1.  Inputs: the
+ * relation's COO (src, dst [n_edges]), its dst-major CSR as gnnrec_csr_build gives it
+ * (indptr [n_dst+1], indices, eids [n_edges]) and the removal list rm [n_rm] of edge ids, in
+ * any order, duplicates allowed.  Outputs, each allocated at the OLD size with a valid prefix
+ * of E' entries: src_out, dst_out (the masked COO), kept_eids (the old id of new edge i),
+ * indptr_out [n_dst+1], indices_out, eids_out — bit for bit gnnrec_csr_build of the surviving
+ * edges, by stream compaction (the CSR keeps a row in edge-id order and the renumbering is
+ * monotonic): no sort.  status[2] (device): {E', bad}; bad != 0 when some rm[i] lies outside
+ * [0, n_edges) — then status[0] = n_edges and no other output is written.  The status is the
+ * call's only readback, and the caller's.  indptr_out == NULL: the COO alone (the CSR
+ * operands are ignored).  n_edges, n_dst < 2^31.  Workspace from
+ * gnnrec_csr_remove_edges_workspace_bytes (about 0.8 B per edge). */
+size_t gnnrec_csr_remove_edges_workspace_bytes(int64_t n_edges, int64_t n_dst);
+int gnnrec_csr_remove_edges(const int64_t* src, const int64_t* dst, const int64_t* indptr,
+                            const int32_t* indices, const int64_t* eids, int64_t n_edges,
+                            int64_t n_dst, const int64_t* rm, int64_t n_rm, void* workspace,
+                            size_t workspace_bytes, int64_t* src_out, int64_t* dst_out,
+                            int64_t* kept_eids, int64_t* indptr_out, int32_t* indices_out,
+                            int64_t* eids_out, int64_t* status, void* stream);
+
 /* K10 — DGLGraph.has_edges_between(u, v, etype) (reference src/train/run.py:95-101,160-166,
  * the false-negative mask; DGL 0.5.2 [ext]: `_CAPI_DGLHeteroHasEdgesBetween`): out[i] = 1
  * when some edge u[i] -> v[i] exists, else 0; ids outside [0, n_src) / [0, n_dst) give 0.
