@@ -195,6 +195,152 @@ static void validation() {
 #undef RM_EDGES
 }
 
+// the four fused aggregate+project entries (spmm_project.hip, spmm_pair_mfma.hip): every
+// refusal comes before a device call and names its own entry; one argument wrong at a time
+struct FusedArgs {
+  const int64_t* indptr;
+  const float *X, *H, *W, *attn_vec;
+  float *attn_state, *out;
+  int64_t ld, n_dst, d;
+  int reduce, epilogue, mode;
+};
+
+static void fused_entries() {
+  int64_t* const l16 = reinterpret_cast<int64_t*>(16);
+  float* const f16 = reinterpret_cast<float*>(16);
+  float* const f24 = reinterpret_cast<float*>(24);  // 8-B aligned, not 16
+  using Call = int (*)(const FusedArgs&);
+  const Call single_valu = [](const FusedArgs& a) {
+    return gnnrec_spmm_project_f32(a.indptr, nullptr, nullptr, a.X, a.ld, a.H, a.ld, a.W, a.W,
+                                   nullptr, nullptr, a.n_dst, a.d, a.reduce, a.epilogue, a.mode,
+                                   0.f, a.attn_vec, a.attn_state, a.out, a.ld, nullptr);
+  };
+  const Call single_mfma = [](const FusedArgs& a) {
+    return gnnrec_spmm_project_mfma_f32(a.indptr, nullptr, nullptr, a.X, a.ld, a.H, a.ld, a.W,
+                                        a.W, nullptr, nullptr, a.n_dst, a.d, a.reduce, a.epilogue,
+                                        a.mode, 0.f, a.attn_vec, a.attn_state, a.out, a.ld,
+                                        nullptr);
+  };
+  const Call project2 = [](const FusedArgs& a) {
+    return gnnrec_spmm_project2_f32(a.indptr, nullptr, nullptr, a.X, a.ld, a.reduce, nullptr,
+                                    a.indptr, nullptr, nullptr, a.X, a.ld, a.reduce, nullptr, a.H,
+                                    a.ld, a.W, a.W, nullptr, nullptr, a.n_dst, a.d, a.epilogue,
+                                    a.mode, a.attn_vec, 0.f, a.out, a.ld, nullptr);
+  };
+  const Call pair = [](const FusedArgs& a) {
+    return gnnrec_spmm_pair_f32(a.indptr, nullptr, nullptr, a.reduce, nullptr, nullptr, a.indptr,
+                                nullptr, nullptr, a.reduce, nullptr, nullptr, a.X, 300, a.ld, a.H,
+                                a.ld, a.W, a.n_dst, a.d, a.epilogue, a.mode, a.attn_vec, 0.f,
+                                a.out, a.ld, nullptr);
+  };
+  struct Entry {
+    const char* name;
+    Call call;
+    bool two;  // two relations: `mode` is a combine, attention takes attn_vec alone
+  };
+  const Entry entries[] = {{"gnnrec_spmm_project_f32", single_valu, false},
+                           {"gnnrec_spmm_project_mfma_f32", single_mfma, false},
+                           {"gnnrec_spmm_project2_f32", project2, true},
+                           {"gnnrec_spmm_pair_f32", pair, true}};
+  for (const Entry& e : entries) {
+    const FusedArgs ok{l16, f16, f16, f16, nullptr, nullptr, f16, 128, 10, 128,
+                       GNNREC_REDUCE_MEAN, GNNREC_EPI_RELU, GNNREC_ACC_ADD};
+    auto refused = [&](const FusedArgs& a, const char* text, const char* what) {
+      const int st = e.call(a);
+      const char* err = gnnrec_last_error();
+      const size_t nl = std::strlen(e.name);
+      CHECK(st == GNNREC_EINVAL, what);
+      CHECK(std::strncmp(err, e.name, nl) == 0 && err[nl] == ':', what);
+      CHECK(err_has(text), what);
+    };
+    FusedArgs a = ok;
+    a.d = 64;
+    refused(a, "only d = 128 (got 64)", "fused d");
+    a = ok;
+    a.epilogue = 4;
+    refused(a, "epilogue must be RELU|L2NORM", "fused epilogue bit");
+    a = ok;
+    a.mode = 17;
+    refused(a, e.two ? "combine must be GNNREC_ACC_ADD, _MAX or _ATTN_LAST"
+                     : "unknown accumulate mode 17", "fused mode");
+    a = ok;
+    a.mode = GNNREC_ACC_ATTN_LAST;
+    a.attn_state = f16;
+    refused(a, e.two ? "attn_vec goes with combine GNNREC_ACC_ATTN_LAST"
+                     : "attention accumulation needs attn_vec, attn_state",
+            "fused attention without attn_vec");
+    a = ok;
+    a.n_dst = -1;
+    refused(a, "negative n_dst", "fused negative n_dst");
+    a = ok;
+    a.H = nullptr;
+    refused(a, "null pointer", "fused null H");
+    a = ok;
+    a.out = nullptr;
+    refused(a, "null pointer", "fused null out");
+    a = ok;
+    a.X = f24;
+    refused(a, "need 16-B aligned rows, out 8-B", "fused misaligned source rows");
+    a = ok;
+    a.ld = 130;
+    refused(a, "need 16-B aligned rows, out 8-B", "fused row stride");
+    a = ok;
+    a.out = reinterpret_cast<float*>(20);
+    refused(a, "need 16-B aligned rows, out 8-B", "fused misaligned out");
+    a = ok;
+    a.reduce = 9;
+    refused(a, "reduce", "fused reduce");
+    a = ok;
+    a.n_dst = 0;
+    a.indptr = nullptr;
+    a.out = nullptr;
+    CHECK(e.call(a) == GNNREC_OK, "fused empty");
+  }
+  // entry-specific refusals
+  CHECK(gnnrec_spmm_project_f32(l16, nullptr, nullptr, f16, 128, f16, 128, f16, nullptr, nullptr,
+                                nullptr, 10, 128, GNNREC_REDUCE_MEAN, 0, GNNREC_ACC_STORE, 0.f,
+                                nullptr, nullptr, f16, 128, nullptr) == GNNREC_EINVAL &&
+            err_has("gnnrec_spmm_project_f32: W_neighT = NULL (pre-projected source rows) is "
+                    "gnnrec_spmm_project_mfma_f32's form"),
+        "valu entry without W_neighT");
+  CHECK(gnnrec_spmm_project_mfma_f32(l16, nullptr, nullptr, f16, 128, f16, 128, f16, nullptr,
+                                     nullptr, nullptr, 10, 128, GNNREC_REDUCE_MAX, 0,
+                                     GNNREC_ACC_STORE, 0.f, nullptr, nullptr, f16, 128, nullptr) ==
+                GNNREC_EINVAL &&
+            err_has("gnnrec_spmm_project_mfma_f32: pre-projected rows (W_neighT = NULL) need a "
+                    "sum or mean reduce"),
+        "PRE with max");
+  CHECK(gnnrec_spmm_project_mfma_f32(l16, nullptr, nullptr, f16, 128, f16, 128, f16, f24, nullptr,
+                                     nullptr, 10, 128, GNNREC_REDUCE_SUM, 0, GNNREC_ACC_STORE, 0.f,
+                                     nullptr, nullptr, f16, 128, nullptr) == GNNREC_EINVAL &&
+            err_has("gnnrec_spmm_project_mfma_f32: X/H/W need 16-B aligned rows, out 8-B"),
+        "mfma misaligned W_neighT");
+  CHECK(gnnrec_spmm_project2_f32(l16, nullptr, nullptr, f16, 128, GNNREC_REDUCE_MAX, nullptr, l16,
+                                 nullptr, nullptr, f16, 128, GNNREC_REDUCE_SUM, nullptr, f16, 128,
+                                 f16, f16, nullptr, nullptr, 10, 128, 0, GNNREC_ACC_ADD, nullptr,
+                                 0.f, f16, 128, nullptr) == GNNREC_EINVAL &&
+            err_has("gnnrec_spmm_project2_f32: pre-projected relations reduce by sum or mean"),
+        "project2 max");
+  CHECK(gnnrec_spmm_project2_f32(l16, nullptr, nullptr, f16, 128, GNNREC_REDUCE_SUM, nullptr, l16,
+                                 nullptr, nullptr, f24, 128, GNNREC_REDUCE_SUM, nullptr, f16, 128,
+                                 f16, f16, nullptr, nullptr, 10, 128, 0, GNNREC_ACC_ADD, nullptr,
+                                 0.f, f16, 128, nullptr) == GNNREC_EINVAL &&
+            err_has("gnnrec_spmm_project2_f32: Y/H/W need 16-B aligned rows, out 8-B"),
+        "project2 misaligned Yb");
+  CHECK(gnnrec_spmm_pair_f32(l16, nullptr, nullptr, GNNREC_REDUCE_SUM, nullptr, nullptr, l16,
+                             nullptr, nullptr, GNNREC_REDUCE_MAX, nullptr, nullptr, f16, 300, 128,
+                             f16, 128, f16, 10, 128, 0, GNNREC_ACC_ADD, nullptr, 0.f, f16, 128,
+                             nullptr) == GNNREC_EINVAL &&
+            err_has("gnnrec_spmm_pair_f32: both relations reduce by sum or mean"),
+        "pair max");
+  CHECK(gnnrec_spmm_pair_f32(l16, nullptr, nullptr, GNNREC_REDUCE_SUM, nullptr, nullptr, l16,
+                             nullptr, nullptr, GNNREC_REDUCE_SUM, nullptr, nullptr, f16, 300, 128,
+                             f16, 128, nullptr, 10, 128, 0, GNNREC_ACC_ADD, nullptr, 0.f, f16, 128,
+                             nullptr) == GNNREC_EINVAL &&
+            err_has("gnnrec_spmm_pair_f32: null WT4"),
+        "pair null WT4");
+}
+
 // the fused sampler's planner: capacities grow as the docs say, and bad plans are refused
 static void sampler_plans() {
   gnnrec_sample_plan P;
@@ -292,6 +438,7 @@ static void dropout_mask() {
 
 int main() {
   validation();
+  fused_entries();
   sampler_plans();
   dropout_mask();
   std::fprintf(stderr, g_fail ? "asan_capi: FAILED\n" : "asan_capi: ok\n");

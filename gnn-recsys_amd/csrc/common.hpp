@@ -4,6 +4,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdarg>
+#include <initializer_list>
+#include <type_traits>
 
 #include "gnnrec.h"
 
@@ -23,6 +25,21 @@ inline int check_launch(const char* what) {
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// A launch's run-time mode as a compile-time constant: f(std::bool_constant<b>{}) and
+// f(std::integral_constant<int, reduce>{}), reduce one of GNNREC_REDUCE_SUM / _MEAN / _MAX
+// (validated by the caller).  Nested, they pick one instantiation of a kernel template.
+template <class F>
+inline void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <class F>
+inline void dispatch_reduce(int reduce, F&& f) {
+  if (reduce == GNNREC_REDUCE_SUM) f(std::integral_constant<int, GNNREC_REDUCE_SUM>{});
+  else if (reduce == GNNREC_REDUCE_MEAN) f(std::integral_constant<int, GNNREC_REDUCE_MEAN>{});
+  else f(std::integral_constant<int, GNNREC_REDUCE_MAX>{});
+}
 
 // CDNA4 wavefront is 64 lanes.
 constexpr int kWave = 64;
@@ -67,3 +84,45 @@ __host__ __device__ inline uint64_t hash3(uint64_t seed, uint64_t a, uint64_t b)
       return GNNREC_EINVAL;              \
     }                                    \
   } while (0)
+
+namespace gnnrec {
+
+// What the four fused aggregate+project entries (spmm_project.hip, spmm_pair_mfma.hip) check
+// alike; `name` is the entry's, so every message keeps its prefix.  d, the epilogue bits,
+// the accumulate mode (one relation: attention takes attn_vec and attn_state) or the combine
+// (two relations: attn_vec goes with GNNREC_ACC_ATTN_LAST), n_dst; then, unless the problem
+// is empty (the entry returns GNNREC_OK): `need` non-null, the tables `rows16` 16-B aligned
+// (a null one is optional) with row strides `ld4` multiples of 4, out 8-B aligned.  `table`:
+// the source table's letter in the message.
+inline int fused_check(const char* name, int64_t d, int epilogue, bool two_relations, int mode,
+                       const void* attn_vec, const void* attn_state, int64_t n_dst, char table,
+                       std::initializer_list<const void*> need,
+                       std::initializer_list<const void*> rows16,
+                       std::initializer_list<int64_t> ld4, const float* out, int64_t ldo) {
+  GNNREC_REQUIRE(d == 128, "%s: only d = %d (got %lld)", name, 128, (long long)d);
+  GNNREC_REQUIRE((epilogue & ~(GNNREC_EPI_RELU | GNNREC_EPI_L2NORM)) == 0,
+                 "%s: epilogue must be RELU|L2NORM", name);
+  if (two_relations) {
+    GNNREC_REQUIRE(mode == GNNREC_ACC_ADD || mode == GNNREC_ACC_MAX ||
+                       mode == GNNREC_ACC_ATTN_LAST,
+                   "%s: combine must be GNNREC_ACC_ADD, _MAX or _ATTN_LAST", name);
+    GNNREC_REQUIRE((mode == GNNREC_ACC_ATTN_LAST) == (attn_vec != nullptr),
+                   "%s: attn_vec goes with combine GNNREC_ACC_ATTN_LAST", name);
+  } else {
+    GNNREC_REQUIRE(mode >= GNNREC_ACC_STORE && mode <= GNNREC_ACC_ATTN_LAST,
+                   "%s: unknown accumulate mode %d", name, mode);
+    GNNREC_REQUIRE(mode < GNNREC_ACC_ATTN_FIRST || (attn_vec && attn_state),
+                   "%s: attention accumulation needs attn_vec, attn_state", name);
+  }
+  GNNREC_REQUIRE(n_dst >= 0, "%s: negative n_dst", name);
+  if (n_dst == 0) return GNNREC_OK;
+  bool have = out != nullptr, ok = ldo % 2 == 0 && (reinterpret_cast<uintptr_t>(out) & 7u) == 0;
+  for (const void* p : need) have = have && p != nullptr;
+  for (const void* p : rows16) ok = ok && aligned16(p);
+  for (const int64_t ld : ld4) ok = ok && ld % 4 == 0;
+  GNNREC_REQUIRE(have, "%s: null pointer", name);
+  GNNREC_REQUIRE(ok, "%s: %c/H/W need 16-B aligned rows, out 8-B", name, table);
+  return GNNREC_OK;
+}
+
+}  // namespace gnnrec

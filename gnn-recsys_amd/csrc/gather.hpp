@@ -1,7 +1,8 @@
 // Shared device helpers of the neighbour gather (a1): used by the aggregation
 // kernels (spmm.hip: dense, packed and dropout-masked source rows) and the fused
 // aggregate+project kernels (spmm_project.hip, spmm_pair_mfma.hip), so all reduce
-// every row in the same fixed order.
+// every row in the same fixed order.  Below the gather: what the fused kernels share past
+// it, their row epilogue and the streamed-weight MFMA projection.
 #pragma once
 #include "common.hpp"
 #include "pack_rows.hpp"
@@ -244,6 +245,206 @@ __device__ __forceinline__ void finalize(Frag<VEC>& acc, int64_t deg, int empty_
       for (int v = 0; v < VEC; ++v) acc.v[v] = 0.f;
     }
   }
+}
+
+// Up to 4 rows [rbase, rbase + nv) of one relation gathered in lockstep (LPR = 32, VEC = 4):
+// their bounds and first 64 indices (and weights) are requested together, then every step
+// issues the loads of all 4 rows (4·LU·2 source rows in flight per wave), so a 10-edge row
+// does not pay its own index -> row round trips.  Each row's neighbours are still summed by
+// lane group in gather_range's order (k = j + u·NPI + grp, ascending: the same sequence for
+// any LU), so the aggregate has gather_range's bits; when any of the rows has more than 64
+// edges, all take gather_range<..., UNROLL, PRE> row by row.  acc[i]: row i's aggregate after
+// combine_groups and finalize, in every lane group; dg[i]: its degree (0 from row nv on).
+template <int REDUCE, bool WEIGHTED, int LU, int UNROLL>
+__device__ __forceinline__ void gather_lockstep4(const int64_t* __restrict__ indptr,
+                                                 const int32_t* __restrict__ indices,
+                                                 const float* __restrict__ ew,
+                                                 const float* __restrict__ X, int64_t ldx,
+                                                 int64_t rbase, int nv, int lane,
+                                                 Frag<4> (&acc)[4], int (&dg)[4]) {
+  constexpr int LPR = 32, VEC = 4, NPI = kWave / LPR, kLR = 4;
+  const int grp = lane / LPR, col = (lane % LPR) * VEC;
+  const float init = (REDUCE == GNNREC_REDUCE_MAX) ? -INFINITY : 0.f;
+  const int64_t ipl = nv > 0 && lane <= nv ? ld_stream(indptr + rbase + lane) : 0;
+  int64_t b[kLR + 1];
+#pragma unroll
+  for (int i = 0; i <= kLR; ++i) b[i] = __shfl(ipl, i <= nv ? i : nv);
+  int ridx[kLR];
+  float rwt[kLR];
+  int dmax = 0;
+#pragma unroll
+  for (int i = 0; i < kLR; ++i) {
+    dg[i] = i < nv ? (int)(b[i + 1] - b[i]) : 0;
+    ridx[i] = lane < dg[i] ? ld_stream(indices + b[i] + lane) : 0;
+    rwt[i] = 0.f;
+    if constexpr (WEIGHTED) rwt[i] = lane < dg[i] ? ld_stream(ew + b[i] + lane) : 0.f;
+    dmax = dg[i] > dmax ? dg[i] : dmax;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[i].v[v] = init;
+  }
+  if (dmax <= 64) {
+    for (int j = 0; j < dmax; j += NPI * LU) {
+      Frag<VEC> val[kLR][LU];
+      bool ok[kLR][LU];
+#pragma unroll
+      for (int i = 0; i < kLR; ++i)
+#pragma unroll
+        for (int u = 0; u < LU; ++u) {
+          ok[i][u] = j + u * NPI + grp < dg[i];
+          const int src = edge_bcast<NPI>(ridx[i], j + u * NPI, grp);
+          if (ok[i][u]) {
+            load_frag<VEC>(val[i][u], X + (int64_t)src * ldx + col);
+          } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) val[i][u].v[v] = 0.f;
+          }
+        }
+#pragma unroll
+      for (int i = 0; i < kLR; ++i)
+#pragma unroll
+        for (int u = 0; u < LU; ++u) {
+          float w = 1.f;
+          if constexpr (WEIGHTED) w = edge_bcast<NPI>(rwt[i], j + u * NPI, grp);
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) {
+            const float m = WEIGHTED ? val[i][u].v[v] * w : val[i][u].v[v];
+            if constexpr (REDUCE == GNNREC_REDUCE_MAX) {
+              if (ok[i][u]) acc[i].v[v] = fmaxf(acc[i].v[v], m);
+            } else {
+              acc[i].v[v] += m;
+            }
+          }
+        }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < kLR; ++i)
+      if (i < nv)
+        gather_range<LPR, VEC, REDUCE, WEIGHTED, UNROLL, true>(
+            b[i], b[i + 1], indices, ew, X, ldx, col, true, lane, grp, acc[i], ridx[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < kLR; ++i) {
+    combine_groups<LPR, VEC, REDUCE>(acc[i]);
+    finalize<VEC, REDUCE>(acc[i], dg[i], 0);
+  }
+}
+
+// ---- row epilogue of the fused aggregate+project kernels: a wave holds one output row, lane
+// = its columns j0 = 2·lane and j0 + 1 ---------------------------------------------------------
+typedef float f32x2s __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void st_stream2(float* p, float a, float b) {
+  __builtin_nontemporal_store(f32x2s{a, b}, reinterpret_cast<f32x2s*>(p));
+}
+
+// ReLU and the zero-guarded row L2 norm over the wave's 64 lanes
+__device__ __forceinline__ void activate(bool relu, bool l2, float& y0, float& y1) {
+  if (relu) {
+    y0 = fmaxf(y0, 0.f);
+    y1 = fmaxf(y1, 0.f);
+  }
+  if (l2) {
+    float ss = y0 * y0 + y1 * y1;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) ss += __shfl_xor(ss, off);
+    float nrm = sqrtf(ss);
+    if (nrm == 0.f) nrm = 1.f;
+    y0 = y0 / nrm;
+    y1 = y1 / nrm;
+  }
+}
+
+// Two relations' activated rows ya, yb into one: max, sum, or (GNNREC_ACC_ATTN_LAST) the
+// softmax over the two relations of s_r = a·y_r, (at0, at1) this lane's pair of a — as the
+// single-relation launches' online form: a first (max s_a, sum 1), then b rescales and
+// normalises.  Then out_div and one non-temporal store to p (the row's columns j0, j0 + 1)
+// when `valid` (wave-uniform; padding rows take part in the shuffles, store nothing).
+__device__ __forceinline__ void combine2_store(float ya0, float ya1, float yb0, float yb1,
+                                               int combine, float at0, float at1, float out_div,
+                                               bool valid, float* p) {
+  float y0, y1;
+  if (combine == GNNREC_ACC_MAX) {
+    y0 = fmaxf(ya0, yb0);
+    y1 = fmaxf(ya1, yb1);
+  } else if (combine == GNNREC_ACC_ATTN_LAST) {
+    float sa = ya0 * at0 + ya1 * at1, sb = yb0 * at0 + yb1 * at1;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      sa += __shfl_xor(sa, off);
+      sb += __shfl_xor(sb, off);
+    }
+    const float mnew = fmaxf(sa, sb);
+    const float keep = expf(sa - mnew), cnew = expf(sb - mnew);
+    const float nrm = 1.f / (1.f * keep + cnew);
+    y0 = (ya0 * keep + yb0 * cnew) * nrm;
+    y1 = (ya1 * keep + yb1 * cnew) * nrm;
+  } else {
+    y0 = ya0 + yb0;
+    y1 = ya1 + yb1;
+  }
+  if (out_div > 0.f) {
+    y0 = y0 / out_div;
+    y1 = y1 / out_div;
+  }
+  if (valid) st_stream2(p, y0, y1);
+}
+
+// ---- 32-row projection on the fp32 MFMA, the B operands (weights) streamed from L2 --------------
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int kMfmaWChunk = 16;  // B operands per chunk (64 — all loaded up front — measured slower)
+
+// Buffer resource over `bytes` of weights at the wave-uniform pointer p: loads then take one
+// 32-bit per-lane offset plus an immediate row offset, instead of hoisted 64-bit addresses
+// (which the compiler spills)
+__device__ __forceinline__ auto weight_rsrc(const void* p, int bytes) {
+  const uint64_t base =
+      ((uint64_t)__builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)p >> 32)) << 32) |
+      (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)p);
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(base), 0, bytes, 0x00020000);
+}
+
+// C (32 × 32) = A · B over KL values of K per lane half, as KL v_mfma_f32_32x32x2_f32: lane
+// (row li = lane & 31, half bh = lane >> 5) reads its A operands from ap[0, KL) (an LDS tile
+// row, ds_read_b128) and B operand i from byte offset wvoff + i·WLD·4 of the weight buffer, in
+// chunks of kMfmaWChunk, double-buffered: the next chunk's loads are in flight under this
+// chunk's MFMAs instead of KL live registers.
+template <int KL, int WLD, class Rsrc>
+__device__ __forceinline__ f32x16 mfma_project32(const Rsrc& wrsrc, int wvoff, const float* ap) {
+  constexpr int kWC = kMfmaWChunk;
+  float bw[2][kWC];
+  auto load_w = [&](float* dst, int i0) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < kWC; ++i)
+      dst[i] = __uint_as_float(
+          __builtin_amdgcn_raw_buffer_load_b32(wrsrc, wvoff, (i0 + i) * WLD * 4, 0));
+  };
+  f32x16 c;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) c[v] = 0.f;
+  load_w(bw[0], 0);
+#pragma unroll
+  for (int ch = 0; ch < KL / kWC; ++ch) {
+    if (ch + 1 < KL / kWC) load_w(bw[(ch + 1) & 1], (ch + 1) * kWC);
+    __builtin_amdgcn_sched_barrier(0);
+    const float* w = bw[ch & 1];
+#pragma unroll
+    for (int i = 0; i < kWC; i += 4) {
+      const f32x4s a = *reinterpret_cast<const f32x4s*>(ap + ch * kWC + i);
+      c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], w[i], c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], w[i + 1], c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], w[i + 2], c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], w[i + 3], c, 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  return c;
+}
+
+// The accumulator to a C tile of row stride ld, cp = the tile's column of this lane (block
+// column + lane & 31).  D map of the 32x32 MFMA: col = lane & 31, row = (v & 3) + 8 (v >> 2) + 4 bh
+__device__ __forceinline__ void store_c32(float* cp, int ld, int bh, const f32x16& c) {
+#pragma unroll
+  for (int v = 0; v < 16; ++v) cp[((v & 3) + 8 * (v >> 2) + 4 * bh) * ld] = c[v];
 }
 
 }  // namespace

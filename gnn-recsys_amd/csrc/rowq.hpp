@@ -45,6 +45,22 @@ void scan_launched(int ticket, hipStream_t stream);
 int device_cus();       // CUs of the current device
 int cu_reserve();       // CUs the row kernels leave free for concurrent kernels
 
+// Grid of a persistent row kernel: per_cu blocks on every CU but those reserved for
+// concurrent kernels (8 CUs at the least), and no more blocks than work units (tiles, or a
+// block's rows per iteration)
+inline int64_t persistent_blocks(int64_t units, int per_cu) {
+  const int64_t cus = device_cus() - cu_reserve();
+  const int64_t blocks = per_cu * (cus > 8 ? cus : 8);
+  return units < blocks ? units : blocks;
+}
+
+// A row-queue slot (rowq_slot) when each of the grid's `drawers` (the waves, or the blocks,
+// that draw tickets of rq_ch rows) has several tickets of work; else nullptr: static rows
+inline unsigned* rowq_slot_for(int64_t n_dst, int64_t drawers, int rq_ch, hipStream_t stream,
+                               int* ticket) {
+  return n_dst >= drawers * rq_ch * 4 ? rowq_slot(stream, ticket) : nullptr;
+}
+
 __device__ inline int xcc_id() {
   // s_getreg_b32 hwreg(HW_REG_XCC_ID, 0, 4): size-1 in [15:11], offset [10:6], id 20
   return __builtin_amdgcn_s_getreg((3 << 11) | 20) & (kRqHeads - 1);
@@ -138,6 +154,63 @@ __device__ inline bool rq_next(RqCursor& c, unsigned* q, int64_t n, int ch, int6
     c.t = rq_take(q + c.h * kRqStride);
   }
 }
+
+// Block-level tile cursor, for kernels whose whole block (of 64-lane waves) consumes one
+// chunk of whole T-row tiles at a time: begin() once, then next(r0, r1) until false; the block
+// runs the tiles of [r0, r1).  Chunks come from the row queue (blocks that start late, behind
+// another kernel, take fewer) or, statically, one tile at a time from this block's XCD's
+// contiguous eighth of the tiles (blocks are dispatched round-robin over the 8 XCDs, so each
+// XCD's L2 sees contiguous indptr / H / out rows).  A grid of fewer than 8 blocks (small
+// relations) leaves some XCDs without a block: then a plain block-strided walk, so no
+// eighth of the tiles is left without an owner.
+// Wave 0 draws each chunk and publishes it through blk_r (two LDS words of the caller); one
+// barrier follows the publication.  None is needed before the next one: every published
+// chunk has r0 < r1, so it runs at least one tile, and every tile ends in a __syncthreads()
+// that all waves reach only after they have read blk_r — wave 0 cannot overwrite it sooner.
+template <int T>
+struct TileCursor {
+  RqCursor c;
+  unsigned* rq;
+  int64_t n, st, st_hi, per;
+  int rq_ch;
+  int64_t* blk_r;
+
+  __device__ void begin(unsigned* q, int64_t n_rows, int ch, int64_t* lds_r) {
+    rq = q;
+    n = n_rows;
+    rq_ch = ch;
+    blk_r = lds_r;
+    if (rq != nullptr && threadIdx.x < 64) rq_begin(c, rq);
+    const int64_t tiles = (n + T - 1) / T;
+    const bool by_xcd = gridDim.x >= (unsigned)kRqHeads;
+    const int xcd = by_xcd ? blockIdx.x % kRqHeads : 0;
+    per = by_xcd ? (int64_t)(gridDim.x - xcd + kRqHeads - 1) / kRqHeads  // blocks on xcd
+                 : (int64_t)gridDim.x;
+    st = by_xcd ? tiles * xcd / kRqHeads + blockIdx.x / kRqHeads : (int64_t)blockIdx.x;
+    st_hi = by_xcd ? tiles * (xcd + 1) / kRqHeads : tiles;
+  }
+
+  __device__ bool next(int64_t& r0, int64_t& r1) {
+    if (threadIdx.x < 64) {
+      int64_t a = -1, b = 0;
+      if (rq != nullptr) {
+        if (!rq_next(c, rq, n, rq_ch, a, b)) a = -1;
+      } else if (st < st_hi) {
+        a = st * T;
+        b = a + T < n ? a + T : n;
+        st += per;
+      }
+      if (threadIdx.x == 0) {
+        blk_r[0] = a;
+        blk_r[1] = b;
+      }
+    }
+    __syncthreads();
+    r0 = blk_r[0];
+    r1 = blk_r[1];
+    return r0 >= 0;
+  }
+};
 
 // end of a queued launch: after every wave of the block has left rq_for_each, one lane
 // counts the block out; the last block of the grid zeroes the slot for its next user

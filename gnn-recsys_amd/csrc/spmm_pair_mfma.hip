@@ -14,25 +14,25 @@
 // one raw 512 MB table, and all four 128×128 projections run in the epilogue.  Four fp32
 // weight matrices (256 KiB) do not fit in LDS, so the VALU matvec of the one-relation kernel
 // is out; instead a block owns 32-row tiles:
-//   gather   each of the 8 waves gathers 4 rows of relation a, then of relation b, in
-//            lockstep (the 4 rows' bounds and first 64 indices requested together, then
-//            steps of 2·LU neighbours of all 4 rows; per row the summation order of
-//            spmm_csr_kernel's gather_range, so each aggregate has its bits), into the
-//            LDS tile A = [h_self | agg_a | agg_b] (32 × 384 fp32, row stride 388 floats:
-//            conflict-free ds_read_b128);
+//   gather   each of the 8 waves gathers 4 rows of relation a, then of relation b, with
+//            gather.hpp's gather_lockstep4 (the one spmm_project_mfma_kernel calls; per row
+//            gather_range's summation order, so each aggregate has spmm_csr_kernel's bits),
+//            into the LDS tile A = [h_self | agg_a | agg_b] (32 × 384 fp32, row stride 388
+//            floats: conflict-free ds_read_b128);
 //   project  wave w owns output columns 32·(w & 3) of relation (w >> 2): C = [h | agg_r] ·
 //            [W_self,r | W_neigh,r]ᵀ, K = 256, as 128 v_mfma_f32_32x32x2_f32 — lane half 0
 //            consumes the self half of K, lane half 1 the neighbour half (a fixed
 //            permutation of the reference's summation order); the B operands stream from L2
 //            by buffer loads out of ONE packed [4][128][128] k-major weight array (a
-//            wave-uniform base), in chunks of 16 double-buffered under the MFMAs — 256 KiB
-//            per 32 rows instead of per row pair;
+//            wave-uniform base) in gather.hpp's mfma_project32, chunks of 16 double-buffered
+//            under the MFMAs — 256 KiB per 32 rows instead of per row pair;
 //   epilogue C of both relations lands in LDS over the A tile; each wave finishes 4 rows:
-//            bias (+ the non-empty bias), ReLU, zero-guarded L2 norm and the combine (sum,
-//            max, or the attention softmax over the two relations) in registers, one
-//            non-temporal 512-B store per row.
+//            bias (+ the non-empty bias), then gather.hpp's activate and combine2_store
+//            (spmm_project2_pipe_kernel's row epilogue: sum, max, or the attention softmax
+//            over the two relations, in registers), one non-temporal 512-B store per row.
 // Two blocks per CU (≈50 KiB of LDS each), so one block's MFMA phase runs under the other's
-// gather.  Rows come from the row queue in whole tiles, or an XCD-contiguous static walk.
+// gather.  Rows come in whole tiles through rowq.hpp's TileCursor (the row queue, or an
+// XCD-contiguous static walk).
 //
 // Measured (C5 user side, 10M rows × (40 + 10) edges, 268 GB, tools/gpu/r04c_pairvar.sh and
 // r04e_pairh.sh): the gather phase alone (a round-4 timing build) 34.6 ms = 0.969 of
@@ -71,11 +71,8 @@ constexpr int kQALd = 3 * kQD + 4;       // A tile row stride (floats)
 constexpr int kQCLd = kQD + 8;           // C tile row stride
 constexpr int kQLU = 2;   // lockstep gather: steps of 2·LU neighbours of 4 rows at once
 constexpr int kQU = 4;    // gather_range unroll for rows above 64 edges
-constexpr int kQWC = 16;  // B operands per chunk
 static_assert(2 * kQT * kQCLd <= kQT * kQALd, "C tiles must fit over the A tile");
-
-typedef float f32x16q __attribute__((ext_vector_type(16)));
-typedef float f32x4q __attribute__((ext_vector_type(4)));
+static_assert(kQRows == 4, "a wave gathers its rows with one gather_lockstep4");
 
 // Four consecutive A-tile elements of row `row`, columns [c, c + 4)
 __device__ __forceinline__ void put4(float* tile, int row, int c, float4 v) {
@@ -91,90 +88,22 @@ struct RawRel {
   int mean;
 };
 
-__device__ __forceinline__ void activate_q(bool relu, bool l2, float& y0, float& y1) {
-  if (relu) {
-    y0 = fmaxf(y0, 0.f);
-    y1 = fmaxf(y1, 0.f);
-  }
-  if (l2) {
-    float ss = y0 * y0 + y1 * y1;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) ss += __shfl_xor(ss, off);
-    float nrm = sqrtf(ss);
-    if (nrm == 0.f) nrm = 1.f;
-    y0 = y0 / nrm;
-    y1 = y1 / nrm;
-  }
-}
-
 // The 4 rows [rbase, rbase + nv) of one relation, gathered in lockstep into A tile columns
 // [cofs, cofs + 128) of tile rows [r0, r0 + 4); their non-empty flags into ne[].
 template <bool W>
-__device__ __forceinline__ void gather4(const RawRel& r, const float* __restrict__ X,
-                                        int64_t ldx, int64_t rbase, int nv, float* As,
-                                        int r0, int cofs, int* ne, int lane) {
-  constexpr int LPR = 32, VEC = 4, NPI = kWave / LPR, U = kQLU, kLR = 4;
-  const int grp = lane / LPR, col = (lane % LPR) * VEC;
-  const int64_t ipl = nv > 0 && lane <= nv ? ld_stream(r.indptr + rbase + lane) : 0;
-  int64_t b[kLR + 1];
+__device__ __forceinline__ void gather_rel(const RawRel& r, const float* __restrict__ X,
+                                           int64_t ldx, int64_t rbase, int nv, float* As,
+                                           int r0, int cofs, int* ne, int lane) {
+  Frag<4> acc[kQRows];
+  int dg[kQRows];
+  gather_lockstep4<GNNREC_REDUCE_SUM, W, kQLU, kQU>(r.indptr, r.indices, r.ew, X, ldx, rbase, nv,
+                                                    lane, acc, dg);
 #pragma unroll
-  for (int i = 0; i <= kLR; ++i) b[i] = __shfl(ipl, i <= nv ? i : nv);
-  int ridx[kLR], dg[kLR];
-  float rwt[kLR];
-  int dmax = 0;
-#pragma unroll
-  for (int i = 0; i < kLR; ++i) {
-    dg[i] = i < nv ? (int)(b[i + 1] - b[i]) : 0;
-    ridx[i] = lane < dg[i] ? ld_stream(r.indices + b[i] + lane) : 0;
-    rwt[i] = 0.f;
-    if constexpr (W) rwt[i] = lane < dg[i] ? ld_stream(r.ew + b[i] + lane) : 0.f;
-    dmax = dg[i] > dmax ? dg[i] : dmax;
-  }
-  Frag<VEC> acc[kLR];
-#pragma unroll
-  for (int i = 0; i < kLR; ++i)
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) acc[i].v[v] = 0.f;
-  if (dmax <= 64) {
-    for (int j = 0; j < dmax; j += NPI * U) {
-      Frag<VEC> val[kLR][U];
-#pragma unroll
-      for (int i = 0; i < kLR; ++i)
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int k = j + u * NPI + grp;
-          const int src = __shfl(ridx[i], k & 63);
-          if (k < dg[i]) {
-            load_frag<VEC>(val[i][u], X + (int64_t)src * ldx + col);
-          } else {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) val[i][u].v[v] = 0.f;
-          }
-        }
-#pragma unroll
-      for (int i = 0; i < kLR; ++i)
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          float w = 1.f;
-          if constexpr (W) w = __shfl(rwt[i], (j + u * NPI + grp) & 63);
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) acc[i].v[v] += W ? val[i][u].v[v] * w : val[i][u].v[v];
-        }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < kLR; ++i)
-      if (i < nv)
-        gather_range<LPR, VEC, GNNREC_REDUCE_SUM, W, kQU, true>(
-            b[i], b[i + 1], r.indices, r.ew, X, ldx, col, true, lane, grp, acc[i], ridx[i]);
-  }
-#pragma unroll
-  for (int i = 0; i < kLR; ++i) {
-    combine_groups<LPR, VEC, GNNREC_REDUCE_SUM>(acc[i]);
-    if (r.mean) finalize<VEC, GNNREC_REDUCE_MEAN>(acc[i], dg[i], 0);
-    if (grp == 0)
-      put4(As, r0 + i, cofs + col,
-                make_float4(acc[i].v[0], acc[i].v[1], acc[i].v[2], acc[i].v[3]));
+  for (int i = 0; i < kQRows; ++i) {
+    if (r.mean) finalize<4, GNNREC_REDUCE_MEAN>(acc[i], dg[i], 0);
+    if (lane < 32)
+      put4(As, r0 + i, cofs + lane * 4,
+           make_float4(acc[i].v[0], acc[i].v[1], acc[i].v[2], acc[i].v[3]));
     if (lane == 0) ne[r0 + i] = dg[i] > 0;
   }
 }
@@ -200,13 +129,8 @@ __global__ __launch_bounds__(kQWaves * 64, 4) void spmm_pair_mfma_kernel(
 
   // B operands: lane half bh of a relation-rr wave reads matrix 2·rr + bh of the packed
   // [W_self,aᵀ, W_neigh,aᵀ, W_self,bᵀ, W_neigh,bᵀ] (each k-major 128×128): element
-  // [i][32·cb + li]; one 32-bit per-lane offset + an immediate row offset per load
-  const void* const wsrc = WT4;
-  const uint64_t wbase = ((uint64_t)__builtin_amdgcn_readfirstlane(
-                              (unsigned)((uintptr_t)wsrc >> 32)) << 32) |
-                         (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)wsrc);
-  const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<void*>(wbase), 0, 4 * kQD * kQD * 4, 0x00020000);
+  // [i][32·cb + li]
+  const auto wrsrc = weight_rsrc(WT4, 4 * kQD * kQD * 4);
   const int wvoff = ((2 * rr + bh) * kQD * kQD + 32 * cb + li) * 4;
   // A operands: row li of the tile, K columns [0, 128) (self) for lane half 0 and the
   // relation's aggregate [128 + 128·rr, +128) for lane half 1
@@ -226,48 +150,21 @@ __global__ __launch_bounds__(kQWaves * 64, 4) void spmm_pair_mfma_kernel(
       const int rl = 2 * q + bh;
       hs[q] = rl < nv ? ld_stream4(H + (rbase + rl) * ldh + col) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    gather4<WA>(ra, X, ldx, rbase, nv, As, r0, kQD, nes[0], lane);
-    gather4<WB>(rb, X, ldx, rbase, nv, As, r0, 2 * kQD, nes[1], lane);
+    gather_rel<WA>(ra, X, ldx, rbase, nv, As, r0, kQD, nes[0], lane);
+    gather_rel<WB>(rb, X, ldx, rbase, nv, As, r0, 2 * kQD, nes[1], lane);
 #pragma unroll
     for (int q = 0; q < kQRows / 2; ++q) put4(As, r0 + 2 * q + bh, col, hs[q]);
     __syncthreads();
 
-    constexpr int kWC = kQWC;
-    float bw[2][kWC];
-    auto load_w = [&](float* dst, int i0) __attribute__((always_inline)) {
-#pragma unroll
-      for (int i = 0; i < kWC; ++i)
-        dst[i] = __uint_as_float(
-            __builtin_amdgcn_raw_buffer_load_b32(wrsrc, wvoff, (i0 + i) * kQD * 4, 0));
-    };
-    f32x16q c;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) c[v] = 0.f;
-    load_w(bw[0], 0);
-#pragma unroll
-    for (int ch = 0; ch < kQD / kWC; ++ch) {
-      if (ch + 1 < kQD / kWC) load_w(bw[(ch + 1) & 1], (ch + 1) * kWC);
-      __builtin_amdgcn_sched_barrier(0);
-      const float* w = bw[ch & 1];
-#pragma unroll
-      for (int i = 0; i < kWC; i += 4) {
-        const f32x4q a = *reinterpret_cast<const f32x4q*>(ap + ch * kWC + i);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], w[i], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], w[i + 1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], w[i + 2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], w[i + 3], c, 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    const f32x16 c = mfma_project32<kQD, kQD>(wrsrc, wvoff, ap);
     __syncthreads();  // every wave's MFMAs have read the A tile: C goes over it
-    // D map of the 32x32 MFMA: col = lane & 31, row = (v & 3) + 8 (v >> 2) + 4 bh
-    float* cp = (rr ? Cb : Ca) + 32 * cb + li;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) cp[((v & 3) + 8 * (v >> 2) + 4 * bh) * kQCLd] = c[v];
+    store_c32((rr ? Cb : Ca) + 32 * cb + li, kQCLd, bh, c);
     __syncthreads();
 
     const float ba0 = ra.bias ? ra.bias[j0] : 0.f, ba1 = ra.bias ? ra.bias[j0 + 1] : 0.f;
     const float bb0 = rb.bias ? rb.bias[j0] : 0.f, bb1 = rb.bias ? rb.bias[j0 + 1] : 0.f;
+    const bool attn = combine == GNNREC_ACC_ATTN_LAST;
+    const float at0 = attn ? attn_vec[j0] : 0.f, at1 = attn ? attn_vec[j0 + 1] : 0.f;
 #pragma unroll
     for (int r = 0; r < kQRows; ++r) {
       const int rl = r0 + r;
@@ -283,76 +180,19 @@ __global__ __launch_bounds__(kQWaves * 64, 4) void spmm_pair_mfma_kernel(
         yb0 += rb.bias_ne[j0];
         yb1 += rb.bias_ne[j0 + 1];
       }
-      activate_q(relu, l2, ya0, ya1);
-      activate_q(relu, l2, yb0, yb1);
-      float y0, y1;
-      if (combine == GNNREC_ACC_MAX) {
-        y0 = fmaxf(ya0, yb0);
-        y1 = fmaxf(ya1, yb1);
-      } else if (combine == GNNREC_ACC_ATTN_LAST) {
-        // softmax over the two relations of s_r = a·y_r, as the single-relation launches'
-        // online form: a first (max s_a, sum 1), then b rescales and normalises
-        const float at0 = attn_vec[j0], at1 = attn_vec[j0 + 1];
-        float sa = ya0 * at0 + ya1 * at1, sb = yb0 * at0 + yb1 * at1;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          sa += __shfl_xor(sa, off);
-          sb += __shfl_xor(sb, off);
-        }
-        const float mnew = fmaxf(sa, sb);
-        const float keep = expf(sa - mnew), cnew = expf(sb - mnew);
-        const float nrm = 1.f / (1.f * keep + cnew);
-        y0 = (ya0 * keep + yb0 * cnew) * nrm;
-        y1 = (ya1 * keep + yb1 * cnew) * nrm;
-      } else {
-        y0 = ya0 + yb0;
-        y1 = ya1 + yb1;
-      }
-      if (out_div > 0.f) {
-        y0 = y0 / out_div;
-        y1 = y1 / out_div;
-      }
-      if (r < nv) {
-        typedef float f32x2s __attribute__((ext_vector_type(2)));
-        __builtin_nontemporal_store(f32x2s{y0, y1},
-                                    reinterpret_cast<f32x2s*>(out + (rbase + r) * ldo + j0));
-      }
+      activate(relu, l2, ya0, ya1);
+      activate(relu, l2, yb0, yb1);
+      combine2_store(ya0, ya1, yb0, yb1, combine, at0, at1, out_div, r < nv,
+                     out + (rbase + r) * ldo + j0);
     }
     __syncthreads();  // the tile's LDS is free for the next one
   };
 
-  // whole tiles from the row queue, or statically from this block's XCD's contiguous
-  // eighth of the tiles (block-strided below 8 blocks); wave 0 draws, the block follows
-  RqCursor cur;
-  if (rq != nullptr && wave == 0) rq_begin(cur, rq);
-  const int64_t tiles = (n_dst + kQT - 1) / kQT;
-  const bool by_xcd = gridDim.x >= (unsigned)kRqHeads;
-  const int xcd = by_xcd ? blockIdx.x % kRqHeads : 0;
-  const int64_t per = by_xcd ? (int64_t)(gridDim.x - xcd + kRqHeads - 1) / kRqHeads
-                             : (int64_t)gridDim.x;
-  int64_t st = by_xcd ? tiles * xcd / kRqHeads + blockIdx.x / kRqHeads : (int64_t)blockIdx.x;
-  const int64_t st_hi = by_xcd ? tiles * (xcd + 1) / kRqHeads : tiles;
-  while (true) {
-    if (wave == 0) {
-      int64_t r0 = -1, r1 = 0;
-      if (rq != nullptr) {
-        if (!rq_next(cur, rq, n_dst, rq_ch, r0, r1)) r0 = -1;
-      } else if (st < st_hi) {
-        r0 = st * kQT;
-        r1 = r0 + kQT < n_dst ? r0 + kQT : n_dst;
-        st += per;
-      }
-      if (lane == 0) {
-        blk_r[0] = r0;
-        blk_r[1] = r1;
-      }
-    }
-    __syncthreads();
-    const int64_t r0 = blk_r[0], r1 = blk_r[1];
-    __syncthreads();  // blk_r read by every wave before wave 0 may overwrite it
-    if (r0 < 0) break;
+  TileCursor<kQT> cur;
+  cur.begin(rq, n_dst, rq_ch, blk_r);
+  int64_t r0, r1;
+  while (cur.next(r0, r1))
     for (int64_t t0 = r0; t0 < r1; t0 += kQT) tile(t0, r1);
-  }
   if (rq != nullptr) rq_finish(rq);
 }
 
@@ -368,50 +208,33 @@ extern "C" int gnnrec_spmm_pair_f32(
     const float* bias_nonempty_b, const float* X, int64_t n_src, int64_t ldx, const float* H,
     int64_t ldh, const float* WT4, int64_t n_dst, int64_t d, int epilogue,
     int combine, const float* attn_vec, float out_div, float* out, int64_t ldo, void* stream) {
-  GNNREC_REQUIRE(d == kQD, "gnnrec_spmm_pair_f32: only d = %d (got %lld)", kQD, (long long)d);
+  const char* const name = "gnnrec_spmm_pair_f32";
   GNNREC_REQUIRE((reduce_a == GNNREC_REDUCE_SUM || reduce_a == GNNREC_REDUCE_MEAN) &&
                      (reduce_b == GNNREC_REDUCE_SUM || reduce_b == GNNREC_REDUCE_MEAN),
                  "gnnrec_spmm_pair_f32: both relations reduce by sum or mean");
-  GNNREC_REQUIRE((epilogue & ~(GNNREC_EPI_RELU | GNNREC_EPI_L2NORM)) == 0,
-                 "gnnrec_spmm_pair_f32: epilogue must be RELU|L2NORM");
-  GNNREC_REQUIRE(combine == GNNREC_ACC_ADD || combine == GNNREC_ACC_MAX ||
-                     combine == GNNREC_ACC_ATTN_LAST,
-                 "gnnrec_spmm_pair_f32: combine must be GNNREC_ACC_ADD, _MAX or _ATTN_LAST");
-  GNNREC_REQUIRE((combine == GNNREC_ACC_ATTN_LAST) == (attn_vec != nullptr),
-                 "gnnrec_spmm_pair_f32: attn_vec goes with combine GNNREC_ACC_ATTN_LAST");
-  GNNREC_REQUIRE(n_dst >= 0, "gnnrec_spmm_pair_f32: negative n_dst");
-  if (n_dst == 0) return GNNREC_OK;
-  GNNREC_REQUIRE(indptr_a && indptr_b && X && H && out, "gnnrec_spmm_pair_f32: null pointer");
+  const int st = fused_check(name, d, epilogue, true, combine, attn_vec, nullptr, n_dst, 'X',
+                             {indptr_a, indptr_b, X, H}, {X, H, WT4}, {ldx, ldh}, out, ldo);
+  if (st != GNNREC_OK || n_dst == 0) return st;
   GNNREC_REQUIRE(WT4 != nullptr, "gnnrec_spmm_pair_f32: null WT4");
-  GNNREC_REQUIRE(aligned16(X) && aligned16(H) && aligned16(WT4) && ldx % 4 == 0 &&
-                     ldh % 4 == 0 && ldo % 2 == 0 &&
-                     (reinterpret_cast<uintptr_t>(out) & 7u) == 0,
-                 "gnnrec_spmm_pair_f32: X/H/W need 16-B aligned rows, out 8-B");
-  const int64_t tiles = (n_dst + kQT - 1) / kQT;
-  const int64_t cus = device_cus() - cu_reserve();
-  int64_t blocks = 2 * (cus > 8 ? cus : 8);
-  if (blocks > tiles) blocks = tiles;
-  constexpr int rq_ch = 2 * kQT;  // rows per queue ticket (whole tiles)
+  GNNREC_REQUIRE(n_src >= 0, "gnnrec_spmm_pair_f32: negative n_src");
+  // two persistent 8-wave blocks per CU, a queue ticket of two whole tiles per block draw
+  const int64_t blocks = persistent_blocks((n_dst + kQT - 1) / kQT, 2);
+  constexpr int rq_ch = 2 * kQT;
   hipStream_t s = as_stream(stream);
   int ticket = -1;
-  unsigned* rq = n_dst >= blocks * rq_ch * 4 ? rowq_slot(s, &ticket) : nullptr;
+  unsigned* rq = rowq_slot_for(n_dst, blocks, rq_ch, s, &ticket);
   const RawRel a{indptr_a, indices_a, ew_a, bias_a, bias_nonempty_a,
                  reduce_a == GNNREC_REDUCE_MEAN};
   const RawRel b{indptr_b, indices_b, ew_b, bias_b, bias_nonempty_b,
                  reduce_b == GNNREC_REDUCE_MEAN};
   const dim3 grid((unsigned)blocks), block(kQWaves * 64);
-  GNNREC_REQUIRE(n_src >= 0, "gnnrec_spmm_pair_f32: negative n_src");
-#define GNNREC_SPQ(WA_, WB_)                                                                 \
-  hipLaunchKernelGGL((spmm_pair_mfma_kernel<WA_, WB_>), grid, block, 0, s, a, b, X, ldx, H, ldh, \
-                     WT4, n_dst, epilogue, combine, attn_vec, out_div, out, ldo, rq, rq_ch)
-  if (ew_a) {
-    if (ew_b) GNNREC_SPQ(true, true);
-    else GNNREC_SPQ(true, false);
-  } else {
-    if (ew_b) GNNREC_SPQ(false, true);
-    else GNNREC_SPQ(false, false);
-  }
-#undef GNNREC_SPQ
+  dispatch_bool(ew_a != nullptr, [&](auto wa) {
+    dispatch_bool(ew_b != nullptr, [&](auto wb) {
+      hipLaunchKernelGGL((spmm_pair_mfma_kernel<decltype(wa)::value, decltype(wb)::value>), grid,
+                         block, 0, s, a, b, X, ldx, H, ldh, WT4, n_dst, epilogue, combine,
+                         attn_vec, out_div, out, ldo, rq, rq_ch);
+    });
+  });
   rowq_launched(ticket, s);
-  return check_launch("gnnrec_spmm_pair_f32");
+  return check_launch(name);
 }

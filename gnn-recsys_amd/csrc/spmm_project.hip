@@ -7,9 +7,9 @@
 // Why: the gather is HBM-bound (≈6.5 TB/s) and leaves the CU's VALU and LDS mostly
 // idle, while the separate projection GEMM re-reads h_self and the aggregate from HBM,
 // writes the output again and, run beside the next gather, competes with it for HBM.
-// Here each wave owns ROWS destination rows at a time end to end: gather (the same
-// gather_range / fixed xor-tree combine as spmm_csr_kernel, so the aggregate is
-// bit-identical to the plain kernel's), then a 128×128 matvec per row on the VALU with
+// Here each wave owns ROWS destination rows at a time end to end: gather (gather.hpp's
+// gather_range and combine_groups, which spmm_csr_kernel runs: the aggregate has the plain
+// kernel's bits), then a 128×128 matvec per row on the VALU with
 // both weight matrices resident in LDS (loaded once per persistent block), ReLU,
 // zero-guarded row L2 norm, hetero accumulate, one 512-B store.  HBM per row: the
 // gathered rows + h_self row + output row; no aggregate round trip, no GEMM launch.
@@ -18,6 +18,14 @@
 // spmm + gemm otherwise, and when the CSR has rows above the heavy-row split.
 // LDS: W_selfᵀ, W_neighᵀ (2 × 64 KiB, k-major so a lane's two output columns are one
 // ds_read_b64) + per wave ROWS × (agg, self) row slots read back as broadcasts.
+//
+// Three kernels live here (spmm_project_kernel above, spmm_project_mfma_kernel and
+// spmm_project2_pipe_kernel below) beside spmm_pair_mfma.hip's fourth; what they have in
+// common is written once: gather.hpp has the lockstep 4-row gather (gather_lockstep4), the
+// row epilogue (activate, combine2_store) and the streamed-weight MFMA projection
+// (weight_rsrc, mfma_project32, store_c32); rowq.hpp the block-level tile walk (TileCursor)
+// and the launch geometry (persistent_blocks, rowq_slot_for); common.hpp the entries'
+// argument checks (fused_check) and the launch dispatch (dispatch_bool, dispatch_reduce).
 #include "common.hpp"
 #include "gather.hpp"
 #include "rowq.hpp"
@@ -33,9 +41,9 @@ constexpr int kPRows = 2;      // rows per wave per iteration (halves the LDS we
 // rows per queue ticket (rowq.hpp): four iterations, ≈120 µs at C4 (a multiple of kPRows)
 constexpr int kFusedChunk = 8;
 
-// The per-row epilogue both fused kernels share: lane = output columns j0, j0+1 of `row`
-// (y = the projected pre-activation incl. bias): ReLU, zero-guarded L2 norm over the 64
-// lanes, the cross-relation accumulate (store / add / max / online-softmax attention),
+// The per-row epilogue both single-relation kernels share: lane = output columns j0, j0+1 of
+// `row` (y = the projected pre-activation incl. bias): gather.hpp's activate (ReLU, zero-guarded
+// L2 norm), the cross-relation accumulate (store / add / max / online-softmax attention),
 // out_div, one float2 store per lane.  `valid` (wave-uniform) is false for padding rows
 // past the range end: they take part in the shuffles, store nothing.
 struct EpiArgs {
@@ -47,23 +55,6 @@ struct EpiArgs {
   int64_t ldo;
   int j0;
 };
-
-// ReLU and the zero-guarded row L2 norm over the wave's 64 lanes (2 columns per lane)
-__device__ __forceinline__ void activate(bool relu, bool l2, float& y0, float& y1) {
-  if (relu) {
-    y0 = fmaxf(y0, 0.f);
-    y1 = fmaxf(y1, 0.f);
-  }
-  if (l2) {
-    float ss = y0 * y0 + y1 * y1;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) ss += __shfl_xor(ss, off);
-    float nrm = sqrtf(ss);
-    if (nrm == 0.f) nrm = 1.f;
-    y0 = y0 / nrm;
-    y1 = y1 / nrm;
-  }
-}
 
 __device__ __forceinline__ void epilogue_row(const EpiArgs& e, int64_t row, bool valid,
                                              float y0, float y1) {
@@ -111,8 +102,7 @@ __device__ __forceinline__ void epilogue_row(const EpiArgs& e, int64_t row, bool
     y0 = y0 / e.out_div;
     y1 = y1 / e.out_div;
   }
-  typedef float f32x2s __attribute__((ext_vector_type(2)));
-  __builtin_nontemporal_store(f32x2s{y0, y1}, reinterpret_cast<f32x2s*>(p));  // (gather.hpp)
+  st_stream2(reinterpret_cast<float*>(p), y0, y1);
 }
 
 template <int REDUCE, bool WEIGHTED, int UNROLL>
@@ -251,9 +241,10 @@ __global__ __launch_bounds__(kPWaves * 64) void spmm_project_kernel(
 // Why: the VALU kernel above re-reads both 64 KiB weight matrices from LDS for every 2
 // rows, a fixed per-row cost that the gather hides at C4's 50 edges/row but that bounds
 // a 10-edges/row relation (C5 bought-by: 18.0 ms fused vs 7.6 ms gather + 7.1 ms GEMM).
-// Here a block of 8 waves owns 32-row tiles: the waves gather 4 rows each (the same
-// gather_range / xor tree as spmm_csr_kernel, so the aggregate is bit-identical) into an
-// LDS tile A = [h_self | agg] (32 × 256 fp32), then 32×128 = A · [W_self | W_neigh]ᵀ
+// Here a block of 8 waves owns 32-row tiles: the waves gather 4 rows each (gather.hpp's
+// gather_lockstep4: gather_range's order and xor tree, the aggregate bit-identical to
+// spmm_csr_kernel's) into an LDS tile A = [h_self | agg] (32 × 256 fp32), then 32×128 = A ·
+// [W_self | W_neigh]ᵀ
 // runs as v_mfma_f32_32x32x2_f32: wave w owns output columns 32·(w&3) and K half (w>>2)
 // (W_self or W_neigh), i.e. 64 B operands per lane, re-read from L2 per tile by buffer
 // loads (held across the gather they would spill: 128 VGPRs is the budget at two 8-wave
@@ -266,7 +257,9 @@ __global__ __launch_bounds__(kPWaves * 64) void spmm_project_kernel(
 //
 // The gather runs the wave's 4 rows in lockstep (all 4 rows' index loads, then steps of
 // 2·LU neighbours of every row), so a 10-edge row does not pay its own index -> row round
-// trips; the W operands stream from L2 in chunks of 16 under the MFMAs.
+// trips; the W operands stream from L2 in chunks of 16 under the MFMAs (gather.hpp's
+// mfma_project32 and store_c32, which spmm_pair_mfma_kernel runs too); tiles come through
+// rowq.hpp's TileCursor.
 //
 // PRE (W_neighT = NULL): the source rows arrive already projected (Y = X·W_neighᵀ, linear
 // reductions only), the neighbour term is their aggregate, read from the A tile in the
@@ -288,19 +281,15 @@ __global__ __launch_bounds__(kPWaves * 64) void spmm_project_kernel(
 constexpr int kSppU = 4;   // the VALU kernel's gather wave-instructions in flight per lane
 constexpr int kSpmU = 4;   // the MFMA kernel's, rows > 64 edges
 constexpr int kSpmLU = 2;  // lockstep gather: steps of 2·LU neighbours of 4 rows at once
-constexpr int kSpmWC = 16; // W operands per chunk (64 — all loaded up front — measured slower)
 constexpr int kSpmEU = 4;  // epilogue rows unrolled
-constexpr int kMT = 32;                  // rows per tile
-constexpr int kMB = kMT / 32;            // 32-row MFMA blocks per tile
+constexpr int kMT = 32;                  // rows per tile: one 32-row MFMA block
 constexpr int kMWaves = 8;               // waves per block
 constexpr int kMRows = kMT / kMWaves;    // rows gathered per wave per tile
 constexpr int kALd = 2 * kPD + 4;        // A tile row stride (floats): conflict-free b128 reads
 constexpr int kCLd = kPD + 8;            // C tile row stride: the two lane halves' stores
                                          // land on disjoint banks
 constexpr int kALds = kMT * kALd;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+static_assert(kMRows == 4, "a wave gathers its rows with one gather_lockstep4");
 
 template <int REDUCE, bool WEIGHTED, int UNROLL, bool PRE>
 __global__ __launch_bounds__(kMWaves * 64, 4) void spmm_project_mfma_kernel(
@@ -318,30 +307,20 @@ __global__ __launch_bounds__(kMWaves * 64, 4) void spmm_project_mfma_kernel(
   float* const Cs0 = lds + kALds;
   float* const Cs1 = Cs0 + kMT * kCLd;
 
-  constexpr int LPR = 32, VEC = 4;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int grp = lane / LPR;
   const int li = lane & 31, bh = lane >> 5;
-  const int col = li * VEC;
+  const int col = li * 4;
   const int j0 = 2 * lane;
   const int cb = wave & 3, kh = wave >> 2;
-  const float init = (REDUCE == GNNREC_REDUCE_MAX) ? -INFINITY : 0.f;
   const bool attn = accum >= GNNREC_ACC_ATTN_FIRST;
   const float a0 = attn ? attn_vec[j0] : 0.f, a1 = attn ? attn_vec[j0 + 1] : 0.f;
   const EpiArgs ep{(epilogue & GNNREC_EPI_RELU) != 0, (epilogue & GNNREC_EPI_L2NORM) != 0,
                    attn, accum, out_div, a0, a1, attn_state, out, ldo, j0};
 
   // B operands: lane supplies Wᵀ[k][n], k = 64·bh + i of this wave's K half, n = 32·cb + li
-  // (PRE: the self half alone, split over the two wave halves: k = 64·kh + 32·bh + i).
-  // Buffer loads: one 32-bit per-lane offset plus an immediate row offset, instead of 64
-  // hoisted 64-bit addresses (which the compiler spills)
+  // (PRE: the self half alone, split over the two wave halves: k = 64·kh + 32·bh + i)
   constexpr int kKL = PRE ? 32 : 64;  // K per lane half
-  const float* WTb = (kh && !PRE) ? WnT : WsT;
-  const uint64_t wbase = ((uint64_t)__builtin_amdgcn_readfirstlane(
-                              (unsigned)((uintptr_t)WTb >> 32)) << 32) |
-                         (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)WTb);
-  const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(wbase), 0,
-                                                       kPD * kPD * 4, 0x00020000);
+  const auto wrsrc = weight_rsrc((kh && !PRE) ? WnT : WsT, kPD * kPD * 4);
   const int wvoff = ((PRE ? 64 * kh + 32 * bh : 64 * bh) * kPD + 32 * cb + li) * 4;
 
   // one tile: rows [t0, min(t0 + kMT, lim)); every wave of the block takes part
@@ -349,147 +328,34 @@ __global__ __launch_bounds__(kMWaves * 64, 4) void spmm_project_mfma_kernel(
     const int64_t rbase = t0 + wave * kMRows;
     const int64_t left = lim - rbase;
     const int nv = (int)(left <= 0 ? 0 : left < kMRows ? left : kMRows);
-    // the rows' bounds in one load (nv == 0: rows past the range end — nothing is read,
+    // the wave's 4 rows in lockstep (nv == 0: rows past the range end — nothing is read,
     // the tile rows stay zero); self rows two per instruction, after the gather
-    const int64_t ipl = nv > 0 && lane <= nv ? indptr[rbase + lane] : 0;
-    auto bound = [&](int r) { return __shfl(ipl, r <= nv ? r : nv); };
-    auto self_rows = [&](int q) {  // lanes of half bh: self row 2q + bh
-      const int rl = 2 * q + bh;
-      return rl < nv ? *reinterpret_cast<const float4*>(H + (rbase + rl) * ldh + col)
-                     : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    // Lockstep gather, 4 rows at a time: their bounds and first 64 indices are requested up
-    // front, then every step issues the loads of all 4 rows (4·LU·2 source rows in flight
-    // per wave), so a 10-edge row does not pay its own index -> row round trips.  Each
-    // row's neighbours are still summed by group in gather_range's order
-    // (k = j + u·NPI + grp, ascending — the same sequence for any LU): the same aggregate
-    // bits.  Rows with more than 64 edges take gather_range row by row.
-    constexpr int NPI = kWave / LPR, U = kSpmLU, kLR = 4;
+    Frag<4> acc[kMRows];
+    int dg[kMRows];
+    gather_lockstep4<REDUCE, WEIGHTED, kSpmLU, UNROLL>(indptr, indices, ew, X, ldx, rbase, nv,
+                                                       lane, acc, dg);
 #pragma unroll
-    for (int g = 0; g < kMRows; g += kLR) {
-      int ridx[kLR];
-      float rwt[kLR];
-      int dg[kLR];
-      int dmax = 0;
-#pragma unroll
-      for (int r = 0; r < kLR; ++r) {
-        const int64_t b = bound(g + r);
-        dg[r] = g + r < nv ? (int)(bound(g + r + 1) - b) : 0;
-        ridx[r] = lane < dg[r] ? ld_stream(indices + b + lane) : 0;
-        rwt[r] = 0.f;
-        if constexpr (WEIGHTED) rwt[r] = lane < dg[r] ? ld_stream(ew + b + lane) : 0.f;
-        dmax = dg[r] > dmax ? dg[r] : dmax;
-      }
-      Frag<VEC> acc[kLR];
-#pragma unroll
-      for (int r = 0; r < kLR; ++r)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[r].v[v] = init;
-      if (dmax <= 64) {
-        for (int j = 0; j < dmax; j += NPI * U) {
-          Frag<VEC> val[kLR][U];
-          bool ok[kLR][U];
-#pragma unroll
-          for (int r = 0; r < kLR; ++r)
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-              const int k = j + u * NPI + grp;
-              ok[r][u] = k < dg[r];
-              const int src = edge_bcast<NPI>(ridx[r], j + u * NPI, grp);
-              if (ok[r][u]) {
-                load_frag<VEC>(val[r][u], X + (int64_t)src * ldx + col);
-              } else {
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) val[r][u].v[v] = 0.f;
-              }
-            }
-#pragma unroll
-          for (int r = 0; r < kLR; ++r)
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-              float w = 1.f;
-              if constexpr (WEIGHTED) w = edge_bcast<NPI>(rwt[r], j + u * NPI, grp);
-#pragma unroll
-              for (int v = 0; v < VEC; ++v) {
-                const float m = WEIGHTED ? val[r][u].v[v] * w : val[r][u].v[v];
-                if constexpr (REDUCE == GNNREC_REDUCE_MAX) {
-                  if (ok[r][u]) acc[r].v[v] = fmaxf(acc[r].v[v], m);
-                } else {
-                  acc[r].v[v] += m;
-                }
-              }
-            }
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < kLR; ++r)
-          if (g + r < nv)
-            gather_range<LPR, VEC, REDUCE, WEIGHTED, UNROLL, true>(
-                bound(g + r), bound(g + r + 1), indices, ew, X, ldx, col, true, lane, grp,
-                acc[r], ridx[r]);
-      }
-#pragma unroll
-      for (int r = 0; r < kLR; ++r) {
-        combine_groups<LPR, VEC, REDUCE>(acc[r]);
-        finalize<VEC, REDUCE>(acc[r], dg[r], 0);
-        const int rl = wave * kMRows + g + r;
-        if (grp == 0)
-          *reinterpret_cast<float4*>(&As[rl * kALd + kPD + col]) =
-              make_float4(acc[r].v[0], acc[r].v[1], acc[r].v[2], acc[r].v[3]);
-        if (lane == 0) nes[rl] = dg[r] > 0;
-      }
+    for (int r = 0; r < kMRows; ++r) {
+      const int rl = wave * kMRows + r;
+      if (bh == 0)
+        *reinterpret_cast<float4*>(&As[rl * kALd + kPD + col]) =
+            make_float4(acc[r].v[0], acc[r].v[1], acc[r].v[2], acc[r].v[3]);
+      if (lane == 0) nes[rl] = dg[r] > 0;
     }
 #pragma unroll
-    for (int q = 0; q < kMRows / 2; ++q)
-      *reinterpret_cast<float4*>(&As[(wave * kMRows + 2 * q + bh) * kALd + col]) = self_rows(q);
+    for (int q = 0; q < kMRows / 2; ++q) {  // lanes of half bh: self row 2q + bh
+      const int rl = 2 * q + bh;
+      *reinterpret_cast<float4*>(&As[(wave * kMRows + rl) * kALd + col]) =
+          rl < nv ? *reinterpret_cast<const float4*>(H + (rbase + rl) * ldh + col)
+                  : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     __syncthreads();
 
-    // C_kh[rows 32·b.., 32 × 32 block cb] = A[:, K half kh] · Wᵀ[K half kh, block cb], the
-    // W operands loaded once for the tile's kMB row blocks
-    // W operands stream in 4 chunks of 16 (double-buffered, the next chunk's loads in
-    // flight under this chunk's MFMAs) instead of 64 live registers
-    constexpr int kWC = kSpmWC;
-    float bw[2][kWC];
-    auto load_w = [&](float* dst, int i0) __attribute__((always_inline)) {
-#pragma unroll
-      for (int i = 0; i < kWC; ++i)
-        dst[i] = __uint_as_float(
-            __builtin_amdgcn_raw_buffer_load_b32(wrsrc, wvoff, (i0 + i) * kPD * 4, 0));
-    };
-    f32x16 c[kMB];
-#pragma unroll
-    for (int b = 0; b < kMB; ++b)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) c[b][v] = 0.f;
-    const float* ap = As + li * kALd + (PRE ? 64 * kh + 32 * bh : kh * kPD + 64 * bh);
-    {
-      load_w(bw[0], 0);
-#pragma unroll
-      for (int ch = 0; ch < kKL / kWC; ++ch) {
-        if (ch + 1 < kKL / kWC) load_w(bw[(ch + 1) & 1], (ch + 1) * kWC);
-        __builtin_amdgcn_sched_barrier(0);
-        const float* w = bw[ch & 1];
-#pragma unroll
-        for (int i = 0; i < kWC; i += 4) {
-#pragma unroll
-          for (int b = 0; b < kMB; ++b) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(ap + 32 * b * kALd + ch * kWC + i);
-            c[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], w[i], c[b], 0, 0, 0);
-            c[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], w[i + 1], c[b], 0, 0, 0);
-            c[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], w[i + 2], c[b], 0, 0, 0);
-            c[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], w[i + 3], c[b], 0, 0, 0);
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    // D map of the 32x32 MFMA: col = lane & 31, row = (v & 3) + 8 (v >> 2) + 4 h
-    float* cp = (kh ? Cs1 : Cs0) + 32 * cb + li;
-#pragma unroll
-    for (int b = 0; b < kMB; ++b)
-#pragma unroll
-      for (int v = 0; v < 16; ++v)
-        cp[(32 * b + (v & 3) + 8 * (v >> 2) + 4 * bh) * kCLd] = c[b][v];
+    // C_kh[32 × 32 block cb] = A[:, K half kh] · Wᵀ[K half kh, block cb]; the two K halves
+    // (PRE: the two halves of the self half) meet in LDS
+    const f32x16 c = mfma_project32<kKL, kPD>(
+        wrsrc, wvoff, As + li * kALd + (PRE ? 64 * kh + 32 * bh : kh * kPD + 64 * bh));
+    store_c32((kh ? Cs1 : Cs0) + 32 * cb + li, kCLd, bh, c);
     __syncthreads();
 
 #pragma unroll kSpmEU
@@ -516,42 +382,11 @@ __global__ __launch_bounds__(kMWaves * 64, 4) void spmm_project_mfma_kernel(
     __syncthreads();  // As / Cs / nes free for the next tile
   };
 
-  // chunks of rows come from the queue (blocks that start late, behind another kernel,
-  // take fewer) or, statically, one tile at a time from this block's XCD's contiguous
-  // eighth of the tiles (blocks are dispatched round-robin over the 8, so each XCD's L2
-  // sees contiguous indptr / H / out rows); wave 0 draws and publishes each chunk, and
-  // the whole block processes it — one call site of the tile body
-  RqCursor cur;
-  if (rq != nullptr && wave == 0) rq_begin(cur, rq);
-  const int64_t tiles = (n_dst + kMT - 1) / kMT;
-  // a grid of fewer than 8 blocks (small relations) leaves some XCDs without a block: then
-  // a plain block-strided walk, so no eighth of the tiles is left without an owner
-  const bool by_xcd = gridDim.x >= (unsigned)kRqHeads;
-  const int xcd = by_xcd ? blockIdx.x % kRqHeads : 0;
-  const int64_t per = by_xcd ? (int64_t)(gridDim.x - xcd + kRqHeads - 1) / kRqHeads  // blocks on xcd
-                             : (int64_t)gridDim.x;
-  int64_t st = by_xcd ? tiles * xcd / kRqHeads + blockIdx.x / kRqHeads : (int64_t)blockIdx.x;
-  const int64_t st_hi = by_xcd ? tiles * (xcd + 1) / kRqHeads : tiles;
-  while (true) {
-    if (wave == 0) {
-      int64_t r0 = -1, r1 = 0;
-      if (rq != nullptr) {
-        if (!rq_next(cur, rq, n_dst, rq_ch, r0, r1)) r0 = -1;
-      } else if (st < st_hi) {
-        r0 = st * kMT;
-        r1 = r0 + kMT < n_dst ? r0 + kMT : n_dst;
-        st += per;
-      }
-      if (lane == 0) {
-        blk_r[0] = r0;
-        blk_r[1] = r1;
-      }
-    }
-    __syncthreads();
-    const int64_t r0 = blk_r[0], r1 = blk_r[1];
-    if (r0 < 0) break;
+  TileCursor<kMT> cur;
+  cur.begin(rq, n_dst, rq_ch, blk_r);
+  int64_t r0, r1;
+  while (cur.next(r0, r1))
     for (int64_t t0 = r0; t0 < r1; t0 += kMT) tile(t0, r1);  // ends with a barrier
-  }
   if (rq != nullptr) rq_finish(rq);
 }
 
@@ -568,53 +403,34 @@ extern "C" int gnnrec_spmm_project_f32(const int64_t* indptr, const int32_t* ind
                                        int reduce, int epilogue, int accum, float out_div,
                                        const float* attn_vec, float* attn_state, float* out,
                                        int64_t ldo, void* stream) {
-  GNNREC_REQUIRE(d == kPD, "gnnrec_spmm_project_f32: only d = %d (got %lld)", kPD,
-                 (long long)d);
+  const char* const name = "gnnrec_spmm_project_f32";
   GNNREC_REQUIRE(reduce == GNNREC_REDUCE_SUM || reduce == GNNREC_REDUCE_MEAN ||
                      reduce == GNNREC_REDUCE_MAX,
                  "gnnrec_spmm_project_f32: unknown reduce %d", reduce);
-  GNNREC_REQUIRE((epilogue & ~(GNNREC_EPI_RELU | GNNREC_EPI_L2NORM)) == 0,
-                 "gnnrec_spmm_project_f32: epilogue must be RELU|L2NORM");
-  GNNREC_REQUIRE(accum >= GNNREC_ACC_STORE && accum <= GNNREC_ACC_ATTN_LAST,
-                 "gnnrec_spmm_project_f32: unknown accumulate mode %d", accum);
-  GNNREC_REQUIRE(accum < GNNREC_ACC_ATTN_FIRST || (attn_vec && attn_state),
-                 "gnnrec_spmm_project_f32: attention accumulation needs attn_vec, attn_state");
-  GNNREC_REQUIRE(n_dst >= 0, "gnnrec_spmm_project_f32: negative n_dst");
-  if (n_dst == 0) return GNNREC_OK;
+  const int st = fused_check(name, d, epilogue, false, accum, attn_vec, attn_state, n_dst, 'X',
+                             {indptr, X, H, W_selfT}, {X, H, W_selfT, W_neighT}, {ldx, ldh}, out,
+                             ldo);
+  if (st != GNNREC_OK || n_dst == 0) return st;
   GNNREC_REQUIRE(W_neighT, "gnnrec_spmm_project_f32: W_neighT = NULL (pre-projected source "
                            "rows) is gnnrec_spmm_project_mfma_f32's form");
-  GNNREC_REQUIRE(indptr && X && H && W_selfT && out, "gnnrec_spmm_project_f32: null pointer");
-  GNNREC_REQUIRE(aligned16(X) && aligned16(H) && aligned16(W_selfT) && aligned16(W_neighT) &&
-                     ldx % 4 == 0 && ldh % 4 == 0 && ldo % 2 == 0 &&
-                     (reinterpret_cast<uintptr_t>(out) & 7u) == 0,
-                 "gnnrec_spmm_project_f32: X/H/W need 16-B aligned rows, out 8-B");
-  // one persistent block per CU, minus the CUs reserved for concurrent kernels
+  // one persistent block per CU; queued rows when every wave has several tickets of work
   const int64_t per_block = (int64_t)kPWaves * kPRows;
-  int64_t blocks = (n_dst + per_block - 1) / per_block;
-  const int64_t cus = device_cus() - cu_reserve();
-  if (blocks > (cus > 8 ? cus : 8)) blocks = cus > 8 ? cus : 8;
-  // queued rows when every wave has several tickets of work
+  const int64_t blocks = persistent_blocks((n_dst + per_block - 1) / per_block, 1);
   const int rq_ch = kFusedChunk;
   hipStream_t s = as_stream(stream);
   int ticket = -1;
-  unsigned* rq = n_dst >= blocks * kPWaves * rq_ch * 4 ? rowq_slot(s, &ticket) : nullptr;
+  unsigned* rq = rowq_slot_for(n_dst, blocks * kPWaves, rq_ch, s, &ticket);
   const dim3 grid((unsigned)blocks), block(kPWaves * 64);
-#define GNNREC_SPP(R, W)                                                                      \
-  hipLaunchKernelGGL((spmm_project_kernel<R, W, kSppU>), grid, block, 0, s, indptr, indices, ew, \
-                     X, ldx, H, ldh, W_selfT, W_neighT, bias, bias_nonempty, n_dst, epilogue,    \
-                     accum, out_div, attn_vec, attn_state, out, ldo, rq, rq_ch)
-  if (ew) {
-    if (reduce == GNNREC_REDUCE_SUM) GNNREC_SPP(GNNREC_REDUCE_SUM, true);
-    else if (reduce == GNNREC_REDUCE_MEAN) GNNREC_SPP(GNNREC_REDUCE_MEAN, true);
-    else GNNREC_SPP(GNNREC_REDUCE_MAX, true);
-  } else {
-    if (reduce == GNNREC_REDUCE_SUM) GNNREC_SPP(GNNREC_REDUCE_SUM, false);
-    else if (reduce == GNNREC_REDUCE_MEAN) GNNREC_SPP(GNNREC_REDUCE_MEAN, false);
-    else GNNREC_SPP(GNNREC_REDUCE_MAX, false);
-  }
-#undef GNNREC_SPP
+  dispatch_bool(ew != nullptr, [&](auto w) {
+    dispatch_reduce(reduce, [&](auto r) {
+      hipLaunchKernelGGL((spmm_project_kernel<decltype(r)::value, decltype(w)::value, kSppU>),
+                         grid, block, 0, s, indptr, indices, ew, X, ldx, H, ldh, W_selfT, W_neighT,
+                         bias, bias_nonempty, n_dst, epilogue, accum, out_div, attn_vec,
+                         attn_state, out, ldo, rq, rq_ch);
+    });
+  });
   rowq_launched(ticket, s);
-  return check_launch("gnnrec_spmm_project_f32");
+  return check_launch(name);
 }
 
 extern "C" int gnnrec_spmm_project_mfma_f32(const int64_t* indptr, const int32_t* indices,
@@ -626,67 +442,42 @@ extern "C" int gnnrec_spmm_project_mfma_f32(const int64_t* indptr, const int32_t
                                             float out_div, const float* attn_vec,
                                             float* attn_state, float* out, int64_t ldo,
                                             void* stream) {
-  GNNREC_REQUIRE(d == kPD, "gnnrec_spmm_project_mfma_f32: only d = %d (got %lld)", kPD,
-                 (long long)d);
+  const char* const name = "gnnrec_spmm_project_mfma_f32";
   GNNREC_REQUIRE(reduce == GNNREC_REDUCE_SUM || reduce == GNNREC_REDUCE_MEAN ||
                      reduce == GNNREC_REDUCE_MAX,
                  "gnnrec_spmm_project_mfma_f32: unknown reduce %d", reduce);
-  GNNREC_REQUIRE((epilogue & ~(GNNREC_EPI_RELU | GNNREC_EPI_L2NORM)) == 0,
-                 "gnnrec_spmm_project_mfma_f32: epilogue must be RELU|L2NORM");
-  GNNREC_REQUIRE(accum >= GNNREC_ACC_STORE && accum <= GNNREC_ACC_ATTN_LAST,
-                 "gnnrec_spmm_project_mfma_f32: unknown accumulate mode %d", accum);
-  GNNREC_REQUIRE(accum < GNNREC_ACC_ATTN_FIRST || (attn_vec && attn_state),
-                 "gnnrec_spmm_project_mfma_f32: attention accumulation needs attn_vec, "
-                 "attn_state");
-  GNNREC_REQUIRE(n_dst >= 0, "gnnrec_spmm_project_mfma_f32: negative n_dst");
-  if (n_dst == 0) return GNNREC_OK;
-  GNNREC_REQUIRE(indptr && X && H && W_selfT && out,
-                 "gnnrec_spmm_project_mfma_f32: null pointer");
+  const int st = fused_check(name, d, epilogue, false, accum, attn_vec, attn_state, n_dst, 'X',
+                             {indptr, X, H, W_selfT}, {X, H, W_selfT, W_neighT}, {ldx, ldh}, out,
+                             ldo);
+  if (st != GNNREC_OK || n_dst == 0) return st;
   // W_neighT == NULL: X holds pre-projected source rows (X·W_neighᵀ), the neighbour half
   // is their aggregate itself — linear reductions only
   const bool pre = W_neighT == nullptr;
   GNNREC_REQUIRE(!pre || reduce != GNNREC_REDUCE_MAX,
                  "gnnrec_spmm_project_mfma_f32: pre-projected rows (W_neighT = NULL) need a "
                  "sum or mean reduce");
-  GNNREC_REQUIRE(aligned16(X) && aligned16(H) && aligned16(W_selfT) &&
-                     (pre || aligned16(W_neighT)) && ldx % 4 == 0 && ldh % 4 == 0 &&
-                     ldo % 2 == 0 && (reinterpret_cast<uintptr_t>(out) & 7u) == 0,
-                 "gnnrec_spmm_project_mfma_f32: X/H/W need 16-B aligned rows, out 8-B");
-  // two persistent 8-wave blocks per CU, minus the CUs reserved for concurrent kernels
-  const int64_t tiles = (n_dst + kMT - 1) / kMT;
-  const int64_t cus = device_cus() - cu_reserve();
-  int64_t blocks = 2 * (cus > 8 ? cus : 8);
-  if (blocks > tiles) blocks = tiles;
-  constexpr int rq_ch = 2 * kMT;  // rows per queue ticket (whole tiles)
+  // two persistent 8-wave blocks per CU, a queue ticket of two whole tiles per block draw
+  const int64_t blocks = persistent_blocks((n_dst + kMT - 1) / kMT, 2);
+  constexpr int rq_ch = 2 * kMT;
   hipStream_t s = as_stream(stream);
   int ticket = -1;
-  unsigned* rq = n_dst >= blocks * rq_ch * 4 ? rowq_slot(s, &ticket) : nullptr;
+  unsigned* rq = rowq_slot_for(n_dst, blocks, rq_ch, s, &ticket);
   const dim3 grid((unsigned)blocks), block(kMWaves * 64);
-#define GNNREC_SPM(R, W, P)                                                                     \
-  hipLaunchKernelGGL((spmm_project_mfma_kernel<R, W, kSpmU, P>), grid, block, 0, s,      \
-                     indptr, indices, ew, X, ldx, H, ldh, W_selfT, W_neighT, bias,              \
-                     bias_nonempty, n_dst, epilogue, accum, out_div, attn_vec, attn_state, out, \
-                     ldo, rq, rq_ch)
-  if (pre) {
-    if (ew) {
-      if (reduce == GNNREC_REDUCE_SUM) GNNREC_SPM(GNNREC_REDUCE_SUM, true, true);
-      else GNNREC_SPM(GNNREC_REDUCE_MEAN, true, true);
-    } else {
-      if (reduce == GNNREC_REDUCE_SUM) GNNREC_SPM(GNNREC_REDUCE_SUM, false, true);
-      else GNNREC_SPM(GNNREC_REDUCE_MEAN, false, true);
-    }
-  } else if (ew) {
-    if (reduce == GNNREC_REDUCE_SUM) GNNREC_SPM(GNNREC_REDUCE_SUM, true, false);
-    else if (reduce == GNNREC_REDUCE_MEAN) GNNREC_SPM(GNNREC_REDUCE_MEAN, true, false);
-    else GNNREC_SPM(GNNREC_REDUCE_MAX, true, false);
-  } else {
-    if (reduce == GNNREC_REDUCE_SUM) GNNREC_SPM(GNNREC_REDUCE_SUM, false, false);
-    else if (reduce == GNNREC_REDUCE_MEAN) GNNREC_SPM(GNNREC_REDUCE_MEAN, false, false);
-    else GNNREC_SPM(GNNREC_REDUCE_MAX, false, false);
-  }
-#undef GNNREC_SPM
+  dispatch_bool(pre, [&](auto p) {
+    dispatch_bool(ew != nullptr, [&](auto w) {
+      dispatch_reduce(reduce, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        constexpr bool P = decltype(p)::value;
+        if constexpr (!(P && R == GNNREC_REDUCE_MAX))  // refused above: not instantiated
+          hipLaunchKernelGGL((spmm_project_mfma_kernel<R, decltype(w)::value, kSpmU, P>), grid,
+                             block, 0, s, indptr, indices, ew, X, ldx, H, ldh, W_selfT, W_neighT,
+                             bias, bias_nonempty, n_dst, epilogue, accum, out_div, attn_vec,
+                             attn_state, out, ldo, rq, rq_ch);
+      });
+    });
+  });
   rowq_launched(ticket, s);
-  return check_launch("gnnrec_spmm_project_mfma_f32");
+  return check_launch(name);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -999,37 +790,8 @@ __global__ __launch_bounds__(kP2Waves * 64) void spmm_project2_pipe_kernel(
       float yb0 = zb[i][0] + gb[i][0], yb1 = zb[i][1] + gb[i][1];
       activate(relu, l2, ya0, ya1);
       activate(relu, l2, yb0, yb1);
-      float y0, y1;
-      if (combine == GNNREC_ACC_MAX) {
-        y0 = fmaxf(ya0, yb0);
-        y1 = fmaxf(ya1, yb1);
-      } else if (combine == GNNREC_ACC_ATTN_LAST) {
-        float sa = ya0 * at0 + ya1 * at1, sb = yb0 * at0 + yb1 * at1;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          sa += __shfl_xor(sa, off);
-          sb += __shfl_xor(sb, off);
-        }
-        const float mnew = fmaxf(sa, sb);
-        const float keep = expf(sa - mnew), cnew = expf(sb - mnew);
-        const float nrm = 1.f / (1.f * keep + cnew);
-        y0 = ya0 * keep + yb0 * cnew;
-        y1 = ya1 * keep + yb1 * cnew;
-        y0 *= nrm;
-        y1 *= nrm;
-      } else {
-        y0 = ya0 + yb0;
-        y1 = ya1 + yb1;
-      }
-      if (out_div > 0.f) {
-        y0 = y0 / out_div;
-        y1 = y1 / out_div;
-      }
-      if (i < nv) {
-        typedef float f32x2s __attribute__((ext_vector_type(2)));
-        __builtin_nontemporal_store(f32x2s{y0, y1},
-                                    reinterpret_cast<f32x2s*>(out + (row0 + i) * ldo + j0));
-      }
+      combine2_store(ya0, ya1, yb0, yb1, combine, at0, at1, out_div, i < nv,
+                     out + (row0 + i) * ldo + j0);
     }
     row0 = nrow0;
     lim = nlim;
@@ -1049,8 +811,7 @@ extern "C" int gnnrec_spmm_project2_f32(
     const float* W_self_bT, const float* bias_a, const float* bias_b, int64_t n_dst, int64_t d,
     int epilogue, int combine, const float* attn_vec, float out_div, float* out, int64_t ldo,
     void* stream) {
-  GNNREC_REQUIRE(d == kPD, "gnnrec_spmm_project2_f32: only d = %d (got %lld)", kPD,
-                 (long long)d);
+  const char* const name = "gnnrec_spmm_project2_f32";
   // GNNREC_SRC_STREAM on one relation: its source rows non-temporal (NT = 1: a, 2: b)
   int nt = ((reduce_a & GNNREC_SRC_STREAM) ? 1 : 0) | ((reduce_b & GNNREC_SRC_STREAM) ? 2 : 0);
   if (nt == 3) nt = 0;  // both: nothing to keep in the caches for
@@ -1059,57 +820,42 @@ extern "C" int gnnrec_spmm_project2_f32(
   GNNREC_REQUIRE((reduce_a == GNNREC_REDUCE_SUM || reduce_a == GNNREC_REDUCE_MEAN) &&
                      (reduce_b == GNNREC_REDUCE_SUM || reduce_b == GNNREC_REDUCE_MEAN),
                  "gnnrec_spmm_project2_f32: pre-projected relations reduce by sum or mean");
-  GNNREC_REQUIRE((epilogue & ~(GNNREC_EPI_RELU | GNNREC_EPI_L2NORM)) == 0,
-                 "gnnrec_spmm_project2_f32: epilogue must be RELU|L2NORM");
-  GNNREC_REQUIRE(combine == GNNREC_ACC_ADD || combine == GNNREC_ACC_MAX ||
-                     combine == GNNREC_ACC_ATTN_LAST,
-                 "gnnrec_spmm_project2_f32: combine must be GNNREC_ACC_ADD, _MAX or _ATTN_LAST");
-  GNNREC_REQUIRE((combine == GNNREC_ACC_ATTN_LAST) == (attn_vec != nullptr),
-                 "gnnrec_spmm_project2_f32: attn_vec goes with combine GNNREC_ACC_ATTN_LAST");
-  GNNREC_REQUIRE(n_dst >= 0, "gnnrec_spmm_project2_f32: negative n_dst");
-  if (n_dst == 0) return GNNREC_OK;
-  GNNREC_REQUIRE(indptr_a && Ya && indptr_b && Yb && H && W_self_aT && W_self_bT && out,
-                 "gnnrec_spmm_project2_f32: null pointer");
-  GNNREC_REQUIRE(aligned16(Ya) && aligned16(Yb) && aligned16(H) && aligned16(W_self_aT) &&
-                     aligned16(W_self_bT) && ldya % 4 == 0 && ldyb % 4 == 0 && ldh % 4 == 0 &&
-                     ldo % 2 == 0 && (reinterpret_cast<uintptr_t>(out) & 7u) == 0,
-                 "gnnrec_spmm_project2_f32: Y/H/W need 16-B aligned rows, out 8-B");
+  const int st = fused_check(name, d, epilogue, true, combine, attn_vec, nullptr, n_dst, 'Y',
+                             {indptr_a, Ya, indptr_b, Yb, H, W_self_aT, W_self_bT},
+                             {Ya, Yb, H, W_self_aT, W_self_bT}, {ldya, ldyb, ldh}, out, ldo);
+  if (st != GNNREC_OK || n_dst == 0) return st;
+  // one persistent block per CU
   const int64_t per_block = (int64_t)kP2Waves * kPRows;
-  int64_t blocks = (n_dst + per_block - 1) / per_block;
-  const int64_t cus = device_cus() - cu_reserve();
-  if (blocks > (cus > 8 ? cus : 8)) blocks = cus > 8 ? cus : 8;
+  const int64_t blocks = persistent_blocks((n_dst + per_block - 1) / per_block, 1);
   // rows per queue ticket: 16 (C5 user side, one session: 38.4–38.8 ms at 8, 37.4 at 16,
   // 37.5 at 32 — within the kernel's ±1 ms run-to-run spread)
   constexpr int rq_ch = 16;
   hipStream_t s = as_stream(stream);
   int ticket = -1;
-  unsigned* rq = n_dst >= blocks * kP2Waves * rq_ch * 4 ? rowq_slot(s, &ticket) : nullptr;
+  unsigned* rq = rowq_slot_for(n_dst, blocks * kP2Waves, rq_ch, s, &ticket);
   const dim3 grid((unsigned)blocks), block(kP2Waves * 64);
   const PreRel a{indptr_a, indices_a, ew_a, Ya, ldya, bias_nonempty_a,
                  reduce_a == GNNREC_REDUCE_MEAN};
   const PreRel b{indptr_b, indices_b, ew_b, Yb, ldyb, bias_nonempty_b,
                  reduce_b == GNNREC_REDUCE_MEAN};
-#define GNNREC_SPP2(WA_, WB_)                                                                \
-  hipLaunchKernelGGL((spmm_project2_pipe_kernel<WA_, WB_>), grid, block, 0, s, a, b, H, ldh,    \
-                     W_self_aT, W_self_bT, bias_a, bias_b, n_dst, epilogue, combine, attn_vec, \
-                     out_div, out, ldo, rq, rq_ch)
-  if (nt && !ew_a && !ew_b) {
-    if (nt == 1)
-      hipLaunchKernelGGL((spmm_project2_pipe_kernel<false, false, 1>), grid, block, 0, s, a, b,
-                         H, ldh, W_self_aT, W_self_bT, bias_a, bias_b, n_dst, epilogue, combine,
-                         attn_vec, out_div, out, ldo, rq, rq_ch);
-    else
-      hipLaunchKernelGGL((spmm_project2_pipe_kernel<false, false, 2>), grid, block, 0, s, a, b,
-                         H, ldh, W_self_aT, W_self_bT, bias_a, bias_b, n_dst, epilogue, combine,
-                         attn_vec, out_div, out, ldo, rq, rq_ch);
-  } else if (ew_a) {
-    if (ew_b) GNNREC_SPP2(true, true);
-    else GNNREC_SPP2(true, false);
-  } else {
-    if (ew_b) GNNREC_SPP2(false, true);
-    else GNNREC_SPP2(false, false);
-  }
-#undef GNNREC_SPP2
+  auto launch = [&](auto wa, auto wb, auto ntc) {
+    hipLaunchKernelGGL(
+        (spmm_project2_pipe_kernel<decltype(wa)::value, decltype(wb)::value, decltype(ntc)::value>),
+        grid, block, 0, s, a, b, H, ldh, W_self_aT, W_self_bT, bias_a, bias_b, n_dst, epilogue,
+        combine, attn_vec, out_div, out, ldo, rq, rq_ch);
+  };
+  dispatch_bool(ew_a != nullptr, [&](auto wa) {
+    dispatch_bool(ew_b != nullptr, [&](auto wb) {
+      using NT0 = std::integral_constant<int, 0>;
+      if constexpr (!decltype(wa)::value && !decltype(wb)::value) {  // the NT forms: unweighted
+        if (nt == 1) launch(wa, wb, std::integral_constant<int, 1>{});
+        else if (nt == 2) launch(wa, wb, std::integral_constant<int, 2>{});
+        else launch(wa, wb, NT0{});
+      } else {
+        launch(wa, wb, NT0{});
+      }
+    });
+  });
   rowq_launched(ticket, s);
-  return check_launch("gnnrec_spmm_project2_f32");
+  return check_launch(name);
 }
