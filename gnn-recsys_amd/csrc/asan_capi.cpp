@@ -150,6 +150,57 @@ static void validation() {
   CHECK(gnnrec_topk_candidates_f32(nullptr, nullptr, 64, 0, nullptr, nullptr, 16, nullptr, 16, 16,
                                    nullptr, nullptr, 10, nullptr, nullptr, nullptr) == GNNREC_OK,
         "candidates empty");
+  // the MLP head's dense scoring (heads.hip) and scored-candidate ranking
+  CHECK(gnnrec_edge_mlp_dense_store_f32(reinterpret_cast<float*>(20), 4, f16, 9, f16, f16, f16,
+                                        f16, f16, 9, nullptr) == GNNREC_EINVAL &&
+            err_has("aligned"),
+        "dense store unaligned P");
+  CHECK(gnnrec_edge_mlp_dense_store_f32(f16, 4, f16, 9, f16, f16, f16, f16, f16, 8, nullptr) ==
+            GNNREC_EINVAL && err_has("ldo"),
+        "dense store ldo");
+  CHECK(gnnrec_edge_mlp_dense_store_f32(f16, 4, f16, (int64_t)1 << 31, f16, f16, f16, f16, f16,
+                                        (int64_t)1 << 31, nullptr) == GNNREC_EINVAL &&
+            err_has("int32"),
+        "dense store item ids");
+  CHECK(gnnrec_edge_mlp_dense_store_f32(nullptr, 0, nullptr, 9, nullptr, nullptr, nullptr,
+                                        nullptr, nullptr, 9, nullptr) == GNNREC_OK,
+        "dense store empty");
+  CHECK(gnnrec_edge_mlp_dense_filter_f32(f16, 4, f16, 9, f16, f16, f16, f16, f16, i16, i16, f16,
+                                         4097, nullptr) == GNNREC_EINVAL && err_has("cap"),
+        "dense filter cap");
+  CHECK(gnnrec_edge_mlp_dense_filter_f32(f16, 4, f16, 9, f16, f16, f16, f16, f16, i16, i16, f16,
+                                         0, nullptr) == GNNREC_EINVAL,
+        "dense filter cap 0");
+  CHECK(gnnrec_edge_mlp_dense_filter_f32(f16, 4, f16, 9, f16, f16, f16, f16, nullptr, i16, i16,
+                                         f16, 64, nullptr) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "dense filter null tau");
+  CHECK(gnnrec_edge_mlp_dense_filter_f32(f16, 4, reinterpret_cast<float*>(8), 9, f16, f16, f16,
+                                         f16, f16, i16, i16, f16, 64, nullptr) == GNNREC_EINVAL &&
+            err_has("aligned"),
+        "dense filter unaligned Q");
+  CHECK(gnnrec_edge_mlp_dense_filter_f32(nullptr, 4, nullptr, 0, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr, nullptr, nullptr, 64,
+                                         nullptr) == GNNREC_OK,
+        "dense filter empty");
+  CHECK(gnnrec_topk_scored_candidates_f32(i16, i16, f16, 64, 3, nullptr, nullptr, nullptr, 65,
+                                          f16, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("k must be"),
+        "scored candidates k > cap");
+  CHECK(gnnrec_topk_scored_candidates_f32(i16, i16, f16, 8192, 3, nullptr, nullptr, nullptr, 10,
+                                          f16, l16, nullptr) == GNNREC_EINVAL,
+        "scored candidates cap");
+  CHECK(gnnrec_topk_scored_candidates_f32(i16, i16, f16, 64, 3, nullptr, l16, nullptr, 10, f16,
+                                          l16, nullptr) == GNNREC_EINVAL &&
+            err_has("indptr without indices"),
+        "scored candidates exclusion");
+  CHECK(gnnrec_topk_scored_candidates_f32(i16, i16, nullptr, 64, 3, nullptr, nullptr, nullptr, 10,
+                                          f16, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "scored candidates null scores");
+  CHECK(gnnrec_topk_scored_candidates_f32(nullptr, nullptr, nullptr, 64, 0, nullptr, nullptr,
+                                          nullptr, 10, nullptr, nullptr, nullptr) == GNNREC_OK,
+        "scored candidates empty");
   // edge removal (csr_filter.hip): every refusal comes before the first memset or launch;
   // an empty problem still writes the status and indptr', so its host side is the
   // workspace query, which must give room for them

@@ -383,6 +383,158 @@ int launch_edge_mlp_lds(bool grouped, EdgeMlpArgs& a, hipStream_t s) {
   return check_launch(grouped ? "gnnrec_edge_mlp_grouped_f32" : "gnnrec_edge_mlp_f32");
 }
 
+// ------------------------------------------------------- dense edge MLP ----
+// Every (user, item) pair of a user batch and an item range, without id arrays: the item of
+// a tile lane is the tile's base plus the lane.  A work item is (item tile, user group): the
+// wave stages the tile's 32 Q rows in its LDS image once (raw, no P added) and scores it for
+// the group's users (at most kDenseUsers) in turn with mlp_tile_score<true>, which forms
+// relu(P[u] + Q[v]) from the image and the user's 16 P chunks of this lane half.  The P rows
+// come from a table that lives in L2; they pass through a small LDS stage, kDenseStage users
+// at a time with the next stage's loads in flight, and a lane half reads a chunk as one
+// broadcast address (16 loads per user straight from the table found no registers left
+// beside W2 and the tile, and ran one at a time, each waiting out its L2 latency).  The
+// arithmetic per pair
+// is that of edge_mlp_lds_kernel — the same relu(p + q) per element, the same k order on the
+// MFMA, the same half-combine and sigmoid — so the scores are bitwise gnnrec_edge_mlp_f32's.
+// Q traffic: each Q row is read once per user group, n_users / kDenseUsers x |Q| in all
+// (16 x 512 MB for 1024 users x 1M items, against 1024 x for a per-user walk).
+// Two epilogues: STORE writes out[u, v]; FILTER appends (v, score) to row u's candidate
+// list where score >= tau[u] (no band: the score is the final fp32 value), counting past
+// cap.  Items past n_cols are staged as zero rows and masked at the store or the compare;
+// rows past n_users are never visited.
+constexpr int kDenseUsers = 64;  // users scored per staged item tile, at most
+constexpr int kDenseStage = 4;   // users whose P rows are staged in LDS at a time
+constexpr int kDenseCandMax = 4096;  // candidate slots per row, at most (recommend.hip's)
+
+struct DenseMlpArgs {
+  EdgeMlpArgs m;        // P, Q, W2, b2, w3, b3; the edge-list fields unused
+  int64_t n_users;
+  int64_t n_cols;       // items
+  int64_t groups;       // user groups per item tile
+  int64_t per_group;    // users per group: the batch split evenly, at most kDenseUsers
+  int64_t work;         // work items: item tiles x user groups
+  float* out;           // STORE
+  int64_t ldo;
+  const float* tau;     // FILTER
+  int* counts;
+  int* cand_items;
+  float* cand_scores;
+  int cap;
+};
+
+// The P rows of users [u0, u0 + kDenseStage) as the stage holds them (row-major, 32 chunks a
+// row: contiguous in the table), lane l the chunks l and 64 + l; zero past u1.
+__device__ __forceinline__ void dense_fetch_p(const float4* __restrict__ P4, int64_t u0,
+                                              int64_t u1, int lane, float4 (&pf)[2]) {
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    pf[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (u0 + 2 * k + (lane >> 5) < u1) pf[k] = P4[u0 * 32 + k * 64 + lane];
+  }
+}
+
+template <bool FILTER>
+__global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) {
+  __shared__ float4 image[kMlpWaves][kMlpTile * 32];     // 16 KB per wave
+  __shared__ float4 pstage[kMlpWaves][kDenseStage * 32];  // 2 KB per wave
+  static_assert(kDenseStage * 32 == 2 * kWave, "a stage is two chunks per lane");
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int r = lane & 31;
+  const int h = lane >> 5;
+  float4* S = image[wv];
+  float4* Ps = pstage[wv];
+  const float4* P4 = reinterpret_cast<const float4*>(a.m.P);
+  const float4* Q4 = reinterpret_cast<const float4*>(a.m.Q);
+  float4 w[16];
+  mlp_load_w2(a.m, r, h, w);
+  const float b3v = a.m.b3[0];
+  // user group fastest: the waves of a block (and neighbouring blocks) share a Q tile in L2
+  for (int64_t item = (int64_t)blockIdx.x * kMlpWaves + wv; item < a.work;
+       item += (int64_t)gridDim.x * kMlpWaves) {
+    const int64_t t = item / a.groups, g = item - t * a.groups;
+    const int64_t col = t * kMlpTile + r;  // this lane's item (both halves)
+    const int v = col < a.n_cols ? (int)col : -1;
+    // the previous work item's reads of the image are done before it is overwritten
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      float4 q[8], p[8];
+      mlp_load<true, 8>(Q4, P4, v, 0, r, h, 8 * half, q, p);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) S[(2 * (8 * half + i) + h) * 32 + r] = q[i];
+    }
+    // the staging stores are visible to the MFMA-layout reads (lane r reads row r)
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const int64_t u_beg = g * a.per_group;
+    const int64_t u1 = min<int64_t>(a.n_users, u_beg + a.per_group);
+    // kDenseStage users' P rows at a time (4 rows x 32 chunks = two per lane, row-major),
+    // the next stage's chunks in flight while this one is scored
+    float4 pf[2];
+    dense_fetch_p(P4, u_beg, u1, lane, pf);
+    for (int64_t u0 = u_beg; u0 < u1; u0 += kDenseStage) {  // wave-uniform
+      // the previous stage's reads are done before it is overwritten
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      Ps[lane] = pf[0];
+      Ps[64 + lane] = pf[1];
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      if (u0 + kDenseStage < u1) dense_fetch_p(P4, u0 + kDenseStage, u1, lane, pf);
+      const int nu = (int)min<int64_t>(kDenseStage, u1 - u0);
+      for (int j = 0; j < nu; ++j) {
+        const int64_t u = u0 + j;
+        float4 pc[16];  // both lane halves read one address each: LDS broadcasts
+#pragma unroll
+        for (int c = 0; c < 16; ++c) pc[c] = Ps[j * 32 + 16 * h + c];
+        float thr = 0.f;
+        if constexpr (FILTER) thr = a.tau[u];
+        const float sc = mlp_tile_score<true>(a.m, S, w, pc, r, h, b3v);
+        if (h == 0 && v >= 0) {
+          if constexpr (FILTER) {
+            if (sc >= thr) {
+              // the counter keeps counting past cap (the overflow signal); a store happens
+              // only inside the row's cap slots
+              const int slot = atomicAdd(a.counts + u, 1);
+              if (slot >= 0 && slot < a.cap) {
+                a.cand_items[u * a.cap + slot] = v;
+                a.cand_scores[u * a.cap + slot] = sc;
+              }
+            }
+          } else {
+            a.out[u * a.ldo + col] = sc;
+          }
+        }
+      }
+    }
+  }
+}
+
+int check_dense(const char* fn, const float* P, int64_t n_users, const float* Q, int64_t n_items,
+                const float* W2, const float* b2, const float* w3, const float* b3) {
+  GNNREC_REQUIRE(n_users >= 0 && n_items >= 0, "%s: negative size", fn);
+  GNNREC_REQUIRE(n_items < (int64_t(1) << 31), "%s: item ids must fit int32", fn);
+  if (n_users == 0 || n_items == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(P && Q && W2 && b2 && w3 && b3, "%s: null pointer", fn);
+  GNNREC_REQUIRE(aligned16(P) && aligned16(Q) && aligned16(W2),
+                 "%s: P/Q/W2 must be 16-byte aligned", fn);
+  return GNNREC_OK;
+}
+
+int launch_edge_mlp_dense(bool filter, DenseMlpArgs& a, hipStream_t s) {
+  // the users split evenly over the groups: 67 users (get_recs' batch against 1M items) are
+  // 34 + 33, not 64 + 3 with every tile staged a second time for three users
+  a.groups = (a.n_users + kDenseUsers - 1) / kDenseUsers;
+  a.per_group = (a.n_users + a.groups - 1) / a.groups;
+  a.work = ((a.n_cols + kMlpTile - 1) / kMlpTile) * a.groups;
+  int64_t blocks = (a.work + kMlpWaves - 1) / kMlpWaves;
+  if (blocks > kMlpResidentWaves / kMlpWaves) blocks = kMlpResidentWaves / kMlpWaves;
+  if (filter)
+    hipLaunchKernelGGL(edge_mlp_dense_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(edge_mlp_dense_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+  return check_launch(filter ? "gnnrec_edge_mlp_dense_filter_f32"
+                             : "gnnrec_edge_mlp_dense_store_f32");
+}
+
 }  // namespace
 }  // namespace gnnrec
 
@@ -471,4 +623,41 @@ extern "C" int gnnrec_edge_mlp_grouped_f32(const int64_t* src_g, int64_t n_group
   EdgeMlpArgs a{src_g, dst, first, out_first, out, P, Q, W2, b2, w3, b3, 0, K, per_group, chunks,
                 n_groups * chunks, ct};
   return launch_edge_mlp_lds(true, a, as_stream(stream));
+}
+
+extern "C" int gnnrec_edge_mlp_dense_store_f32(const float* P, int64_t n_users, const float* Q,
+                                               int64_t n_items, const float* W2, const float* b2,
+                                               const float* w3, const float* b3, float* out,
+                                               int64_t ldo, void* stream) {
+  using namespace gnnrec;
+  const char* fn = "gnnrec_edge_mlp_dense_store_f32";
+  const int rc = check_dense(fn, P, n_users, Q, n_items, W2, b2, w3, b3);
+  if (rc != GNNREC_OK || n_users == 0 || n_items == 0) return rc;
+  GNNREC_REQUIRE(out && ldo >= n_items, "%s: bad out / ldo", fn);
+  DenseMlpArgs a{};
+  a.m.P = P; a.m.Q = Q; a.m.W2 = W2; a.m.b2 = b2; a.m.w3 = w3; a.m.b3 = b3;
+  a.n_users = n_users; a.n_cols = n_items;
+  a.out = out; a.ldo = ldo;
+  return launch_edge_mlp_dense(false, a, as_stream(stream));
+}
+
+extern "C" int gnnrec_edge_mlp_dense_filter_f32(const float* P, int64_t n_users, const float* Q,
+                                                int64_t n_items, const float* W2, const float* b2,
+                                                const float* w3, const float* b3, const float* tau,
+                                                int32_t* counts, int32_t* cand_items,
+                                                float* cand_scores, int64_t cap, void* stream) {
+  using namespace gnnrec;
+  const char* fn = "gnnrec_edge_mlp_dense_filter_f32";
+  const int rc = check_dense(fn, P, n_users, Q, n_items, W2, b2, w3, b3);
+  if (rc != GNNREC_OK) return rc;
+  GNNREC_REQUIRE(cap >= 1 && cap <= kDenseCandMax, "%s: cap must be in [1, %d] (got %lld)", fn,
+                 kDenseCandMax, (long long)cap);
+  if (n_users == 0 || n_items == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(tau && counts && cand_items && cand_scores, "%s: null pointer", fn);
+  DenseMlpArgs a{};
+  a.m.P = P; a.m.Q = Q; a.m.W2 = W2; a.m.b2 = b2; a.m.w3 = w3; a.m.b3 = b3;
+  a.n_users = n_users; a.n_cols = n_items;
+  a.tau = tau; a.counts = counts; a.cand_items = cand_items; a.cand_scores = cand_scores;
+  a.cap = (int)cap;
+  return launch_edge_mlp_dense(true, a, as_stream(stream));
 }

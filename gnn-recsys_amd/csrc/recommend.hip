@@ -17,6 +17,9 @@
 //                         the sample gives tau (the k-th best non-excluded score there)
 //   topk_candidates       drop a row's excluded candidates, rescore the rest with the fp32
 //                         cosine (cos_score.hpp: the bits of gnnrec_sddmm_cos_f32), rank
+//   topk_scored_candidates  the same strike and ranking of (item, score) pairs that need no
+//                         rescoring: the MLP head's, whose filter (heads.hip) compares and
+//                         keeps the final fp32 score
 //
 // THE BOUND.  bf16 has unit roundoff 2^-8: |bf16(û) - û| <= 2^-8 |û| as vectors, and the same
 // for v̂.  With |û| = |v̂| = 1 (up to fp32 rounding) Cauchy-Schwarz gives
@@ -365,11 +368,66 @@ __device__ __forceinline__ bool better(float a, int ia, float b, int ib) {
   return a > b || (a == b && ia < ib);
 }
 
-// One block per batch row: its min(count, cap) candidates into LDS, the excluded ones struck
-// (the exclusion list staged kExChunk ids at a time; rows are unsorted and candidates few, so
-// a scan), the rest scored by lane groups exactly as sddmm_cos_kernel<LPR, 4> scores an edge,
-// then each candidate's rank is the number of better candidates (ids are distinct, so the
-// order (score desc, id asc) is total and the ranks 0 .. n-1 are each taken once).
+// The two steps every candidate ranking shares, on a block's LDS lists (ids[n], sc[n]):
+//
+// strike_excluded: the ids found in user row urow's exclusion list become -1 (the list
+// staged kExChunk ids at a time into ex; rows are unsorted and candidates few, so a scan).
+// The caller's writes of ids are synchronised before the call; the strikes are after it.
+__device__ __forceinline__ void strike_excluded(int* ids, int n, int* ex,
+                                                const int64_t* __restrict__ ex_ptr,
+                                                const int32_t* __restrict__ ex_idx, int64_t urow,
+                                                int tid) {
+  if (!ex_ptr) return;
+  const int64_t e0 = ex_ptr[urow], ne = ex_ptr[urow + 1] - e0;
+  for (int64_t base = 0; base < ne; base += kExChunk) {
+    const int m = (int)min<int64_t>(kExChunk, ne - base);
+    for (int j = tid; j < m; j += 256) ex[j] = ex_idx[e0 + base + j];
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {
+      const int c = ids[i];
+      if (c < 0) continue;
+      for (int j = 0; j < m; ++j)
+        if (ex[j] == c) { ids[i] = -1; break; }
+    }
+    __syncthreads();
+  }
+}
+
+// rank_and_emit: each surviving candidate's rank is the number of better candidates (ids
+// are distinct, so the order (score desc, id asc) is total and the ranks 0 .. n-1 are each
+// taken once); ranks below k go to row b of out_v / out_i, the rest of the row is padded
+// with (-inf, -1).  *n_valid is zero and ids / sc synchronised on entry.
+__device__ __forceinline__ void rank_and_emit(const int* ids, const float* sc, int n, int k,
+                                              int64_t b, float* __restrict__ out_v,
+                                              int64_t* __restrict__ out_i, int* n_valid,
+                                              int tid) {
+  int mine = 0;
+  for (int i = tid; i < n; i += 256) {
+    const int c = ids[i];
+    if (c < 0) continue;
+    ++mine;
+    const float v = sc[i];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) {
+      const int cj = ids[j];
+      rank += (cj >= 0 && better(sc[j], cj, v, c)) ? 1 : 0;
+    }
+    if (rank < k) {
+      out_v[b * k + rank] = v;
+      out_i[b * k + rank] = c;
+    }
+  }
+  if (mine) atomicAdd(n_valid, mine);
+  __syncthreads();
+  for (int r = *n_valid + tid; r < k; r += 256) {
+    out_v[b * k + r] = -INFINITY;
+    out_i[b * k + r] = -1;
+  }
+}
+
+// One block per batch row: its min(count, cap) candidates into LDS, the excluded ones
+// struck, the rest scored by lane groups exactly as sddmm_cos_kernel<LPR, 4> scores an edge,
+// then ranked.
 template <int LPR>
 __global__ __launch_bounds__(256) void topk_candidates_kernel(
     const int* __restrict__ counts, const int* __restrict__ cand, int cap,
@@ -390,21 +448,7 @@ __global__ __launch_bounds__(256) void topk_candidates_kernel(
   for (int i = tid; i < n; i += 256) ids[i] = cand[b * cap + i];
   if (tid == 0) n_valid = 0;
   __syncthreads();
-  if (ex_ptr) {
-    const int64_t e0 = ex_ptr[urow], ne = ex_ptr[urow + 1] - e0;
-    for (int64_t base = 0; base < ne; base += kExChunk) {
-      const int m = (int)min<int64_t>(kExChunk, ne - base);
-      for (int j = tid; j < m; j += 256) ex[j] = ex_idx[e0 + base + j];
-      __syncthreads();
-      for (int i = tid; i < n; i += 256) {
-        const int c = ids[i];
-        if (c < 0) continue;
-        for (int j = 0; j < m; ++j)
-          if (ex[j] == c) { ids[i] = -1; break; }
-      }
-      __syncthreads();
-    }
-  }
+  strike_excluded(ids, n, ex, ex_ptr, ex_idx, urow, tid);
   constexpr int NPW = kWave / LPR;
   const int lane = tid & 63, wave = tid >> 6;
   const int grp = lane / LPR, gl = lane % LPR;
@@ -417,28 +461,34 @@ __global__ __launch_bounds__(256) void topk_candidates_kernel(
     if (gl == LPR - 1 && i < n) sc[i] = ok ? r : -INFINITY;
   }
   __syncthreads();
-  int mine = 0;
+  rank_and_emit(ids, sc, n, k, b, out_v, out_i, &n_valid, tid);
+}
+
+// The same ranking of candidates that come with their scores (the dense MLP filter's
+// (item, score) pairs, heads.hip): nothing is rescored.
+__global__ __launch_bounds__(256) void topk_scored_candidates_kernel(
+    const int* __restrict__ counts, const int* __restrict__ cand,
+    const float* __restrict__ cand_sc, int cap, const int64_t* __restrict__ user_rows,
+    const int64_t* __restrict__ ex_ptr, const int32_t* __restrict__ ex_idx, int k,
+    float* __restrict__ out_v, int64_t* __restrict__ out_i) {
+  __shared__ int ids[kCandMax];
+  __shared__ float sc[kCandMax];
+  __shared__ int ex[kExChunk];
+  __shared__ int n_valid;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int cnt = counts[b];
+  if (cnt > cap || cnt < 0) return;  // overflowed: nothing is emitted, the caller recomputes
+  const int n = cnt;
+  const int64_t urow = user_rows ? user_rows[b] : b;
   for (int i = tid; i < n; i += 256) {
-    const int c = ids[i];
-    if (c < 0) continue;
-    ++mine;
-    const float v = sc[i];
-    int rank = 0;
-    for (int j = 0; j < n; ++j) {
-      const int cj = ids[j];
-      rank += (cj >= 0 && better(sc[j], cj, v, c)) ? 1 : 0;
-    }
-    if (rank < k) {
-      out_v[b * k + rank] = v;
-      out_i[b * k + rank] = c;
-    }
+    ids[i] = cand[b * cap + i];
+    sc[i] = cand_sc[b * cap + i];
   }
-  if (mine) atomicAdd(&n_valid, mine);
+  if (tid == 0) n_valid = 0;
   __syncthreads();
-  for (int r = n_valid + tid; r < k; r += 256) {
-    out_v[b * k + r] = -INFINITY;
-    out_i[b * k + r] = -1;
-  }
+  strike_excluded(ids, n, ex, ex_ptr, ex_idx, urow, tid);
+  rank_and_emit(ids, sc, n, k, b, out_v, out_i, &n_valid, tid);
 }
 
 int check_score_args(const char* fn, const void* U, int64_t B, const void* V, int64_t n,
@@ -557,4 +607,28 @@ extern "C" int gnnrec_topk_candidates_f32(const int32_t* counts, const int32_t* 
   else GNNREC_LAUNCH_CAND(64);
 #undef GNNREC_LAUNCH_CAND
   return check_launch("gnnrec_topk_candidates_f32");
+}
+
+extern "C" int gnnrec_topk_scored_candidates_f32(const int32_t* counts, const int32_t* cand_items,
+                                                 const float* cand_scores, int64_t cap,
+                                                 int64_t n_rows, const int64_t* user_rows,
+                                                 const int64_t* exclude_indptr,
+                                                 const int32_t* exclude_indices, int64_t k,
+                                                 float* out_vals, int64_t* out_idx, void* stream) {
+  using namespace gnnrec;
+  GNNREC_REQUIRE(n_rows >= 0 && n_rows < (int64_t(1) << 31),
+                 "gnnrec_topk_scored_candidates_f32: bad row count");
+  GNNREC_REQUIRE(cap >= 1 && cap <= kCandMax, "gnnrec_topk_scored_candidates_f32: cap must be in "
+                 "[1, %d] (got %lld)", kCandMax, (long long)cap);
+  GNNREC_REQUIRE(k >= 1 && k <= cap, "gnnrec_topk_scored_candidates_f32: k must be in [1, cap] "
+                 "(got %lld)", (long long)k);
+  if (n_rows == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(counts && cand_items && cand_scores && out_vals && out_idx,
+                 "gnnrec_topk_scored_candidates_f32: null pointer");
+  GNNREC_REQUIRE(!exclude_indptr || exclude_indices,
+                 "gnnrec_topk_scored_candidates_f32: exclusion indptr without indices");
+  hipLaunchKernelGGL(topk_scored_candidates_kernel, dim3((unsigned)n_rows), dim3(256), 0,
+                     as_stream(stream), counts, cand_items, cand_scores, (int)cap, user_rows,
+                     exclude_indptr, exclude_indices, (int)k, out_vals, out_idx);
+  return check_launch("gnnrec_topk_scored_candidates_f32");
 }

@@ -14,6 +14,8 @@
 //   sddmm_cos                       <- CosinePrediction.forward src/model.py:317-327
 //   edge_mlp                        <- PredictingModule.forward src/model.py:290-305
 //   edge_mlp_grouped                <- the same over negative_sampler.Uniform's pair graphs
+//   edge_mlp_dense_store / _filter  <- the same for every (user, item) pair: get_recs(pred='nn')
+//                                      src/metrics.py:31-78 and recs.recommend(head=...)
 // The sampler and loader ops (sample_*, scan, relabel, gathers) are in torch_sampler.cpp.
 #include <algorithm>
 #include <utility>
@@ -602,6 +604,65 @@ void edge_mlp_grouped(const Tensor& src_g, const optional<Tensor>& first, int64_
      "gnnrec_edge_mlp_grouped_f32");
 }
 
+// the operands of a dense MLP scoring launch: P [B, 128], Q [n, 128], W2 [32, 128] contiguous
+void dense_mlp_tables(const Tensor& P, const Tensor& Q, const Tensor& W2, const Tensor& b2,
+                      const Tensor& w3, const Tensor& b3) {
+  for (auto* t : {&P, &Q, &W2, &b2, &w3, &b3}) dev(*t, "edge_mlp operand", at::kFloat);
+  TORCH_CHECK_VALUE(P.dim() == 2 && Q.dim() == 2 && W2.dim() == 2 && P.size(1) == 128 &&
+                        Q.size(1) == 128 && W2.size(0) == 32 && W2.size(1) == 128 &&
+                        b2.numel() == 32 && w3.numel() == 32 && b3.numel() == 1,
+                    "edge_mlp expects the reference's 128/32 hidden sizes");
+  TORCH_CHECK_VALUE(P.is_contiguous() && Q.is_contiguous() && W2.is_contiguous() &&
+                        b2.is_contiguous() && w3.is_contiguous(),
+                    "edge_mlp operands must be contiguous");
+}
+
+void edge_mlp_dense_store(const Tensor& P, const Tensor& Q, const Tensor& W2, const Tensor& b2,
+                          const Tensor& w3, const Tensor& b3, Tensor& out) {
+  const OneDevice one_device_;
+  dense_mlp_tables(P, Q, W2, b2, w3, b3);
+  dev(out, "out", at::kFloat);
+  const int64_t B = P.size(0), n = Q.size(0);
+  const int64_t ldo = ld(out, "out");
+  TORCH_CHECK_VALUE(out.size(0) == B && out.size(1) == n, "out must be [", B, ", ", n, "], got ",
+                    out.sizes());
+  if (meta(P)) return;
+  const c10::DeviceGuard g(P.device());
+  ck(gnnrec_edge_mlp_dense_store_f32(p<float>(P), B, p<float>(Q), n, p<float>(W2), p<float>(b2),
+                                     p<float>(w3), p<float>(b3), p<float>(out), ldo,
+                                     stream_of(P)),
+     "gnnrec_edge_mlp_dense_store_f32");
+}
+
+void edge_mlp_dense_filter(const Tensor& P, const Tensor& Q, const Tensor& W2, const Tensor& b2,
+                           const Tensor& w3, const Tensor& b3, const Tensor& tau, Tensor& counts,
+                           Tensor& cand_items, Tensor& cand_scores) {
+  const OneDevice one_device_;
+  dense_mlp_tables(P, Q, W2, b2, w3, b3);
+  dev(tau, "tau", at::kFloat);
+  dev(counts, "counts", at::kInt);
+  dev(cand_items, "cand_items", at::kInt);
+  dev(cand_scores, "cand_scores", at::kFloat);
+  const int64_t B = P.size(0), n = Q.size(0);
+  TORCH_CHECK_VALUE(tau.numel() == B && counts.numel() == B && tau.is_contiguous() &&
+                        counts.is_contiguous(),
+                    "tau / counts must be contiguous [", B, "]");
+  TORCH_CHECK_VALUE(cand_items.dim() == 2 && cand_items.size(0) == B && cand_items.is_contiguous(),
+                    "cand_items must be a contiguous [", B, ", cap], got ", cand_items.sizes());
+  const int64_t cap = cand_items.size(1);
+  TORCH_CHECK_VALUE(cap >= 1 && cap <= 4096, "cand_items: cap must be in [1, 4096], got ", cap);
+  TORCH_CHECK_VALUE(cand_scores.sizes() == cand_items.sizes() && cand_scores.is_contiguous(),
+                    "cand_scores must be a contiguous [", B, ", ", cap, "], got ",
+                    cand_scores.sizes());
+  if (meta(P)) return;
+  const c10::DeviceGuard g(P.device());
+  ck(gnnrec_edge_mlp_dense_filter_f32(p<float>(P), B, p<float>(Q), n, p<float>(W2), p<float>(b2),
+                                      p<float>(w3), p<float>(b3), p<float>(tau),
+                                      p<int32_t>(counts), p<int32_t>(cand_items),
+                                      p<float>(cand_scores), cap, stream_of(P)),
+     "gnnrec_edge_mlp_dense_filter_f32");
+}
+
 // ---------------------------------------------------------------- f1 top-k
 void topk_rows(const Tensor& scores, int64_t k, const optional<Tensor>& exclude_indptr,
                const optional<Tensor>& exclude_indices, Tensor& out_vals, Tensor& out_idx) {
@@ -763,6 +824,51 @@ void topk_candidates_f32(const Tensor& counts, const Tensor& cand_items,
                                 d, p<int64_t>(exclude_indptr), p<int32_t>(exclude_indices), k,
                                 p<float>(out_vals), p<int64_t>(out_idx), stream_of(counts)),
      "gnnrec_topk_candidates_f32");
+}
+
+void topk_scored_candidates_f32(const Tensor& counts, const Tensor& cand_items,
+                                const Tensor& cand_scores, const optional<Tensor>& user_rows,
+                                const optional<Tensor>& exclude_indptr,
+                                const optional<Tensor>& exclude_indices, int64_t k,
+                                Tensor& out_vals, Tensor& out_idx) {
+  const OneDevice one_device_;
+  dev(counts, "counts", at::kInt);
+  dev(cand_items, "cand_items", at::kInt);
+  dev(cand_scores, "cand_scores", at::kFloat);
+  dev(user_rows, "user_rows", at::kLong);
+  dev(exclude_indptr, "exclude_indptr", at::kLong);
+  dev(exclude_indices, "exclude_indices", at::kInt);
+  dev(out_vals, "out_vals", at::kFloat);
+  dev(out_idx, "out_idx", at::kLong);
+  const int64_t B = counts.numel();
+  TORCH_CHECK_VALUE(cand_items.dim() == 2 && cand_items.size(0) == B && cand_items.is_contiguous() &&
+                        counts.is_contiguous(),
+                    "cand_items must be a contiguous [", B, ", cap], got ", cand_items.sizes());
+  const int64_t cap = cand_items.size(1);
+  TORCH_CHECK_VALUE(cap >= 1 && cap <= 4096, "cand_items: cap must be in [1, 4096], got ", cap);
+  TORCH_CHECK_VALUE(cand_scores.sizes() == cand_items.sizes() && cand_scores.is_contiguous(),
+                    "cand_scores must be a contiguous [", B, ", ", cap, "], got ",
+                    cand_scores.sizes());
+  TORCH_CHECK_VALUE(k >= 1 && k <= cap, "k must be in [1, cap = ", cap, "], got ", k);
+  TORCH_CHECK_VALUE(!has(user_rows) || (user_rows->numel() == B && user_rows->is_contiguous()),
+                    "user_rows must be contiguous [", B, "]");
+  TORCH_CHECK_VALUE(has(exclude_indptr) == has(exclude_indices),
+                    "exclude_indptr and exclude_indices come together");
+  TORCH_CHECK_VALUE(!has(exclude_indptr) ||
+                        (exclude_indptr->is_contiguous() && exclude_indices->is_contiguous() &&
+                         exclude_indptr->numel() >= 1 &&
+                         (has(user_rows) || exclude_indptr->numel() > B)),
+                    "exclude_indptr must be a contiguous indptr over the user rows");
+  TORCH_CHECK_VALUE(out_vals.numel() == B * k && out_idx.numel() == B * k &&
+                        out_vals.is_contiguous() && out_idx.is_contiguous(),
+                    "out_vals / out_idx must be contiguous [", B, ", ", k, "]");
+  if (meta(counts)) return;
+  const c10::DeviceGuard g(counts.device());
+  ck(gnnrec_topk_scored_candidates_f32(p<int32_t>(counts), p<int32_t>(cand_items),
+                                       p<float>(cand_scores), cap, B, p<int64_t>(user_rows),
+                                       p<int64_t>(exclude_indptr), p<int32_t>(exclude_indices), k,
+                                       p<float>(out_vals), p<int64_t>(out_idx), stream_of(counts)),
+     "gnnrec_topk_scored_candidates_f32");
 }
 
 // ---------------------------------------------------------------- f2 training
@@ -1775,6 +1881,13 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor b3, Tensor(a!) out) -> ()");
   m.def("edge_mlp_grouped(Tensor src_g, Tensor? first, int K, Tensor dst, Tensor P, Tensor Q, "
         "Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor(a!) out_first, Tensor(b!) out) -> ()");
+  m.def("edge_mlp_dense_store_f32(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, Tensor b3, "
+        "Tensor(a!) out) -> ()");
+  m.def("edge_mlp_dense_filter_f32(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, Tensor b3, "
+        "Tensor tau, Tensor(a!) counts, Tensor(b!) cand_items, Tensor(c!) cand_scores) -> ()");
+  m.def("topk_scored_candidates_f32(Tensor counts, Tensor cand_items, Tensor cand_scores, "
+        "Tensor? user_rows, Tensor? exclude_indptr, Tensor? exclude_indices, int k, "
+        "Tensor(a!) out_vals, Tensor(b!) out_idx) -> ()");
   m.def("topk_rows(Tensor scores, int k, Tensor? exclude_indptr, Tensor? exclude_indices, "
         "Tensor(a!) out_vals, Tensor(b!) out_idx) -> ()");
   m.def("normalize_rows_bf16(Tensor x, Tensor? row_map, Tensor(a!) out) -> ()");
@@ -1890,6 +2003,9 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("sddmm_cos_backward", &sddmm_cos_backward);     \
   m.impl("edge_mlp", &edge_mlp);                         \
   m.impl("edge_mlp_grouped", &edge_mlp_grouped);         \
+  m.impl("edge_mlp_dense_store_f32", &edge_mlp_dense_store); \
+  m.impl("edge_mlp_dense_filter_f32", &edge_mlp_dense_filter); \
+  m.impl("topk_scored_candidates_f32", &topk_scored_candidates_f32); \
   m.impl("topk_rows", &topk_rows);                       \
   m.impl("normalize_rows_bf16", &normalize_rows_bf16);   \
   m.impl("score_bf16_store", &score_bf16_store);         \

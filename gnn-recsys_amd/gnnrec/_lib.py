@@ -94,6 +94,10 @@ SIGNATURES = {
     "gnnrec_edge_mlp_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gnnrec_edge_mlp_grouped_f32": (_INT, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P,
                                             _P, _P]),
+    # dense MLP scoring of a user batch against an item range (csrc/heads.hip)
+    "gnnrec_edge_mlp_dense_store_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _P]),
+    "gnnrec_edge_mlp_dense_filter_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P,
+                                                _P, _I64, _P]),
     "gnnrec_sample_count": (_INT, [_P, _P, _P, _P, _P, _I64, _I64, _U64, _P, _P]),
     "gnnrec_sample_fill": (_INT, [_P, _P, _P, _P, _P, _P, _I64, _I64, _U64, _P, _P, _P, _P]),
     "gnnrec_scan_workspace_bytes": (_I64, [_I64]),
@@ -159,6 +163,8 @@ SIGNATURES = {
     "gnnrec_mask_excluded_f32": (_INT, [_P, _I64, _I64, _I64, _P, _P, _P, _P]),
     "gnnrec_topk_candidates_f32": (_INT, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _I64, _I64, _P,
                                           _P, _I64, _P, _P, _P]),
+    "gnnrec_topk_scored_candidates_f32": (_INT, [_P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _P,
+                                                 _P, _P]),
     "gnnrec_synth_edges": (_INT, [_U64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     "gnnrec_margin_loss_blocks": (_I64, [_I64]),
     "gnnrec_margin_loss_f32": (_INT, [_P, _P, _I64, _I64, _F32, _P, _P, _INT, _P, _P, _P, _I64,

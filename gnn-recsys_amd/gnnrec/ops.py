@@ -1831,3 +1831,68 @@ def topk_candidates(counts: torch.Tensor, cand_items: torch.Tensor,
     _T().topk_candidates_f32(counts, cand_items, user_rows, h_user, h_item, exclude_indptr,
                              exclude_indices, int(k), out_vals, out_idx)
     return out_vals, out_idx
+
+
+# ---- f1c: many-user top-k for the MLP head (csrc/heads.hip, csrc/recommend.hip) ----
+def _dense_mlp_operands(P, Q, W2, b2, w3, b3):
+    for t, n in ((P, "P"), (Q, "Q"), (W2, "W2"), (b2, "b2"), (w3, "w3"), (b3, "b3")):
+        _dev(t, n, torch.float32)
+    if P.dim() != 2 or Q.dim() != 2 or P.shape[1] != 128 or Q.shape[1] != 128 or \
+            tuple(W2.shape) != (32, 128) or b2.numel() != 32 or w3.numel() != 32 or \
+            b3.numel() != 1:
+        raise ValueError("edge_mlp expects the reference's 128/32 hidden sizes")
+    return (P.contiguous(), Q.contiguous(), W2.detach().contiguous(), b2.detach().contiguous(),
+            w3.detach().reshape(-1).contiguous(), b3.detach().contiguous())
+
+
+def edge_mlp_dense_store(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor,
+                         w3: torch.Tensor, b3: torch.Tensor,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The MLP head's score of every user row of P [B, 128] against every item row of
+    Q [n, 128] -> fp32 [B, n]; each value is bitwise edge_mlp's for the pair.  No id arrays:
+    a 32-item tile of Q is staged once and scored for 64 users in turn."""
+    ops = _dense_mlp_operands(P, Q, W2, b2, w3, b3)
+    if out is None:
+        out = torch.empty((P.shape[0], Q.shape[0]), dtype=torch.float32, device=P.device)
+    _T().edge_mlp_dense_store_f32(*ops, out)
+    return out
+
+
+def edge_mlp_dense_filter(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor,
+                          w3: torch.Tensor, b3: torch.Tensor, tau: torch.Tensor,
+                          counts: torch.Tensor, cand_items: torch.Tensor,
+                          cand_scores: torch.Tensor) -> None:
+    """The same scores, none written to a matrix: where score(u, v) >= tau[u] (compared as
+    is) item v and its score join row u's lists cand_items (int32) / cand_scores (fp32)
+    [B, cap]; counts [B] (int32, zeroed by the caller) counts every passing item, past cap
+    too (counts[u] > cap: the row overflowed)."""
+    ops = _dense_mlp_operands(P, Q, W2, b2, w3, b3)
+    _dev(tau, "tau", torch.float32)
+    _dev(counts, "counts", torch.int32)
+    _dev(cand_items, "cand_items", torch.int32)
+    _dev(cand_scores, "cand_scores", torch.float32)
+    _T().edge_mlp_dense_filter_f32(*ops, tau, counts, cand_items, cand_scores)
+
+
+def topk_scored_candidates(counts: torch.Tensor, cand_items: torch.Tensor,
+                           cand_scores: torch.Tensor, k: int,
+                           user_rows: Optional[torch.Tensor] = None,
+                           exclude_indptr: Optional[torch.Tensor] = None,
+                           exclude_indices: Optional[torch.Tensor] = None,
+                           out_vals: Optional[torch.Tensor] = None,
+                           out_idx: Optional[torch.Tensor] = None):
+    """Per batch row: its first min(count, cap) (item, score) pairs minus the user's excluded
+    items (a CSR over the user rows, int32 ids), ranked by (score desc, item asc) ->
+    (vals [B, k], idx [B, k]), padded with (-inf, -1).  Rows with counts > cap are left
+    unwritten."""
+    _dev(counts, "counts", torch.int32)
+    _dev(cand_items, "cand_items", torch.int32)
+    _dev(cand_scores, "cand_scores", torch.float32)
+    B = counts.numel()
+    if out_vals is None:
+        out_vals = torch.empty((B, k), dtype=torch.float32, device=counts.device)
+    if out_idx is None:
+        out_idx = torch.empty((B, k), dtype=torch.int64, device=counts.device)
+    _T().topk_scored_candidates_f32(counts, cand_items, cand_scores, user_rows, exclude_indptr,
+                                    exclude_indices, int(k), out_vals, out_idx)
+    return out_vals, out_idx

@@ -7,14 +7,16 @@ The reference loops over users in Python: repeat the user embedding once per
 item, cosine (or the MLP head) against every item, copy to the host, argsort,
 filter already-bought items, keep k.  Here a batch of users is scored against
 every item in one fp32 MFMA GEMM of L2-normalised embeddings (gnnrec_gemm_f32),
-or by the re-associated MLP head (gnnrec_edge_mlp_f32), and
+or by the re-associated MLP head (gnnrec_edge_mlp_dense_store_f32: every pair
+without id arrays, the bits of gnnrec_edge_mlp_f32), and
 gnnrec_topk_rows_f32 selects the k best non-bought items per user on the
 device.  Only the [users, k] result leaves the GPU.
 
 `recommend` / `recommend_for_graph` / `recs_to_metrics_device` serve many users (the
 reference's `--user_ids all`) on device tensors: the same ranking for the cosine head, bit
 for bit, from a bf16 MFMA prefilter and an fp32 rescoring of the few items it cannot rule
-out, with no score matrix.
+out, with no score matrix.  With `head=` (a PredictingLayer) they rank by
+the MLP head's score instead, exactly and again without a score matrix.
 """
 from __future__ import annotations
 
@@ -86,12 +88,9 @@ def get_recs(g, h, model, embed_dim, k, user_ids, already_bought_dict,
             scores = ops.gemm(_normalize_rows(users), items_hat)   # [B, n_items] cosine
         else:
             P = ops.gemm(users, W1[:, :embed_dim], bias=layer.hidden_1.bias)
-            B = len(ub)
-            src = torch.arange(B, device=dev).repeat_interleave(n_items)
-            dst = torch.arange(n_items, device=dev).repeat(B)
-            scores = ops.edge_mlp(src, dst, P, Q, layer.hidden_2.weight, layer.hidden_2.bias,
-                                  layer.output.weight.reshape(-1),
-                                  layer.output.bias).view(B, n_items)
+            # every pair without id arrays; the values are bitwise ops.edge_mlp's
+            scores = ops.edge_mlp_dense_store(P, Q, layer.hidden_2.weight, layer.hidden_2.bias,
+                                              layer.output.weight.reshape(-1), layer.output.bias)
         if pop is not None:  # softmax over items, plus weighted popularity (metrics.py:69-72)
             scores = torch.softmax(scores, dim=1) + pop
         ex_ptr = ex_idx = None
@@ -151,8 +150,61 @@ def _rows_exact(h_user, h_item, k, rows, exclude, vals, idx, out_pos):
         idx[pos] = i
 
 
+class _MlpHead:
+    """A PredictingLayer re-associated for scoring a user batch against every item:
+    Q = h_item W1b^T once, P = h_user[rows] W1a^T + b1 per batch, the rest of the head in
+    ops.edge_mlp_dense_store / _filter (each score bitwise ops.edge_mlp's for the pair)."""
+
+    def __init__(self, head, h_user, h_item):
+        d = h_item.shape[1]
+        W1 = head.hidden_1.weight
+        if tuple(W1.shape) != (128, 2 * d):
+            raise ValueError(f'head.hidden_1 must be [128, {2 * d}] for d = {d}, got '
+                             f'{tuple(W1.shape)}')
+        for t in (W1, head.hidden_2.weight, head.output.weight):
+            ops._dev(t, 'head weights', torch.float32)
+        self.h_user, self.W1a, self.b1 = h_user, W1[:, :d], head.hidden_1.bias
+        self.tail = (head.hidden_2.weight.detach().contiguous(),
+                     head.hidden_2.bias.detach().contiguous(),
+                     head.output.weight.detach().reshape(-1).contiguous(),
+                     head.output.bias.detach().contiguous())
+        self.Q = ops.gemm(h_item, W1[:, d:]) if h_item.shape[0] else \
+            torch.empty((0, 128), dtype=torch.float32, device=h_item.device)
+
+    def P(self, rows):
+        return ops.gemm(self.h_user[rows].contiguous(), self.W1a, bias=self.b1)
+
+    def store(self, P, n=None):
+        return ops.edge_mlp_dense_store(P, self.Q if n is None else self.Q[:n], *self.tail)
+
+    def filter(self, P, tau, counts, cand_items, cand_scores):
+        ops.edge_mlp_dense_filter(P, self.Q, *self.tail, tau, counts, cand_items, cand_scores)
+
+
+def _rows_exact_mlp(mlp, n_items, k, rows, exclude, vals, idx, out_pos):
+    """_rows_exact for the MLP head: the dense store of `rows` over all items, in chunks of
+    2^26 / n_items rows, excluded items masked to -inf, topk_rows."""
+    if rows.numel() == 0:
+        return
+    if n_items == 0:
+        vals[out_pos] = float('-inf')
+        idx[out_pos] = -1
+        return
+    step = max(1, (1 << 26) // n_items)
+    for c0 in range(0, rows.numel(), step):
+        r = rows[c0:c0 + step].contiguous()
+        sc = mlp.store(mlp.P(r))
+        if exclude is not None:
+            ops.mask_excluded(sc, r, exclude[0], exclude[1])
+        v, i = topk_rows(sc, k)
+        i = torch.where(v == float('-inf'), torch.full_like(i, -1), i)  # masked or past the end
+        pos = out_pos[c0:c0 + step]
+        vals[pos] = v
+        idx[pos] = i
+
+
 def recommend(h_user, h_item, k, user_rows=None, exclude=None, *, batch_size=8192,
-              sample=65536, cand_cap=1024, return_stats=False):
+              sample=65536, cand_cap=1024, return_stats=False, head=None):
     """The k best items per user by (cosine desc, item id asc), excluded items removed —
     the lists of an exhaustive fp32 ranking, bit for bit — on device tensors and without a
     score matrix.
@@ -178,6 +230,23 @@ def recommend(h_user, h_item, k, user_rows=None, exclude=None, *, batch_size=819
 
     Non-finite embeddings are outside the contract: a NaN or inf score has no place in the
     ranking, and the filter's comparison drops it silently.
+
+    head: None ranks by the cosine, as above.  A PredictingLayer (model.pred_fn.layer_nn,
+    the reference's 128 / 32 hidden sizes, hidden_1 [128, 2 d]) ranks by the MLP head's score
+    instead; vals are then the values of ops.edge_mlp for the pairs, and everything else —
+    the (score desc, item id asc) order, user_rows, exclude, the padding, the stats, the one
+    readback — is the same.  Q = h_item W1b^T is formed once per call; per batch
+    P = h_user[rows] W1a^T + b1, the head's scores of the item prefix are stored (no id
+    arrays) and their k-th best non-excluded value taken as tau; one pass over all items
+    keeps the (item, score) pairs with score >= tau, at most cand_cap per user, and those are
+    ranked.  There is no band: the filter compares the final fp32 score, at least k eligible
+    items of the prefix score >= tau, so every member of the exhaustive top k (and every tie
+    at the k-th value) is kept.  Rows that kept more than cand_cap items — a saturated head,
+    whose scores are 1.0f for many items, does that — and the whole call when
+    k > cand_cap / 4 are recomputed exhaustively (dense scores of the rows over all items in
+    chunks of 2^26 / n_items rows, topk_rows).  use_popularity is not offered here:
+    softmax(scores) + w popularity needs each row's full denominator, and get_recs remains
+    the path for it.  Non-finite scores are outside the contract, as for the cosine.
 
     stats (return_stats=True): candidates_mean, candidates_max (kept items per row, counted
     past the cap), overflow_rows, sample, cand_cap, fast_path."""
@@ -211,6 +280,38 @@ def recommend(h_user, h_item, k, user_rows=None, exclude=None, *, batch_size=819
     m = min(sample, n_items)
     stats = {'candidates_mean': 0.0, 'candidates_max': 0, 'overflow_rows': 0, 'sample': m,
              'cand_cap': cand_cap, 'fast_path': False}
+    if head is not None:
+        mlp = _MlpHead(head, h_user, h_item)
+        all_pos = torch.arange(U, device=dev)
+        if not (k <= cand_cap // 4 and n_items > 0 and U > 0):
+            _rows_exact_mlp(mlp, n_items, k, user_rows, exclude, vals, idx, all_pos)
+            return (idx, vals, stats) if return_stats else (idx, vals)
+        stats['fast_path'] = True
+        counts = torch.zeros(U, dtype=torch.int32, device=dev)
+        for b0 in range(0, U, batch_size):
+            rows = user_rows[b0:b0 + batch_size]
+            B = rows.numel()
+            P = mlp.P(rows)
+            s = mlp.store(P, m)
+            if exclude is not None:
+                ops.mask_excluded(s, rows, exclude[0], exclude[1])
+            tau = topk_rows(s, k)[0][:, k - 1].contiguous()  # -inf: fewer than k eligible there
+            del s
+            cand = torch.empty((B, cand_cap), dtype=torch.int32, device=dev)
+            cand_sc = torch.empty((B, cand_cap), dtype=torch.float32, device=dev)
+            mlp.filter(P, tau, counts[b0:b0 + B], cand, cand_sc)
+            ops.topk_scored_candidates(counts[b0:b0 + B], cand, cand_sc, k, rows,
+                                       None if exclude is None else exclude[0],
+                                       None if exclude is None else exclude[1],
+                                       vals[b0:b0 + B], idx[b0:b0 + B])
+        cnt = counts.cpu().numpy()                   # the call's one readback
+        over = np.nonzero(cnt > cand_cap)[0]
+        if over.size:
+            pos = torch.from_numpy(over).to(dev)
+            _rows_exact_mlp(mlp, n_items, k, user_rows[pos], exclude, vals, idx, pos)
+        stats.update(candidates_mean=float(cnt.mean()), candidates_max=int(cnt.max()),
+                     overflow_rows=int(over.size))
+        return (idx, vals, stats) if return_stats else (idx, vals)
     fast = (k <= cand_cap // 4 and d <= REC_MAX_D and d % 4 == 0 and d >= 4 and n_items > 0
             and U > 0)
     if not fast:

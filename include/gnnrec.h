@@ -446,6 +446,26 @@ int gnnrec_edge_mlp_grouped_f32(const int64_t* src_g, int64_t n_groups, const in
                                 float* out_first, int64_t K, const int64_t* dst, float* out,
                                 const float* P, const float* Q, const float* W2, const float* b2,
                                 const float* w3, const float* b3, void* stream);
+/* The same scores for every pair of a user batch and an item range, without id arrays:
+ * out[u, v] (row stride ldo) = the value gnnrec_edge_mlp_f32 returns for (u, v), bit for
+ * bit, from P [n_users, 128] and Q [n_items, 128].  A 32-item tile of Q is staged once and
+ * scored for 64 users in turn, so Q is read n_users / 64 times, not n_users times.  P, Q, W2
+ * 16-byte aligned, n_items < 2^31. */
+int gnnrec_edge_mlp_dense_store_f32(const float* P, int64_t n_users, const float* Q,
+                                    int64_t n_items, const float* W2, const float* b2,
+                                    const float* w3, const float* b3, float* out, int64_t ldo,
+                                    void* stream);
+/* The same scores, none written to a matrix: where score(u, v) >= tau[u] (compared as is:
+ * the score is the final fp32 value; -inf keeps every item, +inf none) item v takes a slot
+ * of row u with one increment of counts[u] (int32, zero before the first call) and, while
+ * slot < cap, its id and score are stored in cand_items / cand_scores [n_users, cap] (in no
+ * fixed order).  counts keeps counting past cap — counts[u] > cap marks an overflowed row —
+ * the contract of gnnrec_score_bf16_filter.  1 <= cap <= 4096. */
+int gnnrec_edge_mlp_dense_filter_f32(const float* P, int64_t n_users, const float* Q,
+                                     int64_t n_items, const float* W2, const float* b2,
+                                     const float* w3, const float* b3, const float* tau,
+                                     int32_t* counts, int32_t* cand_items, float* cand_scores,
+                                     int64_t cap, void* stream);
 
 /* ---- a9: block sampler (K8) ----------------------------------------------
  * Per relation, for each seed (dst) v: collect its in-edges from the global
@@ -691,6 +711,17 @@ int gnnrec_topk_candidates_f32(const int32_t* counts, const int32_t* cand_items,
                                int64_t ldu, const float* h_item, int64_t ldi, int64_t d,
                                const int64_t* exclude_indptr, const int32_t* exclude_indices,
                                int64_t k, float* out_vals, int64_t* out_idx, void* stream);
+/* The same for candidates that carry their scores (gnnrec_edge_mlp_dense_filter_f32's
+ * cand_items / cand_scores [n_rows, cap]): per batch row r with counts[r] <= cap, its first
+ * counts[r] (item, score) pairs minus the user's excluded items, ranked by (score desc, item
+ * asc) — the slot order is arbitrary, the output is not — into out_vals / out_idx
+ * [n_rows, k], padded with (-inf, -1).  Rows with counts[r] > cap are left unwritten.
+ * 1 <= k <= cap <= 4096. */
+int gnnrec_topk_scored_candidates_f32(const int32_t* counts, const int32_t* cand_items,
+                                      const float* cand_scores, int64_t cap, int64_t n_rows,
+                                      const int64_t* user_rows, const int64_t* exclude_indptr,
+                                      const int32_t* exclude_indices, int64_t k, float* out_vals,
+                                      int64_t* out_idx, void* stream);
 
 /* ---- f2: projection backward (training step) -----------------------------
  * Replace torch autograd of the reference's nn.Linear layers and the
