@@ -201,6 +201,72 @@ static void validation() {
   CHECK(gnnrec_topk_scored_candidates_f32(nullptr, nullptr, nullptr, 64, 0, nullptr, nullptr,
                                           nullptr, 10, nullptr, nullptr, nullptr) == GNNREC_OK,
         "scored candidates empty");
+  // the popularity-weighted ratings (recommend_pop.hip, the rating entries of recommend.hip and
+  // heads.hip): every refusal comes before a launch
+  CHECK(gnnrec_normalize_rows_f32(f16, 104, 5, 102, nullptr, f16, 104, nullptr) == GNNREC_EINVAL &&
+            err_has("multiple of 4"),
+        "normalize f32 d % 4");
+  CHECK(gnnrec_normalize_rows_f32(f16, 100, 5, 100, nullptr, f16, 100, nullptr) == GNNREC_EINVAL &&
+            err_has("dpad"),
+        "normalize f32 dpad");
+  CHECK(gnnrec_normalize_rows_f32(f16, 100, 5, 100, nullptr, reinterpret_cast<float*>(24), 104,
+                                  nullptr) == GNNREC_EINVAL && err_has("aligned"),
+        "normalize f32 unaligned out");
+  CHECK(gnnrec_normalize_rows_f32(nullptr, 100, 0, 100, nullptr, nullptr, 104, nullptr) ==
+            GNNREC_OK,
+        "normalize f32 empty");
+  CHECK(gnnrec_cos_denominator_parts(0) == 0 && gnnrec_cos_denominator_parts(1) == 1 &&
+            gnnrec_cos_denominator_parts(1024) == 1 && gnnrec_cos_denominator_parts(1025) == 2,
+        "denominator parts");
+  CHECK(gnnrec_cos_denominators_f32(f16, 4, f16, 9, 12, f16, f16, nullptr) == GNNREC_EINVAL &&
+            err_has("multiple of 8"),
+        "denominators dpad");
+  CHECK(gnnrec_cos_denominators_f32(f16, 4, reinterpret_cast<float*>(8), 9, 16, f16, f16,
+                                    nullptr) == GNNREC_EINVAL && err_has("unaligned"),
+        "denominators unaligned items");
+  CHECK(gnnrec_cos_denominators_f32(f16, 4, f16, 9, 16, nullptr, f16, nullptr) == GNNREC_EINVAL,
+        "denominators null parts");
+  CHECK(gnnrec_cos_denominators_f32(nullptr, 0, nullptr, 9, 16, nullptr, nullptr, nullptr) ==
+            GNNREC_OK,
+        "denominators no users");
+  CHECK(gnnrec_fold_partials_f32(nullptr, 3, 4, f16, nullptr) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "fold null parts");
+  CHECK(gnnrec_exp_rowsum_f32(f16, 8, 3, 9, f16, nullptr) == GNNREC_EINVAL, "rowsum ld < cols");
+  CHECK(gnnrec_rating_rows_f32(f16, 9, 3, 9, nullptr, f16, nullptr) == GNNREC_EINVAL,
+        "rating rows null Z");
+  CHECK(gnnrec_rating_rows_f32(nullptr, 9, 0, 9, nullptr, nullptr, nullptr) == GNNREC_OK,
+        "rating rows empty");
+  CHECK(gnnrec_rating_thresholds_f32(f16, f16, nullptr, 3, f16, nullptr) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "thresholds null pmax");
+  CHECK(gnnrec_mask_excluded_mapped_f32(f16, 9, 3, 9, nullptr, nullptr, l16, i16, nullptr) ==
+            GNNREC_EINVAL && err_has("col_ids"),
+        "mapped mask null col_ids");
+  CHECK(gnnrec_score_bf16_store_rating(p16, 4, p16, 9, 32, nullptr, f16, f16, 9, nullptr) ==
+            GNNREC_EINVAL && err_has("null Z"),
+        "store rating null Z");
+  CHECK(gnnrec_score_bf16_filter_rating(p16, 4, p16, 9, 32, f16, f16, f16, i16, i16, 4097,
+                                        nullptr) == GNNREC_EINVAL && err_has("cap must be"),
+        "filter rating cap");
+  CHECK(gnnrec_score_bf16_filter_rating(p16, 4, p16, 9, 32, f16, nullptr, f16, i16, i16, 64,
+                                        nullptr) == GNNREC_EINVAL && err_has("null pointer"),
+        "filter rating null p");
+  CHECK(gnnrec_topk_candidates_rating_f32(i16, i16, 64, 3, nullptr, f16, 16, f16, 16, 16, nullptr,
+                                          nullptr, nullptr, f16, 10, f16, l16, nullptr) ==
+            GNNREC_EINVAL && err_has("null Z"),
+        "candidates rating null Z");
+  CHECK(gnnrec_edge_mlp_dense_denominators_f32(f16, 4, f16, 9, f16, f16, f16, f16, nullptr,
+                                               nullptr) == GNNREC_EINVAL && err_has("null parts"),
+        "dense denominators null parts");
+  CHECK(gnnrec_edge_mlp_dense_store_rating_f32(f16, 4, f16, 9, f16, f16, f16, f16, f16, nullptr,
+                                               f16, 9, nullptr) == GNNREC_EINVAL &&
+            err_has("null Z"),
+        "dense store rating null p");
+  CHECK(gnnrec_edge_mlp_dense_filter_rating_f32(f16, 4, f16, 9, f16, f16, f16, f16, f16, f16, f16,
+                                                i16, i16, f16, 0, nullptr) == GNNREC_EINVAL &&
+            err_has("cap must be"),
+        "dense filter rating cap");
   // edge removal (csr_filter.hip): every refusal comes before the first memset or launch;
   // an empty problem still writes the status and indptr', so its host side is the
   // workspace query, which must give room for them

@@ -16,6 +16,7 @@
 //    reference is never built.
 #include "common.hpp"
 #include "cos_score.hpp"
+#include "rating.hpp"
 #include <cmath>
 
 namespace gnnrec {
@@ -402,6 +403,21 @@ int launch_edge_mlp_lds(bool grouped, EdgeMlpArgs& a, hipStream_t s) {
 // list where score >= tau[u] (no band: the score is the final fp32 value), counting past
 // cap.  Items past n_cols are staged as zero rows and masked at the store or the compare;
 // rows past n_users are never visited.
+//
+// The popularity-weighted rating (f1d, rating.hpp) adds three epilogues:
+// STORE_R and FILTER_R are STORE and FILTER with R = rating(score, Z[u], pcol[v]) in the
+// score's place (no band either: the compared value is the final fp32 R, and it is what the
+// filter keeps), and DENOM writes nothing but the partial sums of Z[u] = sum over all items
+// of expf(score).  Their order is fixed by n_items alone: a DENOM work item is (a chunk of
+// kDenseZTiles consecutive item tiles, user group) — the partial is addressed by the chunk's
+// index, whichever wave takes it — the wave walks the chunk's tiles in ascending order, a
+// tile's 32 values expf(score) (items past the end count zero) are folded over the lanes by
+// an xor tree (offsets 1, 2, 4, 8, 16) and added to the user's sum in the wave's LDS; the
+// partials [chunks, n_users] are folded in index order by gnnrec_fold_partials_f32.  No float
+// atomics; a user's sums do not depend on the group it is scored in.
+constexpr int kDenseZTiles = 32;  // item tiles (1024 items) per partial of the denominators
+enum DenseMode { kDenseStore = 0, kDenseFilter = 1, kDenseDenom = 2, kDenseStoreR = 3,
+                 kDenseFilterR = 4 };
 constexpr int kDenseUsers = 64;  // users scored per staged item tile, at most
 constexpr int kDenseStage = 4;   // users whose P rows are staged in LDS at a time
 constexpr int kDenseCandMax = 4096;  // candidate slots per row, at most (recommend.hip's)
@@ -420,6 +436,10 @@ struct DenseMlpArgs {
   int* cand_items;
   float* cand_scores;
   int cap;
+  const float* Z;       // STORE_R / FILTER_R: per user row
+  const float* pcol;    //                     per column of Q
+  float* part;          // DENOM: [chunks, n_users]
+  int64_t n_tiles;      // DENOM: item tiles
 };
 
 // The P rows of users [u0, u0 + kDenseStage) as the stage holds them (row-major, 32 chunks a
@@ -433,10 +453,14 @@ __device__ __forceinline__ void dense_fetch_p(const float4* __restrict__ P4, int
   }
 }
 
-template <bool FILTER>
+template <int MODE>
 __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) {
+  constexpr bool FILTER = MODE == kDenseFilter || MODE == kDenseFilterR;
+  constexpr bool RATING = MODE == kDenseStoreR || MODE == kDenseFilterR;
+  constexpr bool DENOM = MODE == kDenseDenom;
   __shared__ float4 image[kMlpWaves][kMlpTile * 32];     // 16 KB per wave
   __shared__ float4 pstage[kMlpWaves][kDenseStage * 32];  // 2 KB per wave
+  __shared__ float zsum[kMlpWaves][DENOM ? kDenseUsers : 1];  // DENOM: the group's sums
   static_assert(kDenseStage * 32 == 2 * kWave, "a stage is two chunks per lane");
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
@@ -452,9 +476,19 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) 
   // user group fastest: the waves of a block (and neighbouring blocks) share a Q tile in L2
   for (int64_t item = (int64_t)blockIdx.x * kMlpWaves + wv; item < a.work;
        item += (int64_t)gridDim.x * kMlpWaves) {
-    const int64_t t = item / a.groups, g = item - t * a.groups;
+    const int64_t t0 = item / a.groups, g = item - t0 * a.groups;
+    // DENOM: t0 is a chunk of tiles, walked in order; else the tile itself
+    const int64_t t_beg = DENOM ? t0 * kDenseZTiles : t0;
+    const int64_t n_walk = DENOM ? min<int64_t>(kDenseZTiles, a.n_tiles - t_beg) : 1;
+    if constexpr (DENOM) zsum[wv][lane] = 0.f;  // only lane 0 touches it until the write-out
+    // one item tile for the group's users (the body stays at the loop's indentation); a
+    // lambda, called once outside DENOM: as a loop with one trip the store and filter forms
+    // compiled to 12 and 8 more bytes of scratch per lane
+    auto score_tile = [&](const int64_t t) {
     const int64_t col = t * kMlpTile + r;  // this lane's item (both halves)
     const int v = col < a.n_cols ? (int)col : -1;
+    float pv = 0.f;
+    if constexpr (RATING) pv = v >= 0 ? a.pcol[col] : 0.f;
     // the previous work item's reads of the image are done before it is overwritten
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 #pragma unroll
@@ -485,10 +519,17 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) 
         float4 pc[16];  // both lane halves read one address each: LDS broadcasts
 #pragma unroll
         for (int c = 0; c < 16; ++c) pc[c] = Ps[j * 32 + 16 * h + c];
-        float thr = 0.f;
+        float thr = 0.f, zu = 1.f;
         if constexpr (FILTER) thr = a.tau[u];
-        const float sc = mlp_tile_score<true>(a.m, S, w, pc, r, h, b3v);
-        if (h == 0 && v >= 0) {
+        if constexpr (RATING) zu = a.Z[u];
+        float sc = mlp_tile_score<true>(a.m, S, w, pc, r, h, b3v);
+        if constexpr (RATING) sc = rating(sc, zu, pv);
+        if constexpr (DENOM) {
+          float x = (h == 0 && v >= 0) ? expf(sc) : 0.f;
+#pragma unroll
+          for (int off = 1; off < 32; off <<= 1) x += __shfl_xor(x, off);
+          if (lane == 0) zsum[wv][u - u_beg] += x;
+        } else if (h == 0 && v >= 0) {
           if constexpr (FILTER) {
             if (sc >= thr) {
               // the counter keeps counting past cap (the overflow signal); a store happens
@@ -505,6 +546,18 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) 
         }
       }
     }
+    };
+    if constexpr (DENOM) {
+      for (int64_t tt = 0; tt < n_walk; ++tt) score_tile(t_beg + tt);
+    } else {
+      score_tile(t0);
+    }
+    if constexpr (DENOM) {
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // lane 0's sums are visible
+      const int64_t u = g * a.per_group + lane;
+      if (lane < a.per_group && u < a.n_users) a.part[t0 * a.n_users + u] = zsum[wv][lane];
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
   }
 }
 
@@ -519,20 +572,25 @@ int check_dense(const char* fn, const float* P, int64_t n_users, const float* Q,
   return GNNREC_OK;
 }
 
-int launch_edge_mlp_dense(bool filter, DenseMlpArgs& a, hipStream_t s) {
+int launch_edge_mlp_dense(int mode, const char* fn, DenseMlpArgs& a, hipStream_t s) {
   // the users split evenly over the groups: 67 users (get_recs' batch against 1M items) are
   // 34 + 33, not 64 + 3 with every tile staged a second time for three users
   a.groups = (a.n_users + kDenseUsers - 1) / kDenseUsers;
   a.per_group = (a.n_users + a.groups - 1) / a.groups;
-  a.work = ((a.n_cols + kMlpTile - 1) / kMlpTile) * a.groups;
+  a.n_tiles = (a.n_cols + kMlpTile - 1) / kMlpTile;
+  a.work = (mode == kDenseDenom ? (a.n_tiles + kDenseZTiles - 1) / kDenseZTiles : a.n_tiles) *
+           a.groups;
   int64_t blocks = (a.work + kMlpWaves - 1) / kMlpWaves;
   if (blocks > kMlpResidentWaves / kMlpWaves) blocks = kMlpResidentWaves / kMlpWaves;
-  if (filter)
-    hipLaunchKernelGGL(edge_mlp_dense_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL(edge_mlp_dense_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-  return check_launch(filter ? "gnnrec_edge_mlp_dense_filter_f32"
-                             : "gnnrec_edge_mlp_dense_store_f32");
+#define GNNREC_LAUNCH_DENSE(M) \
+  hipLaunchKernelGGL(edge_mlp_dense_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, s, a)
+  if (mode == kDenseFilter) GNNREC_LAUNCH_DENSE(kDenseFilter);
+  else if (mode == kDenseStore) GNNREC_LAUNCH_DENSE(kDenseStore);
+  else if (mode == kDenseDenom) GNNREC_LAUNCH_DENSE(kDenseDenom);
+  else if (mode == kDenseStoreR) GNNREC_LAUNCH_DENSE(kDenseStoreR);
+  else GNNREC_LAUNCH_DENSE(kDenseFilterR);
+#undef GNNREC_LAUNCH_DENSE
+  return check_launch(fn);
 }
 
 }  // namespace
@@ -638,7 +696,7 @@ extern "C" int gnnrec_edge_mlp_dense_store_f32(const float* P, int64_t n_users, 
   a.m.P = P; a.m.Q = Q; a.m.W2 = W2; a.m.b2 = b2; a.m.w3 = w3; a.m.b3 = b3;
   a.n_users = n_users; a.n_cols = n_items;
   a.out = out; a.ldo = ldo;
-  return launch_edge_mlp_dense(false, a, as_stream(stream));
+  return launch_edge_mlp_dense(kDenseStore, fn, a, as_stream(stream));
 }
 
 extern "C" int gnnrec_edge_mlp_dense_filter_f32(const float* P, int64_t n_users, const float* Q,
@@ -659,5 +717,62 @@ extern "C" int gnnrec_edge_mlp_dense_filter_f32(const float* P, int64_t n_users,
   a.n_users = n_users; a.n_cols = n_items;
   a.tau = tau; a.counts = counts; a.cand_items = cand_items; a.cand_scores = cand_scores;
   a.cap = (int)cap;
-  return launch_edge_mlp_dense(true, a, as_stream(stream));
+  return launch_edge_mlp_dense(kDenseFilter, fn, a, as_stream(stream));
+}
+
+extern "C" int gnnrec_edge_mlp_dense_denominators_f32(const float* P, int64_t n_users,
+                                                      const float* Q, int64_t n_items,
+                                                      const float* W2, const float* b2,
+                                                      const float* w3, const float* b3,
+                                                      float* parts, void* stream) {
+  using namespace gnnrec;
+  const char* fn = "gnnrec_edge_mlp_dense_denominators_f32";
+  const int rc = check_dense(fn, P, n_users, Q, n_items, W2, b2, w3, b3);
+  if (rc != GNNREC_OK || n_users == 0 || n_items == 0) return rc;
+  GNNREC_REQUIRE(parts, "%s: null parts", fn);
+  DenseMlpArgs a{};
+  a.m.P = P; a.m.Q = Q; a.m.W2 = W2; a.m.b2 = b2; a.m.w3 = w3; a.m.b3 = b3;
+  a.n_users = n_users; a.n_cols = n_items;
+  a.part = parts;
+  return launch_edge_mlp_dense(kDenseDenom, fn, a, as_stream(stream));
+}
+
+extern "C" int gnnrec_edge_mlp_dense_store_rating_f32(const float* P, int64_t n_users,
+                                                      const float* Q, int64_t n_items,
+                                                      const float* W2, const float* b2,
+                                                      const float* w3, const float* b3,
+                                                      const float* Z, const float* p_col,
+                                                      float* out, int64_t ldo, void* stream) {
+  using namespace gnnrec;
+  const char* fn = "gnnrec_edge_mlp_dense_store_rating_f32";
+  const int rc = check_dense(fn, P, n_users, Q, n_items, W2, b2, w3, b3);
+  if (rc != GNNREC_OK || n_users == 0 || n_items == 0) return rc;
+  GNNREC_REQUIRE(out && ldo >= n_items, "%s: bad out / ldo", fn);
+  GNNREC_REQUIRE(Z && p_col, "%s: null Z / p_col", fn);
+  DenseMlpArgs a{};
+  a.m.P = P; a.m.Q = Q; a.m.W2 = W2; a.m.b2 = b2; a.m.w3 = w3; a.m.b3 = b3;
+  a.n_users = n_users; a.n_cols = n_items;
+  a.out = out; a.ldo = ldo; a.Z = Z; a.pcol = p_col;
+  return launch_edge_mlp_dense(kDenseStoreR, fn, a, as_stream(stream));
+}
+
+extern "C" int gnnrec_edge_mlp_dense_filter_rating_f32(
+    const float* P, int64_t n_users, const float* Q, int64_t n_items, const float* W2,
+    const float* b2, const float* w3, const float* b3, const float* Z, const float* p_col,
+    const float* tau, int32_t* counts, int32_t* cand_items, float* cand_scores, int64_t cap,
+    void* stream) {
+  using namespace gnnrec;
+  const char* fn = "gnnrec_edge_mlp_dense_filter_rating_f32";
+  const int rc = check_dense(fn, P, n_users, Q, n_items, W2, b2, w3, b3);
+  if (rc != GNNREC_OK) return rc;
+  GNNREC_REQUIRE(cap >= 1 && cap <= kDenseCandMax, "%s: cap must be in [1, %d] (got %lld)", fn,
+                 kDenseCandMax, (long long)cap);
+  if (n_users == 0 || n_items == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(Z && p_col && tau && counts && cand_items && cand_scores, "%s: null pointer", fn);
+  DenseMlpArgs a{};
+  a.m.P = P; a.m.Q = Q; a.m.W2 = W2; a.m.b2 = b2; a.m.w3 = w3; a.m.b3 = b3;
+  a.n_users = n_users; a.n_cols = n_items;
+  a.tau = tau; a.counts = counts; a.cand_items = cand_items; a.cand_scores = cand_scores;
+  a.cap = (int)cap; a.Z = Z; a.pcol = p_col;
+  return launch_edge_mlp_dense(kDenseFilterR, fn, a, as_stream(stream));
 }

@@ -39,8 +39,25 @@
 // >= tau_r - eps, and every item of the true top k has a >= tau_r - 2 eps.  Items below
 // that are discarded; a looser tau_r only admits more candidates, never loses one.  (Ties in
 // score at the k-th place are covered too: a tied item's score is >= tau_r - eps as well.)
+//
+// THE RATING BAND (f1d, popularity: rating.hpp, recommend_pop.hip).  With
+// popularity the ranking is by R(u, v) = expf(score) / Z_u + p_v, and the scorer's rating
+// epilogues form Ra = rating(a, Z_u, p_v) from the approximate score.  In real numbers, with
+// |a - score| <= eps and score <= 1 (up to fp32 rounding, covered by the e^eps),
+//   |e^a - e^score| <= e^(1 + eps) (e^eps - 1),
+// the two sides share Z_u and p_v, and each side's three fp32 operations add at most
+// 2^-22 (expf, within 2 ulp) + 2^-24 (divide) relative to its quotient <= e^(1 + eps) / Z_u
+// and 2^-24 (add) relative to the sum <= e^(1 + eps) / Z_u + max p: together, both sides,
+// below 2^-20 e^(1 + eps) / Z_u + 2^-22 max p.  So
+//   |Ra - R| <= delta_u = e^(1 + eps) ((e^eps - 1) + 2^-20) / Z_u + 2^-22 max p,
+// and THE FILTER's argument carries over with R, Ra, delta_u for score, a, eps: for any tau_u
+// with k eligible items at Ra >= tau_u, every member of the true top k (ties at the k-th
+// place too) has Ra >= tau_u - 2 delta_u.  gnnrec_rating_thresholds_f32 forms
+// tau_u - 2 delta_u in double, once per batch, rounded down; the epilogue compares with it
+// as it is.
 #include "common.hpp"
 #include "cos_score.hpp"
+#include "rating.hpp"
 #include <algorithm>
 #include <cmath>
 
@@ -119,13 +136,47 @@ __global__ __launch_bounds__(256) void normalize_rows_bf16_kernel(
 // load per row in front of its compare serialises 32 memory latencies per tile — from
 // thr_lds (the wave's 64 thresholds, staged with the user tile: four rows per 16-B read)
 // when given, else from tau.
-template <bool FILTER>
+//
+// RATING (f1d): the value stored or compared is Ra = rating(a, Z_row, p_col)
+// (rating.hpp) instead of a.  Z (per batch row, from z_lds — staged like the thresholds — or
+// the array) and pcol (per column of the table) come with it, and tau then holds the
+// finished per-row thresholds tau_u - 2 delta_u (gnnrec_rating_thresholds_f32), formed once
+// per batch, compared as they are.
+template <bool FILTER, bool RATING>
 __device__ __forceinline__ void score_epilogue(const f32x16 (&acc)[2][2], int64_t r0, int64_t c0,
                                                int l31, int h, int64_t B, int64_t n,
                                                float* __restrict__ out, int64_t ldo,
                                                const float* __restrict__ tau,
                                                const float* thr_lds, int* __restrict__ counts,
-                                               int* __restrict__ cand, int cap) {
+                                               int* __restrict__ cand, int cap,
+                                               const float* __restrict__ Z, const float* z_lds,
+                                               const float* __restrict__ pcol) {
+  float pj[2] = {0.f, 0.f};
+  if constexpr (RATING) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      if (c0 + j * 32 + l31 < n) pj[j] = pcol[c0 + j * 32 + l31];
+  }
+  // RATING: the Z of rows i 32 + 8 g + 4 h + (0..3), fetched per 32-row half (all 32 at once
+  // leave the dpad = 128 tile no registers)
+  auto fetch_z = [&](int i, f32x4 (&zr)[4]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      if (z_lds) {
+        zr[g] = *reinterpret_cast<const f32x4*>(z_lds + i * 32 + 8 * g + 4 * h);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int64_t row = r0 + i * 32 + 8 * g + 4 * h + q;
+          zr[g][q] = row < B ? Z[row] : 1.f;
+        }
+      }
+    }
+  };
+  auto value = [&](const f32x4 (&zr)[4], int i, int j, int reg) -> float {
+    if constexpr (RATING) return rating(acc[i][j][reg], zr[reg >> 2][reg & 3], pj[j]);
+    else return acc[i][j][reg];
+  };
   if constexpr (FILTER) {
     f32x4 thr[2][4];  // [i][g]: rows i 32 + 8 g + 4 h + (0..3), the registers 4 g .. 4 g + 3
 #pragma unroll
@@ -138,46 +189,55 @@ __device__ __forceinline__ void score_epilogue(const f32x16 (&acc)[2][2], int64_
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int64_t row = r0 + i * 32 + 8 * g + 4 * h + q;
-            thr[i][g][q] = row < B ? tau[row] - 2.f * kRecEps : INFINITY;
+            if constexpr (RATING) thr[i][g][q] = row < B ? tau[row] : INFINITY;
+            else thr[i][g][q] = row < B ? tau[row] - 2.f * kRecEps : INFINITY;
           }
         }
       }
     const bool colok[2] = {c0 + l31 < n, c0 + 32 + l31 < n};
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i) {
+      f32x4 zr[4];
+      if constexpr (RATING) fetch_z(i, zr);
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          if (colok[j] && acc[i][j][reg] >= thr[i][reg >> 2][reg & 3]) {
+          if (colok[j] && value(zr, i, j, reg) >= thr[i][reg >> 2][reg & 3]) {
             // the counter keeps counting past cap (the overflow signal); a store happens
             // only inside the row's cap slots
             const int64_t row = r0 + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
             const int slot = atomicAdd(counts + row, 1);
             if (slot >= 0 && slot < cap) cand[row * cap + slot] = (int)(c0 + j * 32 + l31);
           }
+    }
   } else {
     // addresses split into a wave-uniform part (scalar registers) and one lane offset, so
     // that the 32 rows' address arithmetic does not sit in vector registers
     const int64_t lane_out = (int64_t)(4 * h) * ldo + l31;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i) {
+      f32x4 zr[4];
+      if constexpr (RATING) fetch_z(i, zr);
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
         const int64_t urow = r0 + i * 32 + (reg & 3) + 8 * (reg >> 2);  // uniform
         if (urow + 4 * h >= B) continue;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          if (c0 + j * 32 + l31 < n) (out + urow * ldo + c0 + j * 32)[lane_out] = acc[i][j][reg];
+          if (c0 + j * 32 + l31 < n)
+            (out + urow * ldo + c0 + j * 32)[lane_out] = value(zr, i, j, reg);
       }
+    }
   }
 }
 
-template <bool FILTER>
+template <bool FILTER, bool RATING>
 __global__ __launch_bounds__(256) void score_bf16_kernel(
     const uint16_t* __restrict__ U, int64_t B, const uint16_t* __restrict__ V, int64_t n,
     int dpad, int64_t n_utiles, float* __restrict__ out, int64_t ldo,
-    const float* __restrict__ tau, int* __restrict__ counts, int* __restrict__ cand, int cap) {
+    const float* __restrict__ tau, int* __restrict__ counts, int* __restrict__ cand, int cap,
+    const float* __restrict__ Z, const float* __restrict__ pcol) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, h = lane >> 5;
   const int64_t tile = blockIdx.x;
@@ -217,7 +277,8 @@ __global__ __launch_bounds__(256) void score_bf16_kernel(
         for (int j = 0; j < 2; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][i], b[s][j], acc[i][j], 0, 0, 0);
   }
-  score_epilogue<FILTER>(acc, r0, c0, l31, h, B, n, out, ldo, tau, nullptr, counts, cand, cap);
+  score_epilogue<FILTER, RATING>(acc, r0, c0, l31, h, B, n, out, ldo, tau, nullptr, counts, cand,
+                                 cap, Z, nullptr, pcol);
 }
 
 // The same tile for dpad = 32, 64 and 128 (d <= 64 and 97..128; at 96 the registers of two
@@ -243,16 +304,18 @@ __device__ __forceinline__ void fetch_user_tile(u32x4 (&pf)[DPAD / 16], const ui
   }
 }
 
-template <int DPAD, bool FILTER>
+template <int DPAD, bool FILTER, bool RATING>
 __global__ __launch_bounds__(256, 2) void score_bf16_slab_kernel(
     const uint16_t* __restrict__ U, int64_t B, const uint16_t* __restrict__ V, int64_t n,
     float* __restrict__ out, int64_t ldo, const float* __restrict__ tau,
-    int* __restrict__ counts, int* __restrict__ cand, int cap) {
+    int* __restrict__ counts, int* __restrict__ cand, int cap, const float* __restrict__ Z,
+    const float* __restrict__ pcol) {
   constexpr int KS = DPAD / 16;        // k-steps
   constexpr int CH = DPAD / 8;         // 16-B chunks per row
   constexpr int ROWB = DPAD * 2 + 16;  // LDS bytes per staged row
   __shared__ __attribute__((aligned(16))) unsigned char sA[128 * ROWB];
   __shared__ __attribute__((aligned(16))) float sThr[128];  // the tile's tau - 2 eps (filter)
+  __shared__ __attribute__((aligned(16))) float sZ[RATING ? 128 : 4];  // the tile's Z (rating)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5;
   const int wr = wave >> 1, wc = wave & 1;
@@ -273,11 +336,18 @@ __global__ __launch_bounds__(256, 2) void score_bf16_slab_kernel(
   u32x4 pf[PF];
   // (the filter pass only: the store pass scores the short sample, and its epilogue's
   // addresses leave no room for the tile in flight at two blocks per CU)
-  constexpr bool kAhead = FILTER;
+  // (nor the rating filter, whose epilogue holds Z and p beside the thresholds)
+  constexpr bool kAhead = FILTER && !RATING;
   float tpf = INFINITY;  // thread t < 128: row t's threshold, +inf past the end (never passed)
+  float zpf = 1.f;       // and, for the ratings, row t's Z
   auto fetch_thr = [&](int64_t ut) {
     const int64_t r = ut * 128 + tid;
-    if (tid < 128) tpf = r < B ? tau[r] - 2.f * kRecEps : INFINITY;
+    if constexpr (FILTER && !RATING) {
+      if (tid < 128) tpf = r < B ? tau[r] - 2.f * kRecEps : INFINITY;
+    } else if (tid < 128) {
+      if constexpr (FILTER) tpf = r < B ? tau[r] : INFINITY;
+      zpf = r < B ? Z[r] : 1.f;
+    }
   };
   if (kAhead && (int64_t)blockIdx.y < n_ut) {
     fetch_user_tile<DPAD>(pf, U, B, blockIdx.y, tid);
@@ -285,13 +355,17 @@ __global__ __launch_bounds__(256, 2) void score_bf16_slab_kernel(
   }
   for (int64_t ut = blockIdx.y; ut < n_ut; ut += gridDim.y) {  // block-uniform trip count
     __syncthreads();  // the previous tile's reads are done
-    if constexpr (!kAhead) fetch_user_tile<DPAD>(pf, U, B, ut, tid);
+    if constexpr (!kAhead) {
+      fetch_user_tile<DPAD>(pf, U, B, ut, tid);
+      if constexpr (RATING) fetch_thr(ut);
+    }
 #pragma unroll
     for (int p = 0; p < PF; ++p) {
       const int idx = tid + p * 256;
       *reinterpret_cast<u32x4*>(sA + (idx / CH) * ROWB + (idx % CH) * 16) = pf[p];
     }
     if (FILTER && tid < 128) sThr[tid] = tpf;
+    if (RATING && tid < 128) sZ[tid] = zpf;
     __syncthreads();
     if (kAhead && ut + gridDim.y < n_ut) {
       fetch_user_tile<DPAD>(pf, U, B, ut + gridDim.y, tid);
@@ -319,26 +393,28 @@ __global__ __launch_bounds__(256, 2) void score_bf16_slab_kernel(
         for (int j = 0; j < 2; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], bfr[j][ks], acc[i][j], 0, 0, 0);
     }
-    score_epilogue<FILTER>(acc, r0, c0, l31, h, B, n, out, ldo, tau,
-                           FILTER ? sThr + wr * 64 : nullptr, counts, cand, cap);
+    score_epilogue<FILTER, RATING>(acc, r0, c0, l31, h, B, n, out, ldo, tau,
+                                   FILTER ? sThr + wr * 64 : nullptr, counts, cand, cap, Z,
+                                   RATING ? sZ + wr * 64 : nullptr, pcol);
   }
 }
 
-template <bool FILTER>
+template <bool FILTER, bool RATING = false>
 void launch_score(const uint16_t* U, int64_t B, const uint16_t* V, int64_t n, int dpad, float* out,
-                  int64_t ldo, const float* tau, int* counts, int* cand, int cap, hipStream_t s) {
+                  int64_t ldo, const float* tau, int* counts, int* cand, int cap, hipStream_t s,
+                  const float* Z = nullptr, const float* pcol = nullptr) {
   const int64_t nu = (B + 127) / 128, ni = (n + 127) / 128;
   if (dpad != 32 && dpad != 64 && dpad != 128) {
-    hipLaunchKernelGGL((score_bf16_kernel<FILTER>), dim3((unsigned)(nu * ni)), dim3(256), 0, s, U,
-                       B, V, n, dpad, nu, out, ldo, tau, counts, cand, cap);
+    hipLaunchKernelGGL((score_bf16_kernel<FILTER, RATING>), dim3((unsigned)(nu * ni)), dim3(256),
+                       0, s, U, B, V, n, dpad, nu, out, ldo, tau, counts, cand, cap, Z, pcol);
     return;
   }
   // enough blocks to fill the chip when the item range is short (the sample pass, small tables)
   const int64_t gy = std::min<int64_t>(nu, std::max<int64_t>(1, (2048 + ni - 1) / ni));
   const dim3 grid((unsigned)ni, (unsigned)gy), block(256);
-#define GNNREC_LAUNCH_SLAB(D)                                                                 \
-  hipLaunchKernelGGL((score_bf16_slab_kernel<D, FILTER>), grid, block, 0, s, U, B, V, n, out, \
-                     ldo, tau, counts, cand, cap)
+#define GNNREC_LAUNCH_SLAB(D)                                                                    \
+  hipLaunchKernelGGL((score_bf16_slab_kernel<D, FILTER, RATING>), grid, block, 0, s, U, B, V, n, \
+                     out, ldo, tau, counts, cand, cap, Z, pcol)
   if (dpad == 32) GNNREC_LAUNCH_SLAB(32);
   else if (dpad == 64) GNNREC_LAUNCH_SLAB(64);
   else GNNREC_LAUNCH_SLAB(128);
@@ -428,13 +504,15 @@ __device__ __forceinline__ void rank_and_emit(const int* ids, const float* sc, i
 // One block per batch row: its min(count, cap) candidates into LDS, the excluded ones
 // struck, the rest scored by lane groups exactly as sddmm_cos_kernel<LPR, 4> scores an edge,
 // then ranked.
-template <int LPR>
+// RATING: the rescored cosine becomes R = rating(score, Z[b], p[item]) (rating.hpp) before the
+// ranking, Z per batch row and p per item.
+template <int LPR, bool RATING>
 __global__ __launch_bounds__(256) void topk_candidates_kernel(
     const int* __restrict__ counts, const int* __restrict__ cand, int cap,
     const int64_t* __restrict__ user_rows, const float* __restrict__ Hu, int64_t ldu,
     const float* __restrict__ Hi, int64_t ldi, int d, const int64_t* __restrict__ ex_ptr,
     const int32_t* __restrict__ ex_idx, int k, float* __restrict__ out_v,
-    int64_t* __restrict__ out_i) {
+    int64_t* __restrict__ out_i, const float* __restrict__ Z, const float* __restrict__ p) {
   __shared__ int ids[kCandMax];
   __shared__ float sc[kCandMax];
   __shared__ int ex[kExChunk];
@@ -457,7 +535,8 @@ __global__ __launch_bounds__(256) void topk_candidates_kernel(
     const int i = i0 + grp;
     const int c = i < n ? ids[i] : -1;
     const bool ok = c >= 0;
-    const float r = cos_pair_vec4<LPR>(pu, Hi + (int64_t)(ok ? c : 0) * ldi, d, gl, ok);
+    float r = cos_pair_vec4<LPR>(pu, Hi + (int64_t)(ok ? c : 0) * ldi, d, gl, ok);
+    if constexpr (RATING) r = rating(r, Z[b], p[ok ? c : 0]);
     if (gl == LPR - 1 && i < n) sc[i] = ok ? r : -INFINITY;
   }
   __syncthreads();
@@ -573,13 +652,15 @@ extern "C" int gnnrec_mask_excluded_f32(float* scores, int64_t ld, int64_t n_row
   return check_launch("gnnrec_mask_excluded_f32");
 }
 
-extern "C" int gnnrec_topk_candidates_f32(const int32_t* counts, const int32_t* cand_items,
-                                          int64_t cap, int64_t n_rows, const int64_t* user_rows,
-                                          const float* h_user, int64_t ldu, const float* h_item,
-                                          int64_t ldi, int64_t d, const int64_t* exclude_indptr,
-                                          const int32_t* exclude_indices, int64_t k,
-                                          float* out_vals, int64_t* out_idx, void* stream) {
-  using namespace gnnrec;
+namespace gnnrec {
+namespace {
+// gnnrec_topk_candidates_f32, and with Z / p its rating form
+int topk_candidates_impl(const int32_t* counts, const int32_t* cand_items, int64_t cap,
+                         int64_t n_rows, const int64_t* user_rows, const float* h_user,
+                         int64_t ldu, const float* h_item, int64_t ldi, int64_t d,
+                         const int64_t* exclude_indptr, const int32_t* exclude_indices, int64_t k,
+                         float* out_vals, int64_t* out_idx, const float* Z, const float* p,
+                         void* stream) {
   GNNREC_REQUIRE(n_rows >= 0 && n_rows < (int64_t(1) << 31),
                  "gnnrec_topk_candidates_f32: bad row count");
   GNNREC_REQUIRE(cap >= 1 && cap <= kCandMax, "gnnrec_topk_candidates_f32: cap must be in "
@@ -598,15 +679,81 @@ extern "C" int gnnrec_topk_candidates_f32(const int32_t* counts, const int32_t* 
                  "gnnrec_topk_candidates_f32: exclusion indptr without indices");
   hipStream_t s = as_stream(stream);
   const dim3 grid((unsigned)n_rows), block(256);
-#define GNNREC_LAUNCH_CAND(LPR)                                                                 \
-  hipLaunchKernelGGL((topk_candidates_kernel<LPR>), grid, block, 0, s, counts, cand_items,      \
-                     (int)cap, user_rows, h_user, ldu, h_item, ldi, (int)d, exclude_indptr,     \
-                     exclude_indices, (int)k, out_vals, out_idx)
-  if (d <= 64) GNNREC_LAUNCH_CAND(16);  // the lane groups of gnnrec_sddmm_cos_f32
-  else if (d <= 128) GNNREC_LAUNCH_CAND(32);
-  else GNNREC_LAUNCH_CAND(64);
+#define GNNREC_LAUNCH_CAND(LPR, RATING)                                                         \
+  hipLaunchKernelGGL((topk_candidates_kernel<LPR, RATING>), grid, block, 0, s, counts,          \
+                     cand_items, (int)cap, user_rows, h_user, ldu, h_item, ldi, (int)d,         \
+                     exclude_indptr, exclude_indices, (int)k, out_vals, out_idx, Z, p)
+  if (Z) {
+    if (d <= 64) GNNREC_LAUNCH_CAND(16, true);
+    else if (d <= 128) GNNREC_LAUNCH_CAND(32, true);
+    else GNNREC_LAUNCH_CAND(64, true);
+  } else {
+    if (d <= 64) GNNREC_LAUNCH_CAND(16, false);  // the lane groups of gnnrec_sddmm_cos_f32
+    else if (d <= 128) GNNREC_LAUNCH_CAND(32, false);
+    else GNNREC_LAUNCH_CAND(64, false);
+  }
 #undef GNNREC_LAUNCH_CAND
   return check_launch("gnnrec_topk_candidates_f32");
+}
+}  // namespace
+}  // namespace gnnrec
+
+extern "C" int gnnrec_topk_candidates_f32(const int32_t* counts, const int32_t* cand_items,
+                                          int64_t cap, int64_t n_rows, const int64_t* user_rows,
+                                          const float* h_user, int64_t ldu, const float* h_item,
+                                          int64_t ldi, int64_t d, const int64_t* exclude_indptr,
+                                          const int32_t* exclude_indices, int64_t k,
+                                          float* out_vals, int64_t* out_idx, void* stream) {
+  return gnnrec::topk_candidates_impl(counts, cand_items, cap, n_rows, user_rows, h_user, ldu,
+                                      h_item, ldi, d, exclude_indptr, exclude_indices, k, out_vals,
+                                      out_idx, nullptr, nullptr, stream);
+}
+
+extern "C" int gnnrec_topk_candidates_rating_f32(
+    const int32_t* counts, const int32_t* cand_items, int64_t cap, int64_t n_rows,
+    const int64_t* user_rows, const float* h_user, int64_t ldu, const float* h_item, int64_t ldi,
+    int64_t d, const int64_t* exclude_indptr, const int32_t* exclude_indices, const float* Z,
+    const float* p, int64_t k, float* out_vals, int64_t* out_idx, void* stream) {
+  using namespace gnnrec;
+  GNNREC_REQUIRE(n_rows <= 0 || (Z && p), "gnnrec_topk_candidates_rating_f32: null Z / p");
+  return topk_candidates_impl(counts, cand_items, cap, n_rows, user_rows, h_user, ldu, h_item, ldi,
+                              d, exclude_indptr, exclude_indices, k, out_vals, out_idx, Z, p,
+                              stream);
+}
+
+extern "C" int gnnrec_score_bf16_store_rating(const void* users, int64_t n_users,
+                                              const void* items, int64_t n_items, int64_t dpad,
+                                              const float* Z, const float* p_col, float* out,
+                                              int64_t ldo, void* stream) {
+  using namespace gnnrec;
+  const char* fn = "gnnrec_score_bf16_store_rating";
+  const int rc = check_score_args(fn, users, n_users, items, n_items, dpad);
+  if (rc != GNNREC_OK || n_users == 0 || n_items == 0) return rc;
+  GNNREC_REQUIRE(out && ldo >= n_items, "%s: bad out / ldo", fn);
+  GNNREC_REQUIRE(Z && p_col, "%s: null Z / p_col", fn);
+  launch_score<false, true>(static_cast<const uint16_t*>(users), n_users,
+                            static_cast<const uint16_t*>(items), n_items, (int)dpad, out, ldo,
+                            nullptr, nullptr, nullptr, 0, as_stream(stream), Z, p_col);
+  return check_launch(fn);
+}
+
+extern "C" int gnnrec_score_bf16_filter_rating(const void* users, int64_t n_users,
+                                               const void* items, int64_t n_items, int64_t dpad,
+                                               const float* Z, const float* p_col,
+                                               const float* thr, int32_t* counts,
+                                               int32_t* cand_items, int64_t cap, void* stream) {
+  using namespace gnnrec;
+  const char* fn = "gnnrec_score_bf16_filter_rating";
+  const int rc = check_score_args(fn, users, n_users, items, n_items, dpad);
+  if (rc != GNNREC_OK) return rc;
+  GNNREC_REQUIRE(cap >= 1 && cap <= kCandMax, "%s: cap must be in [1, %d] (got %lld)", fn,
+                 kCandMax, (long long)cap);
+  if (n_users == 0 || n_items == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(Z && p_col && thr && counts && cand_items, "%s: null pointer", fn);
+  launch_score<true, true>(static_cast<const uint16_t*>(users), n_users,
+                           static_cast<const uint16_t*>(items), n_items, (int)dpad, nullptr, 0,
+                           thr, counts, cand_items, (int)cap, as_stream(stream), Z, p_col);
+  return check_launch(fn);
 }
 
 extern "C" int gnnrec_topk_scored_candidates_f32(const int32_t* counts, const int32_t* cand_items,

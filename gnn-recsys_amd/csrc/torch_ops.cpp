@@ -826,6 +826,304 @@ void topk_candidates_f32(const Tensor& counts, const Tensor& cand_items,
      "gnnrec_topk_candidates_f32");
 }
 
+// ---------------------------------------------------------------- f1d popularity ratings
+// a per-row / per-column fp32 vector of a rating launch: contiguous, n entries
+void rating_vec(const Tensor& t, const char* name, int64_t n) {
+  dev(t, name, at::kFloat);
+  TORCH_CHECK_VALUE(t.numel() == n && t.is_contiguous(), name, " must be contiguous [", n,
+                    "], got ", t.sizes());
+}
+
+void normalize_rows_f32(const Tensor& x, const optional<Tensor>& row_map, Tensor& out) {
+  const OneDevice one_device_;
+  dev(x, "x", at::kFloat);
+  dev(row_map, "row_map", at::kLong);
+  dev(out, "out", at::kFloat);
+  const int64_t ldx = ld(x, "x"), d = x.size(1);
+  const int64_t n = has(row_map) ? row_map->numel() : x.size(0);
+  const int64_t dpad = (d + 7) / 8 * 8;
+  TORCH_CHECK_VALUE(d >= 4 && d % 4 == 0 && d <= 2048 && ldx % 4 == 0,
+                    "x must have a multiple of 4 columns in [4, 2048] (and such a row stride), "
+                    "got ", x.sizes());
+  TORCH_CHECK_VALUE(out.dim() == 2 && out.size(0) == n && out.size(1) == dpad &&
+                        out.is_contiguous(),
+                    "out must be a contiguous [", n, ", ", dpad, "] (dpad = d rounded up to 8), "
+                    "got ", out.sizes());
+  TORCH_CHECK_VALUE(!has(row_map) || row_map->is_contiguous(), "row_map must be contiguous");
+  if (meta(x)) return;
+  const c10::DeviceGuard g(x.device());
+  ck(gnnrec_normalize_rows_f32(p<float>(x), ldx, n, d, p<int64_t>(row_map), p<float>(out), dpad,
+                               stream_of(x)),
+     "gnnrec_normalize_rows_f32");
+}
+
+void cos_denominators(const Tensor& users, const Tensor& items, Tensor& parts, Tensor& Z) {
+  const OneDevice one_device_;
+  dev(users, "users", at::kFloat);
+  dev(items, "items", at::kFloat);
+  dev(parts, "parts", at::kFloat);
+  dev(Z, "Z", at::kFloat);
+  TORCH_CHECK_VALUE(users.dim() == 2 && items.dim() == 2 && users.is_contiguous() &&
+                        items.is_contiguous(),
+                    "users / items must be contiguous 2-D fp32 tables");
+  const int64_t dpad = users.size(1), B = users.size(0), n = items.size(0);
+  TORCH_CHECK_VALUE(items.size(1) == dpad && dpad >= 8 && dpad % 8 == 0 && dpad <= 2048,
+                    "users / items must share a dpad that is a multiple of 8 in [8, 2048], got ",
+                    users.size(1), " and ", items.size(1));
+  const int64_t n_part = gnnrec_cos_denominator_parts(n);
+  TORCH_CHECK_VALUE(parts.numel() >= n_part * B && parts.is_contiguous(),
+                    "parts must hold ", n_part, " x ", B, " floats, got ", parts.sizes());
+  rating_vec(Z, "Z", B);
+  if (meta(users)) return;
+  const c10::DeviceGuard g(users.device());
+  ck(gnnrec_cos_denominators_f32(p<float>(users), B, p<float>(items), n, dpad, p<float>(parts),
+                                 p<float>(Z), stream_of(users)),
+     "gnnrec_cos_denominators_f32");
+}
+
+void exp_rowsum(const Tensor& scores, Tensor& Z) {
+  const OneDevice one_device_;
+  dev(scores, "scores", at::kFloat);
+  const int64_t lds = ld(scores, "scores"), n_rows = scores.size(0);
+  rating_vec(Z, "Z", n_rows);
+  if (meta(scores)) return;
+  const c10::DeviceGuard g(scores.device());
+  ck(gnnrec_exp_rowsum_f32(p<float>(scores), lds, n_rows, scores.size(1), p<float>(Z),
+                           stream_of(scores)),
+     "gnnrec_exp_rowsum_f32");
+}
+
+void rating_rows_(Tensor& scores, const Tensor& Z, const Tensor& pv) {
+  const OneDevice one_device_;
+  dev(scores, "scores", at::kFloat);
+  const int64_t lds = ld(scores, "scores"), n_rows = scores.size(0);
+  rating_vec(Z, "Z", n_rows);
+  rating_vec(pv, "p", scores.size(1));
+  if (meta(scores)) return;
+  const c10::DeviceGuard g(scores.device());
+  ck(gnnrec_rating_rows_f32(p<float>(scores), lds, n_rows, scores.size(1), p<float>(Z),
+                            p<float>(pv), stream_of(scores)),
+     "gnnrec_rating_rows_f32");
+}
+
+void rating_thresholds(const Tensor& tau, const Tensor& Z, const Tensor& pmax, Tensor& thr) {
+  const OneDevice one_device_;
+  const int64_t B = tau.numel();
+  rating_vec(tau, "tau", B);
+  rating_vec(Z, "Z", B);
+  rating_vec(pmax, "pmax", 1);
+  rating_vec(thr, "thr", B);
+  if (meta(tau)) return;
+  const c10::DeviceGuard g(tau.device());
+  ck(gnnrec_rating_thresholds_f32(p<float>(tau), p<float>(Z), p<float>(pmax), B, p<float>(thr),
+                                  stream_of(tau)),
+     "gnnrec_rating_thresholds_f32");
+}
+
+void mask_excluded_mapped_f32(Tensor& scores, const Tensor& col_ids,
+                              const optional<Tensor>& user_rows, const Tensor& exclude_indptr,
+                              const Tensor& exclude_indices) {
+  const OneDevice one_device_;
+  dev(scores, "scores", at::kFloat);
+  dev(col_ids, "col_ids", at::kInt);
+  dev(user_rows, "user_rows", at::kLong);
+  dev(exclude_indptr, "exclude_indptr", at::kLong);
+  dev(exclude_indices, "exclude_indices", at::kInt);
+  const int64_t lds = ld(scores, "scores"), n_rows = scores.size(0);
+  TORCH_CHECK_VALUE(col_ids.numel() == scores.size(1) && col_ids.is_contiguous(),
+                    "col_ids must be contiguous [", scores.size(1), "], got ", col_ids.sizes());
+  TORCH_CHECK_VALUE(!has(user_rows) || (user_rows->numel() == n_rows && user_rows->is_contiguous()),
+                    "user_rows must be contiguous [", n_rows, "]");
+  TORCH_CHECK_VALUE(exclude_indptr.is_contiguous() && exclude_indices.is_contiguous() &&
+                        exclude_indptr.numel() >= 1 &&
+                        (has(user_rows) || exclude_indptr.numel() > n_rows),
+                    "exclude_indptr must be a contiguous indptr over the user rows");
+  if (meta(scores)) return;
+  const c10::DeviceGuard g(scores.device());
+  ck(gnnrec_mask_excluded_mapped_f32(p<float>(scores), lds, n_rows, scores.size(1),
+                                     p<int32_t>(col_ids), p<int64_t>(user_rows),
+                                     p<int64_t>(exclude_indptr), p<int32_t>(exclude_indices),
+                                     stream_of(scores)),
+     "gnnrec_mask_excluded_mapped_f32");
+}
+
+void score_bf16_store_rating(const Tensor& users, const Tensor& items, const Tensor& Z,
+                             const Tensor& p_col, Tensor& out) {
+  const OneDevice one_device_;
+  const int64_t dpad = score_tables(users, items);
+  dev(out, "out", at::kFloat);
+  const int64_t B = users.size(0), n = items.size(0);
+  const int64_t ldo = ld(out, "out");
+  TORCH_CHECK_VALUE(out.size(0) == B && out.size(1) == n, "out must be [", B, ", ", n, "], got ",
+                    out.sizes());
+  rating_vec(Z, "Z", B);
+  rating_vec(p_col, "p_col", n);
+  if (meta(users)) return;
+  const c10::DeviceGuard g(users.device());
+  ck(gnnrec_score_bf16_store_rating(users.data_ptr(), B, items.data_ptr(), n, dpad, p<float>(Z),
+                                    p<float>(p_col), p<float>(out), ldo, stream_of(users)),
+     "gnnrec_score_bf16_store_rating");
+}
+
+void score_bf16_filter_rating(const Tensor& users, const Tensor& items, const Tensor& Z,
+                              const Tensor& p_col, const Tensor& thr, Tensor& counts,
+                              Tensor& cand_items) {
+  const OneDevice one_device_;
+  const int64_t dpad = score_tables(users, items);
+  dev(counts, "counts", at::kInt);
+  dev(cand_items, "cand_items", at::kInt);
+  const int64_t B = users.size(0), n = items.size(0);
+  rating_vec(Z, "Z", B);
+  rating_vec(p_col, "p_col", n);
+  rating_vec(thr, "thr", B);
+  TORCH_CHECK_VALUE(counts.numel() == B && counts.is_contiguous(),
+                    "counts must be contiguous [", B, "]");
+  TORCH_CHECK_VALUE(cand_items.dim() == 2 && cand_items.size(0) == B && cand_items.is_contiguous(),
+                    "cand_items must be a contiguous [", B, ", cap], got ", cand_items.sizes());
+  const int64_t cap = cand_items.size(1);
+  TORCH_CHECK_VALUE(cap >= 1 && cap <= 4096, "cand_items: cap must be in [1, 4096], got ", cap);
+  if (meta(users)) return;
+  const c10::DeviceGuard g(users.device());
+  ck(gnnrec_score_bf16_filter_rating(users.data_ptr(), B, items.data_ptr(), n, dpad, p<float>(Z),
+                                     p<float>(p_col), p<float>(thr), p<int32_t>(counts),
+                                     p<int32_t>(cand_items), cap, stream_of(users)),
+     "gnnrec_score_bf16_filter_rating");
+}
+
+void topk_candidates_rating_f32(const Tensor& counts, const Tensor& cand_items,
+                                const optional<Tensor>& user_rows, const Tensor& h_user,
+                                const Tensor& h_item, const optional<Tensor>& exclude_indptr,
+                                const optional<Tensor>& exclude_indices, const Tensor& Z,
+                                const Tensor& pv, int64_t k, Tensor& out_vals, Tensor& out_idx) {
+  const OneDevice one_device_;
+  dev(counts, "counts", at::kInt);
+  dev(cand_items, "cand_items", at::kInt);
+  dev(user_rows, "user_rows", at::kLong);
+  dev(h_user, "h_user", at::kFloat);
+  dev(h_item, "h_item", at::kFloat);
+  dev(exclude_indptr, "exclude_indptr", at::kLong);
+  dev(exclude_indices, "exclude_indices", at::kInt);
+  dev(out_vals, "out_vals", at::kFloat);
+  dev(out_idx, "out_idx", at::kLong);
+  const int64_t B = counts.numel();
+  TORCH_CHECK_VALUE(cand_items.dim() == 2 && cand_items.size(0) == B && cand_items.is_contiguous() &&
+                        counts.is_contiguous(),
+                    "cand_items must be a contiguous [", B, ", cap], got ", cand_items.sizes());
+  const int64_t cap = cand_items.size(1);
+  TORCH_CHECK_VALUE(cap >= 1 && cap <= 4096, "cand_items: cap must be in [1, 4096], got ", cap);
+  TORCH_CHECK_VALUE(k >= 1 && k <= cap, "k must be in [1, cap = ", cap, "], got ", k);
+  const int64_t ldu = ld(h_user, "h_user"), ldi = ld(h_item, "h_item"), d = h_user.size(1);
+  TORCH_CHECK_VALUE(h_item.size(1) == d && d >= 4 && d % 4 == 0 && ldu % 4 == 0 && ldi % 4 == 0,
+                    "h_user / h_item must share a feature size that is a multiple of 4 (and row "
+                    "strides too), got ", h_user.sizes(), " and ", h_item.sizes());
+  TORCH_CHECK_VALUE(!has(user_rows) || (user_rows->numel() == B && user_rows->is_contiguous()),
+                    "user_rows must be contiguous [", B, "]");
+  TORCH_CHECK_VALUE(has(user_rows) || h_user.size(0) >= B, "h_user has fewer rows than the batch");
+  TORCH_CHECK_VALUE(has(exclude_indptr) == has(exclude_indices),
+                    "exclude_indptr and exclude_indices come together");
+  TORCH_CHECK_VALUE(!has(exclude_indptr) ||
+                        (exclude_indptr->numel() == h_user.size(0) + 1 &&
+                         exclude_indptr->is_contiguous() && exclude_indices->is_contiguous()),
+                    "exclude_indptr must be a contiguous [n_user_rows + 1] over h_user's rows");
+  rating_vec(Z, "Z", B);
+  rating_vec(pv, "p", h_item.size(0));
+  TORCH_CHECK_VALUE(out_vals.numel() == B * k && out_idx.numel() == B * k &&
+                        out_vals.is_contiguous() && out_idx.is_contiguous(),
+                    "out_vals / out_idx must be contiguous [", B, ", ", k, "]");
+  if (meta(counts)) return;
+  const c10::DeviceGuard g(counts.device());
+  ck(gnnrec_topk_candidates_rating_f32(p<int32_t>(counts), p<int32_t>(cand_items), cap, B,
+                                       p<int64_t>(user_rows), p<float>(h_user), ldu,
+                                       p<float>(h_item), ldi, d, p<int64_t>(exclude_indptr),
+                                       p<int32_t>(exclude_indices), p<float>(Z), p<float>(pv), k,
+                                       p<float>(out_vals), p<int64_t>(out_idx), stream_of(counts)),
+     "gnnrec_topk_candidates_rating_f32");
+}
+
+void edge_mlp_dense_denominators(const Tensor& P, const Tensor& Q, const Tensor& W2,
+                                 const Tensor& b2, const Tensor& w3, const Tensor& b3,
+                                 Tensor& parts) {
+  const OneDevice one_device_;
+  dense_mlp_tables(P, Q, W2, b2, w3, b3);
+  dev(parts, "parts", at::kFloat);
+  const int64_t B = P.size(0), n = Q.size(0);
+  const int64_t n_part = gnnrec_cos_denominator_parts(n);
+  TORCH_CHECK_VALUE(parts.dim() == 2 && parts.size(0) == n_part && parts.size(1) == B &&
+                        parts.is_contiguous(),
+                    "parts must be a contiguous [", n_part, ", ", B, "], got ", parts.sizes());
+  if (meta(P)) return;
+  const c10::DeviceGuard g(P.device());
+  ck(gnnrec_edge_mlp_dense_denominators_f32(p<float>(P), B, p<float>(Q), n, p<float>(W2),
+                                            p<float>(b2), p<float>(w3), p<float>(b3),
+                                            p<float>(parts), stream_of(P)),
+     "gnnrec_edge_mlp_dense_denominators_f32");
+}
+
+void fold_partials_f32(const Tensor& parts, Tensor& Z) {
+  const OneDevice one_device_;
+  dev(parts, "parts", at::kFloat);
+  TORCH_CHECK_VALUE(parts.dim() == 2 && parts.is_contiguous(),
+                    "parts must be a contiguous [n_parts, n_rows], got ", parts.sizes());
+  rating_vec(Z, "Z", parts.size(1));
+  if (meta(parts)) return;
+  const c10::DeviceGuard g(parts.device());
+  ck(gnnrec_fold_partials_f32(p<float>(parts), parts.size(0), parts.size(1), p<float>(Z),
+                              stream_of(parts)),
+     "gnnrec_fold_partials_f32");
+}
+
+void edge_mlp_dense_store_rating(const Tensor& P, const Tensor& Q, const Tensor& W2,
+                                 const Tensor& b2, const Tensor& w3, const Tensor& b3,
+                                 const Tensor& Z, const Tensor& p_col, Tensor& out) {
+  const OneDevice one_device_;
+  dense_mlp_tables(P, Q, W2, b2, w3, b3);
+  dev(out, "out", at::kFloat);
+  const int64_t B = P.size(0), n = Q.size(0);
+  const int64_t ldo = ld(out, "out");
+  TORCH_CHECK_VALUE(out.size(0) == B && out.size(1) == n, "out must be [", B, ", ", n, "], got ",
+                    out.sizes());
+  rating_vec(Z, "Z", B);
+  rating_vec(p_col, "p_col", n);
+  if (meta(P)) return;
+  const c10::DeviceGuard g(P.device());
+  ck(gnnrec_edge_mlp_dense_store_rating_f32(p<float>(P), B, p<float>(Q), n, p<float>(W2),
+                                            p<float>(b2), p<float>(w3), p<float>(b3), p<float>(Z),
+                                            p<float>(p_col), p<float>(out), ldo, stream_of(P)),
+     "gnnrec_edge_mlp_dense_store_rating_f32");
+}
+
+void edge_mlp_dense_filter_rating(const Tensor& P, const Tensor& Q, const Tensor& W2,
+                                  const Tensor& b2, const Tensor& w3, const Tensor& b3,
+                                  const Tensor& Z, const Tensor& p_col, const Tensor& tau,
+                                  Tensor& counts, Tensor& cand_items, Tensor& cand_scores) {
+  const OneDevice one_device_;
+  dense_mlp_tables(P, Q, W2, b2, w3, b3);
+  dev(counts, "counts", at::kInt);
+  dev(cand_items, "cand_items", at::kInt);
+  dev(cand_scores, "cand_scores", at::kFloat);
+  const int64_t B = P.size(0), n = Q.size(0);
+  rating_vec(Z, "Z", B);
+  rating_vec(p_col, "p_col", n);
+  rating_vec(tau, "tau", B);
+  TORCH_CHECK_VALUE(counts.numel() == B && counts.is_contiguous(),
+                    "counts must be contiguous [", B, "]");
+  TORCH_CHECK_VALUE(cand_items.dim() == 2 && cand_items.size(0) == B && cand_items.is_contiguous(),
+                    "cand_items must be a contiguous [", B, ", cap], got ", cand_items.sizes());
+  const int64_t cap = cand_items.size(1);
+  TORCH_CHECK_VALUE(cap >= 1 && cap <= 4096, "cand_items: cap must be in [1, 4096], got ", cap);
+  TORCH_CHECK_VALUE(cand_scores.sizes() == cand_items.sizes() && cand_scores.is_contiguous(),
+                    "cand_scores must be a contiguous [", B, ", ", cap, "], got ",
+                    cand_scores.sizes());
+  if (meta(P)) return;
+  const c10::DeviceGuard g(P.device());
+  ck(gnnrec_edge_mlp_dense_filter_rating_f32(p<float>(P), B, p<float>(Q), n, p<float>(W2),
+                                             p<float>(b2), p<float>(w3), p<float>(b3),
+                                             p<float>(Z), p<float>(p_col), p<float>(tau),
+                                             p<int32_t>(counts), p<int32_t>(cand_items),
+                                             p<float>(cand_scores), cap, stream_of(P)),
+     "gnnrec_edge_mlp_dense_filter_rating_f32");
+}
+
 void topk_scored_candidates_f32(const Tensor& counts, const Tensor& cand_items,
                                 const Tensor& cand_scores, const optional<Tensor>& user_rows,
                                 const optional<Tensor>& exclude_indptr,
@@ -1814,6 +2112,7 @@ int64_t csr_build_workspace_bytes(int64_t E, int64_t n_dst) {
   const OneDevice one_device_;
   return (int64_t)gnnrec_csr_build_workspace_bytes(E, n_dst);
 }
+int64_t cos_denominator_parts(int64_t n_items) { return gnnrec_cos_denominator_parts(n_items); }
 int64_t csr_remove_edges_workspace_bytes(int64_t E, int64_t n_dst) {
   return (int64_t)gnnrec_csr_remove_edges_workspace_bytes(E, n_dst);
 }
@@ -1899,6 +2198,28 @@ TORCH_LIBRARY(gnnrec, m) {
   m.def("topk_candidates_f32(Tensor counts, Tensor cand_items, Tensor? user_rows, Tensor h_user, "
         "Tensor h_item, Tensor? exclude_indptr, Tensor? exclude_indices, int k, "
         "Tensor(a!) out_vals, Tensor(b!) out_idx) -> ()");
+  m.def("edge_mlp_dense_denominators_f32(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, "
+        "Tensor b3, Tensor(a!) parts) -> ()");
+  m.def("fold_partials_f32(Tensor parts, Tensor(a!) Z) -> ()");
+  m.def("edge_mlp_dense_store_rating_f32(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, "
+        "Tensor b3, Tensor Z, Tensor p_col, Tensor(a!) out) -> ()");
+  m.def("edge_mlp_dense_filter_rating_f32(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, "
+        "Tensor b3, Tensor Z, Tensor p_col, Tensor tau, Tensor(a!) counts, "
+        "Tensor(b!) cand_items, Tensor(c!) cand_scores) -> ()");
+  m.def("normalize_rows_f32(Tensor x, Tensor? row_map, Tensor(a!) out) -> ()");
+  m.def("cos_denominators_f32(Tensor users, Tensor items, Tensor(a!) parts, Tensor(b!) Z) -> ()");
+  m.def("exp_rowsum_f32(Tensor scores, Tensor(a!) Z) -> ()");
+  m.def("rating_rows_f32(Tensor(a!) scores, Tensor Z, Tensor p) -> ()");
+  m.def("rating_thresholds_f32(Tensor tau, Tensor Z, Tensor pmax, Tensor(a!) thr) -> ()");
+  m.def("mask_excluded_mapped_f32(Tensor(a!) scores, Tensor col_ids, Tensor? user_rows, "
+        "Tensor exclude_indptr, Tensor exclude_indices) -> ()");
+  m.def("score_bf16_store_rating(Tensor users, Tensor items, Tensor Z, Tensor p_col, "
+        "Tensor(a!) out) -> ()");
+  m.def("score_bf16_filter_rating(Tensor users, Tensor items, Tensor Z, Tensor p_col, "
+        "Tensor thr, Tensor(a!) counts, Tensor(b!) cand_items) -> ()");
+  m.def("topk_candidates_rating_f32(Tensor counts, Tensor cand_items, Tensor? user_rows, "
+        "Tensor h_user, Tensor h_item, Tensor? exclude_indptr, Tensor? exclude_indices, "
+        "Tensor Z, Tensor p, int k, Tensor(a!) out_vals, Tensor(b!) out_idx) -> ()");
   m.def("gemm_tn(Tensor A, Tensor B, Tensor(b!)? colsum, bool accumulate, Tensor(a!) out, "
         "Tensor(c!) workspace, Tensor? row_ptr=None) -> ()");
   m.def("act_backward(Tensor u, Tensor gz, int flags, Tensor(a!) out) -> ()");
@@ -1977,6 +2298,7 @@ TORCH_LIBRARY(gnnrec, m) {
   m.def("csr_from_keys_workspace_bytes(int n_edges, int n_rows) -> int",
         &csr_from_keys_workspace_bytes);
   m.def("csr_build_workspace_bytes(int n_edges, int n_dst) -> int", &csr_build_workspace_bytes);
+  m.def("cos_denominator_parts(int n_items) -> int", &cos_denominator_parts);
   m.def("csr_remove_edges_workspace_bytes(int n_edges, int n_dst) -> int",
         &csr_remove_edges_workspace_bytes);
   m.def("sddmm_cos_backward_workspace_bytes(int n_edges, int n_src, int n_dst, int d, "
@@ -2012,6 +2334,19 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("score_bf16_filter", &score_bf16_filter);       \
   m.impl("mask_excluded_f32", &mask_excluded_f32);       \
   m.impl("topk_candidates_f32", &topk_candidates_f32);   \
+  m.impl("edge_mlp_dense_denominators_f32", &edge_mlp_dense_denominators); \
+  m.impl("fold_partials_f32", &fold_partials_f32);       \
+  m.impl("edge_mlp_dense_store_rating_f32", &edge_mlp_dense_store_rating); \
+  m.impl("edge_mlp_dense_filter_rating_f32", &edge_mlp_dense_filter_rating); \
+  m.impl("normalize_rows_f32", &normalize_rows_f32);     \
+  m.impl("cos_denominators_f32", &cos_denominators);         \
+  m.impl("exp_rowsum_f32", &exp_rowsum);                     \
+  m.impl("rating_rows_f32", &rating_rows_);                 \
+  m.impl("rating_thresholds_f32", &rating_thresholds);       \
+  m.impl("mask_excluded_mapped_f32", &mask_excluded_mapped_f32); \
+  m.impl("score_bf16_store_rating", &score_bf16_store_rating); \
+  m.impl("score_bf16_filter_rating", &score_bf16_filter_rating); \
+  m.impl("topk_candidates_rating_f32", &topk_candidates_rating_f32); \
   m.impl("gemm_tn", &gemm_tn);                           \
   m.impl("act_backward", &act_backward);                 \
   m.impl("act_backward_normed", &act_backward_normed);   \

@@ -165,6 +165,25 @@ SIGNATURES = {
                                           _P, _I64, _P, _P, _P]),
     "gnnrec_topk_scored_candidates_f32": (_INT, [_P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _P,
                                                  _P, _P]),
+    # popularity-weighted ratings (csrc/recommend_pop.hip, csrc/recommend.hip)
+    "gnnrec_normalize_rows_f32": (_INT, [_P, _I64, _I64, _I64, _P, _P, _I64, _P]),
+    "gnnrec_cos_denominator_parts": (_I64, [_I64]),
+    "gnnrec_cos_denominators_f32": (_INT, [_P, _I64, _P, _I64, _I64, _P, _P, _P]),
+    "gnnrec_fold_partials_f32": (_INT, [_P, _I64, _I64, _P, _P]),
+    "gnnrec_edge_mlp_dense_denominators_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "gnnrec_edge_mlp_dense_store_rating_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P,
+                                                      _P, _I64, _P]),
+    "gnnrec_edge_mlp_dense_filter_rating_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P,
+                                                       _P, _P, _P, _P, _I64, _P]),
+    "gnnrec_exp_rowsum_f32": (_INT, [_P, _I64, _I64, _I64, _P, _P]),
+    "gnnrec_rating_rows_f32": (_INT, [_P, _I64, _I64, _I64, _P, _P, _P]),
+    "gnnrec_rating_thresholds_f32": (_INT, [_P, _P, _P, _I64, _P, _P]),
+    "gnnrec_mask_excluded_mapped_f32": (_INT, [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
+    "gnnrec_score_bf16_store_rating": (_INT, [_P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P]),
+    "gnnrec_score_bf16_filter_rating": (_INT, [_P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P,
+                                               _I64, _P]),
+    "gnnrec_topk_candidates_rating_f32": (_INT, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _I64,
+                                                 _I64, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "gnnrec_synth_edges": (_INT, [_U64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     "gnnrec_margin_loss_blocks": (_I64, [_I64]),
     "gnnrec_margin_loss_f32": (_INT, [_P, _P, _I64, _I64, _F32, _P, _P, _INT, _P, _P, _P, _I64,

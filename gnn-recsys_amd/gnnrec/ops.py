@@ -1896,3 +1896,172 @@ def topk_scored_candidates(counts: torch.Tensor, cand_items: torch.Tensor,
     _T().topk_scored_candidates_f32(counts, cand_items, cand_scores, user_rows, exclude_indptr,
                                     exclude_indices, int(k), out_vals, out_idx)
     return out_vals, out_idx
+
+
+# ---- f1d: popularity-weighted ratings (csrc/rating.hpp, recommend_pop.hip) ----
+def denominator_parts(n_items: int) -> int:
+    """Partial sums the item axis is cut into for the rating's denominators: a function of
+    n_items alone (1024 consecutive items each)."""
+    return int(_T().cos_denominator_parts(int(n_items)))
+
+
+def normalize_rows_f32(x: torch.Tensor, row_map: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Rows of x (row_map[r] of x when given) divided by max(norm, 1e-12) in fp32 — the values
+    normalize_rows_bf16 rounds — -> [n, dpad], dpad = d rounded up to a multiple of 8 (the
+    pad zero), each group of 8 columns stored as [0, 2, 4, 6, 1, 3, 5, 7]: the operand
+    layout of cos_denominators.  d % 4 == 0, 4 <= d <= 2048."""
+    _dev(x, "x", torch.float32)
+    _rowmajor(x, "x")
+    if row_map is not None:
+        _dev(row_map, "row_map", torch.int64)
+        row_map = row_map.contiguous()
+    n = x.shape[0] if row_map is None else row_map.numel()
+    out = torch.empty((n, (x.shape[1] + 7) // 8 * 8), dtype=torch.float32, device=x.device)
+    _T().normalize_rows_f32(x, row_map, out)
+    return out
+
+
+def cos_denominators(users: torch.Tensor, items: torch.Tensor) -> torch.Tensor:
+    """Z[u] = sum over all items v of expf(users[u] . items[v]) for two normalize_rows_f32
+    tables (fp32 MFMA) -> fp32 [n_users].  A row's Z has the same bits whatever batch it is
+    computed in: the item axis is cut by n_items alone and every fold has a fixed order."""
+    _dev(users, "users", torch.float32)
+    _dev(items, "items", torch.float32)
+    B = users.shape[0]
+    parts = torch.empty((denominator_parts(items.shape[0]), B), dtype=torch.float32,
+                        device=users.device)
+    Z = torch.empty(B, dtype=torch.float32, device=users.device)
+    _T().cos_denominators_f32(users, items, parts, Z)
+    return Z
+
+
+def exp_rowsum(scores: torch.Tensor) -> torch.Tensor:
+    """Z[r] = sum over the columns of expf(scores[r][c]), in a fixed order -> fp32 [n_rows]."""
+    _dev(scores, "scores", torch.float32)
+    Z = torch.empty(scores.shape[0], dtype=torch.float32, device=scores.device)
+    _T().exp_rowsum_f32(scores, Z)
+    return Z
+
+
+def rating_rows_(scores: torch.Tensor, Z: torch.Tensor, p: torch.Tensor) -> torch.Tensor:
+    """scores[r][c] = expf(scores[r][c]) / Z[r] + p[c] in place (the rating of rating.hpp)."""
+    _dev(scores, "scores", torch.float32)
+    _dev(Z, "Z", torch.float32)
+    _dev(p, "p", torch.float32)
+    _T().rating_rows_f32(scores, Z, p)
+    return scores
+
+
+def rating_thresholds(tau: torch.Tensor, Z: torch.Tensor, pmax: torch.Tensor) -> torch.Tensor:
+    """tau[u] - 2 delta_u rounded down, delta_u = REC_RATING_BAND / Z[u] + 2^-22 |pmax|: the
+    rating filter's per-row thresholds (pmax: a one-element tensor, the largest p)."""
+    _dev(tau, "tau", torch.float32)
+    _dev(Z, "Z", torch.float32)
+    _dev(pmax, "pmax", torch.float32)
+    thr = torch.empty_like(tau)
+    _T().rating_thresholds_f32(tau, Z, pmax, thr)
+    return thr
+
+
+def mask_excluded_mapped(scores: torch.Tensor, col_ids: torch.Tensor,
+                         user_rows: Optional[torch.Tensor], exclude_indptr: torch.Tensor,
+                         exclude_indices: torch.Tensor) -> None:
+    """mask_excluded for a table whose column c stands for item col_ids[c] (int32, strictly
+    ascending): the row's excluded items that are among the columns become -inf."""
+    _dev(scores, "scores", torch.float32)
+    _dev(col_ids, "col_ids", torch.int32)
+    _dev(exclude_indptr, "exclude_indptr", torch.int64)
+    _dev(exclude_indices, "exclude_indices", torch.int32)
+    _T().mask_excluded_mapped_f32(scores, col_ids, user_rows, exclude_indptr, exclude_indices)
+
+
+def score_bf16_store_rating(users: torch.Tensor, items: torch.Tensor, Z: torch.Tensor,
+                            p_col: torch.Tensor) -> torch.Tensor:
+    """score_bf16_store with Ra = expf(a) / Z[u] + p_col[c] written instead of a."""
+    _dev(users, "users", torch.bfloat16)
+    _dev(items, "items", torch.bfloat16)
+    _dev(Z, "Z", torch.float32)
+    _dev(p_col, "p_col", torch.float32)
+    out = torch.empty((users.shape[0], items.shape[0]), dtype=torch.float32, device=users.device)
+    _T().score_bf16_store_rating(users, items, Z, p_col, out)
+    return out
+
+
+def score_bf16_filter_rating(users: torch.Tensor, items: torch.Tensor, Z: torch.Tensor,
+                             p_col: torch.Tensor, thr: torch.Tensor, counts: torch.Tensor,
+                             cand_items: torch.Tensor) -> None:
+    """score_bf16_filter with Ra compared: item v joins row u's list where
+    Ra(u, v) >= thr[u] (rating_thresholds', compared as they are)."""
+    _dev(users, "users", torch.bfloat16)
+    _dev(items, "items", torch.bfloat16)
+    for t, n in ((Z, "Z"), (p_col, "p_col"), (thr, "thr")):
+        _dev(t, n, torch.float32)
+    _dev(counts, "counts", torch.int32)
+    _dev(cand_items, "cand_items", torch.int32)
+    _T().score_bf16_filter_rating(users, items, Z, p_col, thr, counts, cand_items)
+
+
+def topk_candidates_rating(counts: torch.Tensor, cand_items: torch.Tensor,
+                           user_rows: Optional[torch.Tensor], h_user: torch.Tensor,
+                           h_item: torch.Tensor, Z: torch.Tensor, p: torch.Tensor, k: int,
+                           exclude_indptr: Optional[torch.Tensor] = None,
+                           exclude_indices: Optional[torch.Tensor] = None,
+                           out_vals: Optional[torch.Tensor] = None,
+                           out_idx: Optional[torch.Tensor] = None):
+    """topk_candidates ranking by R = expf(cosine) / Z[r] + p[item] (Z per batch row, p per
+    item); vals are the R values."""
+    _dev(counts, "counts", torch.int32)
+    _dev(cand_items, "cand_items", torch.int32)
+    _dev(h_user, "h_user", torch.float32)
+    _dev(h_item, "h_item", torch.float32)
+    _dev(Z, "Z", torch.float32)
+    _dev(p, "p", torch.float32)
+    B = counts.numel()
+    if out_vals is None:
+        out_vals = torch.empty((B, k), dtype=torch.float32, device=counts.device)
+    if out_idx is None:
+        out_idx = torch.empty((B, k), dtype=torch.int64, device=counts.device)
+    _T().topk_candidates_rating_f32(counts, cand_items, user_rows, h_user, h_item, exclude_indptr,
+                                    exclude_indices, Z, p, int(k), out_vals, out_idx)
+    return out_vals, out_idx
+
+
+def edge_mlp_dense_denominators(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor,
+                                b2: torch.Tensor, w3: torch.Tensor,
+                                b3: torch.Tensor) -> torch.Tensor:
+    """Z[u] = sum over all item rows of Q of expf(score(u, v)), score the value of
+    edge_mlp_dense_store, nothing else written -> fp32 [B]; the same bits for a row whatever
+    batch it is computed in."""
+    ops = _dense_mlp_operands(P, Q, W2, b2, w3, b3)
+    B = P.shape[0]
+    parts = torch.empty((denominator_parts(Q.shape[0]), B), dtype=torch.float32, device=P.device)
+    Z = torch.empty(B, dtype=torch.float32, device=P.device)
+    _T().edge_mlp_dense_denominators_f32(*ops, parts)
+    _T().fold_partials_f32(parts, Z)
+    return Z
+
+
+def edge_mlp_dense_store_rating(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor,
+                                b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor,
+                                Z: torch.Tensor, p_col: torch.Tensor) -> torch.Tensor:
+    """edge_mlp_dense_store with R = expf(score) / Z[u] + p_col[v] written instead."""
+    ops = _dense_mlp_operands(P, Q, W2, b2, w3, b3)
+    _dev(Z, "Z", torch.float32)
+    _dev(p_col, "p_col", torch.float32)
+    out = torch.empty((P.shape[0], Q.shape[0]), dtype=torch.float32, device=P.device)
+    _T().edge_mlp_dense_store_rating_f32(*ops, Z, p_col, out)
+    return out
+
+
+def edge_mlp_dense_filter_rating(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor,
+                                 b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor,
+                                 Z: torch.Tensor, p_col: torch.Tensor, tau: torch.Tensor,
+                                 counts: torch.Tensor, cand_items: torch.Tensor,
+                                 cand_scores: torch.Tensor) -> None:
+    """edge_mlp_dense_filter with R compared (no band) and kept in cand_scores."""
+    ops = _dense_mlp_operands(P, Q, W2, b2, w3, b3)
+    for t, n in ((Z, "Z"), (p_col, "p_col"), (tau, "tau"), (cand_scores, "cand_scores")):
+        _dev(t, n, torch.float32)
+    _dev(counts, "counts", torch.int32)
+    _dev(cand_items, "cand_items", torch.int32)
+    _T().edge_mlp_dense_filter_rating_f32(*ops, Z, p_col, tau, counts, cand_items, cand_scores)

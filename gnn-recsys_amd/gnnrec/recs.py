@@ -20,6 +20,7 @@ the MLP head's score instead, exactly and again without a score matrix (DESIGN.m
 """
 from __future__ import annotations
 
+import math
 from collections import defaultdict
 
 import numpy as np
@@ -116,12 +117,26 @@ def get_recs(g, h, model, embed_dim, k, user_ids, already_bought_dict,
 REC_EPS = 2.0 ** -7 + 2.0 ** -11
 REC_MAX_D = 2048
 REC_MAX_CAP = 4096
+# |Ra - R| <= REC_RATING_BAND / Z_u + REC_RATING_SLACK max(p) for the rating R = expf(score) /
+# Z_u + p_v and its approximation Ra from the bf16 score (csrc/recommend.hip, THE RATING BAND;
+# DESIGN.md §19): e^(1 + eps) ((e^eps - 1) + 2^-20) and 2^-22, the library's constants.
+REC_RATING_BAND = math.exp(1.0 + REC_EPS) * (math.expm1(REC_EPS) + 2.0 ** -20)
+REC_RATING_SLACK = 2.0 ** -22
 
 
-def _rows_exact(h_user, h_item, k, rows, exclude, vals, idx, out_pos):
+def _to_ratings(sc, c0, rating):
+    """A chunk of exhaustive score rows to ratings in place; rating = (Z over the rows or
+    None, p): without Z the denominators are summed from the score rows themselves."""
+    Z, p = rating
+    Zc = ops.exp_rowsum(sc) if Z is None else Z[c0:c0 + sc.shape[0]].contiguous()
+    ops.rating_rows_(sc, Zc, p)
+
+
+def _rows_exact(h_user, h_item, k, rows, exclude, vals, idx, out_pos, rating=None):
     """The fallback, always exact: every item scored with the fp32 cosine for the user rows
     `rows` (int64 device tensor), excluded items masked to -inf, topk_rows; results into
-    vals/idx at rows `out_pos`."""
+    vals/idx at rows `out_pos`.  rating = (Z [len(rows)] or None, p [n_items]): the score rows
+    become R = expf(score) / Z + p first (Z None: summed from the rows, g = the score)."""
     n_items, dev = h_item.shape[0], h_item.device
     if rows.numel() == 0:
         return
@@ -141,6 +156,8 @@ def _rows_exact(h_user, h_item, k, rows, exclude, vals, idx, out_pos):
         else:
             sc = ops.sddmm_cos(r.repeat_interleave(n_items), dst, h_user, h_item)
         sc = sc.view(G, n_items)
+        if rating is not None:
+            _to_ratings(sc, c0, rating)
         if exclude is not None:
             ops.mask_excluded(sc, r, exclude[0], exclude[1])
         v, i = topk_rows(sc, k)
@@ -180,10 +197,21 @@ class _MlpHead:
     def filter(self, P, tau, counts, cand_items, cand_scores):
         ops.edge_mlp_dense_filter(P, self.Q, *self.tail, tau, counts, cand_items, cand_scores)
 
+    # the rating forms (popularity): Z over all items, R of a sample table, the R filter
+    def denominators(self, P):
+        return ops.edge_mlp_dense_denominators(P, self.Q, *self.tail)
 
-def _rows_exact_mlp(mlp, n_items, k, rows, exclude, vals, idx, out_pos):
+    def store_rating(self, P, Q_cols, Z, p_col):
+        return ops.edge_mlp_dense_store_rating(P, Q_cols, *self.tail, Z, p_col)
+
+    def filter_rating(self, P, Z, p, tau, counts, cand_items, cand_scores):
+        ops.edge_mlp_dense_filter_rating(P, self.Q, *self.tail, Z, p, tau, counts, cand_items,
+                                         cand_scores)
+
+
+def _rows_exact_mlp(mlp, n_items, k, rows, exclude, vals, idx, out_pos, rating=None):
     """_rows_exact for the MLP head: the dense store of `rows` over all items, in chunks of
-    2^26 / n_items rows, excluded items masked to -inf, topk_rows."""
+    2^26 / n_items rows, excluded items masked to -inf, topk_rows.  rating: as _rows_exact."""
     if rows.numel() == 0:
         return
     if n_items == 0:
@@ -194,6 +222,8 @@ def _rows_exact_mlp(mlp, n_items, k, rows, exclude, vals, idx, out_pos):
     for c0 in range(0, rows.numel(), step):
         r = rows[c0:c0 + step].contiguous()
         sc = mlp.store(mlp.P(r))
+        if rating is not None:
+            _to_ratings(sc, c0, rating)
         if exclude is not None:
             ops.mask_excluded(sc, r, exclude[0], exclude[1])
         v, i = topk_rows(sc, k)
@@ -203,8 +233,121 @@ def _rows_exact_mlp(mlp, n_items, k, rows, exclude, vals, idx, out_pos):
         idx[pos] = i
 
 
+def _popularity_vector(popularity, weight_popularity, n_items):
+    """p = popularity * weight as fp32 [n_items] (one fp32 multiply per item, once per call)."""
+    if not isinstance(popularity, torch.Tensor):
+        raise ValueError('popularity must be a fp32 device tensor')
+    ops._dev(popularity, 'popularity', torch.float32)
+    if popularity.dim() > 2 or (popularity.dim() == 2 and popularity.shape[1] != 1) or \
+            popularity.numel() != n_items:
+        raise ValueError(f'popularity must be [n_items] or [n_items, 1] with n_items = '
+                         f'{n_items}, got {tuple(popularity.shape)}')
+    return (popularity.reshape(-1) * float(weight_popularity)).contiguous()
+
+
+def _popular_sample(p, m, pop_sample):
+    """The threshold sample's item ids, ascending (int32): the prefix [0, m) and the
+    pop_sample items of largest p outside it, ties by id."""
+    n, dev = p.numel(), p.device
+    ids = torch.arange(m, device=dev)
+    extra = min(int(pop_sample), n - m)
+    if extra > 0:
+        order = torch.sort(p[m:], descending=True, stable=True).indices[:extra] + m
+        ids = torch.cat((ids, torch.sort(order).values))
+    return ids.to(torch.int32)
+
+
+def _recommend_pop(h_user, h_item, k, user_rows, exclude, batch_size, m, cand_cap, head, p,
+                   pop_sample, stats, vals, idx):
+    """recommend() ranking by R(u, v) = expf(score(u, v)) / Z_u + p_v."""
+    dev = h_item.device
+    n_items, d = h_item.shape
+    U = user_rows.numel()
+    all_pos = torch.arange(U, device=dev)
+    ex0 = None if exclude is None else exclude[0]
+    ex1 = None if exclude is None else exclude[1]
+    mfma = d % 4 == 0 and 4 <= d <= REC_MAX_D      # the widths of the denominator kernel
+    if U == 0 or n_items == 0:   # nothing to rate: the padding of the exhaustive path
+        if head is not None:
+            _rows_exact_mlp(_MlpHead(head, h_user, h_item), n_items, k, user_rows, exclude, vals,
+                            idx, all_pos)
+        else:
+            _rows_exact(h_user, h_item, k, user_rows, exclude, vals, idx, all_pos)
+        return
+    fast = k <= cand_cap // 4 and (head is not None or mfma)
+    Z = torch.empty(U, dtype=torch.float32, device=dev)
+    if head is not None:
+        mlp = _MlpHead(head, h_user, h_item)
+    elif mfma:
+        items_f32 = ops.normalize_rows_f32(h_item)       # converted once per call
+    if not fast:
+        if head is not None:
+            for b0 in range(0, U, batch_size):
+                Z[b0:b0 + batch_size] = mlp.denominators(mlp.P(user_rows[b0:b0 + batch_size]))
+            _rows_exact_mlp(mlp, n_items, k, user_rows, exclude, vals, idx, all_pos, (Z, p))
+        elif mfma:
+            for b0 in range(0, U, batch_size):
+                users_f32 = ops.normalize_rows_f32(h_user, user_rows[b0:b0 + batch_size])
+                Z[b0:b0 + batch_size] = ops.cos_denominators(users_f32, items_f32)
+            _rows_exact(h_user, h_item, k, user_rows, exclude, vals, idx, all_pos, (Z, p))
+        else:  # Z from the exhaustive score rows: g is the score itself
+            _rows_exact(h_user, h_item, k, user_rows, exclude, vals, idx, all_pos, (None, p))
+        return
+    stats['fast_path'] = True
+    col_ids = _popular_sample(p, m, pop_sample)            # chosen once per call
+    cols = col_ids.to(torch.int64)
+    p_col = p[cols].contiguous()
+    pmax = p.max().reshape(1)
+    stats['pop_sample'] = int(col_ids.numel()) - m
+    counts = torch.zeros(U, dtype=torch.int32, device=dev)
+    if head is None:
+        items_bf = ops.normalize_rows_bf16(h_item)
+        sample_bf = items_bf[cols].contiguous()
+    else:
+        sample_Q = mlp.Q[cols].contiguous()
+    for b0 in range(0, U, batch_size):
+        rows = user_rows[b0:b0 + batch_size]
+        B = rows.numel()
+        cand = torch.empty((B, cand_cap), dtype=torch.int32, device=dev)
+        if head is None:
+            Zb = ops.cos_denominators(ops.normalize_rows_f32(h_user, rows), items_f32)
+            users_bf = ops.normalize_rows_bf16(h_user, rows)
+            s = ops.score_bf16_store_rating(users_bf, sample_bf, Zb, p_col)
+        else:
+            P = mlp.P(rows)
+            Zb = mlp.denominators(P)
+            s = mlp.store_rating(P, sample_Q, Zb, p_col)
+        Z[b0:b0 + B] = Zb
+        if exclude is not None:
+            ops.mask_excluded_mapped(s, col_ids, rows, ex0, ex1)
+        tau = topk_rows(s, k)[0][:, k - 1].contiguous()  # -inf: fewer than k eligible there
+        del s
+        if head is None:
+            thr = ops.rating_thresholds(tau, Zb, pmax)     # tau - 2 delta_u, once per batch
+            ops.score_bf16_filter_rating(users_bf, items_bf, Zb, p, thr, counts[b0:b0 + B], cand)
+            ops.topk_candidates_rating(counts[b0:b0 + B], cand, rows, h_user, h_item, Zb, p, k,
+                                       ex0, ex1, vals[b0:b0 + B], idx[b0:b0 + B])
+        else:
+            cand_sc = torch.empty((B, cand_cap), dtype=torch.float32, device=dev)
+            mlp.filter_rating(P, Zb, p, tau, counts[b0:b0 + B], cand, cand_sc)
+            ops.topk_scored_candidates(counts[b0:b0 + B], cand, cand_sc, k, rows, ex0, ex1,
+                                       vals[b0:b0 + B], idx[b0:b0 + B])
+    cnt = counts.cpu().numpy()                       # the call's one readback
+    over = np.nonzero(cnt > cand_cap)[0]
+    if over.size:
+        pos = torch.from_numpy(over).to(dev)
+        if head is None:
+            _rows_exact(h_user, h_item, k, user_rows[pos], exclude, vals, idx, pos, (Z[pos], p))
+        else:
+            _rows_exact_mlp(mlp, n_items, k, user_rows[pos], exclude, vals, idx, pos,
+                            (Z[pos], p))
+    stats.update(candidates_mean=float(cnt.mean()), candidates_max=int(cnt.max()),
+                 overflow_rows=int(over.size))
+
+
 def recommend(h_user, h_item, k, user_rows=None, exclude=None, *, batch_size=8192,
-              sample=65536, cand_cap=1024, return_stats=False, head=None):
+              sample=65536, cand_cap=1024, return_stats=False, head=None, popularity=None,
+              weight_popularity=1.0, pop_sample=4096):
     """The k best items per user by (cosine desc, item id asc), excluded items removed —
     the lists of an exhaustive fp32 ranking, bit for bit — on device tensors and without a
     score matrix.
@@ -244,12 +387,31 @@ def recommend(h_user, h_item, k, user_rows=None, exclude=None, *, batch_size=819
     at the k-th value) is kept.  Rows that kept more than cand_cap items — a saturated head,
     whose scores are 1.0f for many items, does that — and the whole call when
     k > cand_cap / 4 are recomputed exhaustively (dense scores of the rows over all items in
-    chunks of 2^26 / n_items rows, topk_rows).  use_popularity is not offered here:
-    softmax(scores) + w popularity needs each row's full denominator, and get_recs remains
-    the path for it.  Non-finite scores are outside the contract, as for the cosine.
+    chunks of 2^26 / n_items rows, topk_rows).  Non-finite scores are outside the contract,
+    as for the cosine.
+
+    popularity: None ranks by the score, as above (that code path is untouched).  A fp32
+    device tensor [n_items] or [n_items, 1] (the reference's g.ndata['popularity']['item'])
+    ranks by the reference's use_popularity rating instead (src/metrics.py:69-72), for either
+    head, still exactly and without a score matrix:
+        R(u, v) = expf(score(u, v)) / Z_u + popularity[v] * weight_popularity,
+    Z_u the sum of expf over ALL items (excluded ones too: the reference removes bought items
+    after the softmax), each operation rounded once in fp32; vals are the R values.  Z_u is
+    bitwise the same for a user whatever the batch size, the order of user_rows or the run: a
+    fixed-order reduction (for the cosine head on the fp32 MFMA over the fp32-normalised
+    tables, for the MLP head a denominator pass of the dense kernel).  The threshold sample is
+    the item prefix plus the `pop_sample` items of largest popularity * weight outside it
+    (ties by id) — with the reference's weights the best ratings are the popular items', and a
+    tau taken from a prefix without them keeps every popular item for every row.  The cosine
+    filter keeps the items with Ra >= tau - 2 delta_u, Ra the rating of the bf16 score and
+    delta_u = REC_RATING_BAND / Z_u + REC_RATING_SLACK max(p) the bound on |Ra - R|; the MLP
+    filter compares the final R, without a band.  Overflowed rows, k > cand_cap / 4 and (for
+    the cosine head) d % 4 != 0 or d > REC_MAX_D take the exhaustive path: score rows, the
+    same R of the same Z, topk_rows (for those widths Z is summed from the score rows).
 
     stats (return_stats=True): candidates_mean, candidates_max (kept items per row, counted
-    past the cap), overflow_rows, sample, cand_cap, fast_path."""
+    past the cap), overflow_rows, sample, cand_cap, fast_path; with popularity also
+    pop_sample (the items added to the sample)."""
     ops._dev(h_user, 'h_user', torch.float32)
     ops._dev(h_item, 'h_item', torch.float32)
     if h_user.dim() != 2 or h_item.dim() != 2 or h_user.shape[1] != h_item.shape[1]:
@@ -262,6 +424,10 @@ def recommend(h_user, h_item, k, user_rows=None, exclude=None, *, batch_size=819
     dev = h_item.device
     h_user, h_item = h_user.contiguous(), h_item.contiguous()
     n_items, d = h_item.shape
+    if popularity is not None:   # refused before any launch
+        if int(pop_sample) < 0:
+            raise ValueError('recommend: pop_sample must be >= 0')
+        p = _popularity_vector(popularity, weight_popularity, n_items)
     if user_rows is None:
         user_rows = torch.arange(h_user.shape[0], device=dev)
     ops._dev(user_rows, 'user_rows', torch.int64)
@@ -280,6 +446,11 @@ def recommend(h_user, h_item, k, user_rows=None, exclude=None, *, batch_size=819
     m = min(sample, n_items)
     stats = {'candidates_mean': 0.0, 'candidates_max': 0, 'overflow_rows': 0, 'sample': m,
              'cand_cap': cand_cap, 'fast_path': False}
+    if popularity is not None:
+        stats['pop_sample'] = 0
+        _recommend_pop(h_user, h_item, k, user_rows, exclude, batch_size, m, cand_cap, head, p,
+                       pop_sample, stats, vals, idx)
+        return (idx, vals, stats) if return_stats else (idx, vals)
     if head is not None:
         mlp = _MlpHead(head, h_user, h_item)
         all_pos = torch.arange(U, device=dev)
@@ -346,12 +517,23 @@ def recommend(h_user, h_item, k, user_rows=None, exclude=None, *, batch_size=819
     return (idx, vals, stats) if return_stats else (idx, vals)
 
 
-def recommend_for_graph(g, h, k, user_ids=None, etype='bought-by', **kw):
+def recommend_for_graph(g, h, k, user_ids=None, etype='bought-by', use_popularity=False,
+                        weight_popularity=1, **kw):
     """recommend() for the users of a graph, the items each has an `etype` edge from
     removed: the exclusion lists are the graph's own dst-major CSR of
     ('item', etype, 'user') (indptr over users, int32 item ids), already on the device.
-    h: {'user': ..., 'item': ...} embeddings; user_ids: ids to serve (None: every user)."""
+    h: {'user': ..., 'item': ...} embeddings; user_ids: ids to serve (None: every user).
+    use_popularity: rank by softmax + weight_popularity * g.ndata['popularity']['item'], the
+    reference's get_recs(use_popularity=True) (recommend's popularity=)."""
     dev = h['item'].device
+    if use_popularity:
+        try:
+            pop = g.ndata['popularity']['item']
+        except (KeyError, AttributeError, TypeError) as exc:
+            raise KeyError("recommend_for_graph(use_popularity=True): the graph has no "
+                           "ndata['popularity']['item']") from exc
+        kw = dict(kw, popularity=torch.as_tensor(pop).to(dev).float(),
+                  weight_popularity=weight_popularity)
     ex_ptr, ex_idx = g.in_csr(etype)[:2]
     exclude = (ex_ptr.to(dev), ex_idx.to(dev))
     if user_ids is not None:

@@ -723,6 +723,88 @@ int gnnrec_topk_scored_candidates_f32(const int32_t* counts, const int32_t* cand
                                       const int32_t* exclude_indices, int64_t k, float* out_vals,
                                       int64_t* out_idx, void* stream);
 
+/* ---- f1d: popularity-weighted ratings (cosine head) ------------------------
+ * R(u, v) = expf(score(u, v)) / Z_u + p_v, p_v = popularity[v] * weight, Z_u the sum of
+ * expf(g(u, v)) over ALL items in a fixed order (csrc/rating.hpp, csrc/recommend_pop.hip,
+ * DESIGN.md §19): the reference's softmax(ratings) + popularity * weight, src/metrics.py:69-72.
+ *
+ * out[n_rows, dpad] (fp32, 16-byte aligned) = rows of x divided by max(norm, 1e-12), the
+ * values gnnrec_normalize_rows_bf16 rounds, each group of 8 columns stored in the order
+ * [0, 2, 4, 6, 1, 3, 5, 7] (the MFMA operand order of gnnrec_cos_denominators_f32); dpad = d
+ * rounded up to a multiple of 8, the pad zero.  d % 4 == 0, 4 <= d <= 2048, ld % 4 == 0. */
+int gnnrec_normalize_rows_f32(const float* x, int64_t ld, int64_t n_rows, int64_t d,
+                              const int64_t* row_map, float* out, int64_t dpad, void* stream);
+/* Partials of the item axis, a function of n_items alone: ceil(n_items / 1024). */
+int64_t gnnrec_cos_denominator_parts(int64_t n_items);
+/* Z[u] = sum over all items v of expf(users[u] . items[v]) for two gnnrec_normalize_rows_f32
+ * tables (fp32 MFMA, k ascending): bitwise the same for a row whatever the batch around it.
+ * parts: workspace of gnnrec_cos_denominator_parts(n_items) x n_users floats.  n_items = 0
+ * gives Z = 0. */
+int gnnrec_cos_denominators_f32(const float* users, int64_t n_users, const float* items,
+                                int64_t n_items, int64_t dpad, float* parts, float* Z,
+                                void* stream);
+/* Z[r] = parts[0][r] + parts[1][r] + ... in index order (parts [n_parts, n_rows]). */
+int gnnrec_fold_partials_f32(const float* parts, int64_t n_parts, int64_t n_rows, float* Z,
+                             void* stream);
+/* The MLP head's denominators: parts[c][u] = sum of expf(score(u, v)) over the items v of
+ * chunk c (1024 consecutive items, gnnrec_cos_denominator_parts(n_items) chunks), score the
+ * value of gnnrec_edge_mlp_dense_store_f32, in an order fixed by n_items alone;
+ * gnnrec_fold_partials_f32 gives Z.  parts: [chunks, n_users]. */
+int gnnrec_edge_mlp_dense_denominators_f32(const float* P, int64_t n_users, const float* Q,
+                                           int64_t n_items, const float* W2, const float* b2,
+                                           const float* w3, const float* b3, float* parts,
+                                           void* stream);
+/* gnnrec_edge_mlp_dense_store_f32 / _filter_f32 with R = expf(score) / Z[u] + p_col[v] in the
+ * score's place (Z [n_users], p_col [n_items]: one value per row of Q): stored, or compared
+ * with tau[u] as it is and kept in cand_scores. */
+int gnnrec_edge_mlp_dense_store_rating_f32(const float* P, int64_t n_users, const float* Q,
+                                           int64_t n_items, const float* W2, const float* b2,
+                                           const float* w3, const float* b3, const float* Z,
+                                           const float* p_col, float* out, int64_t ldo,
+                                           void* stream);
+int gnnrec_edge_mlp_dense_filter_rating_f32(const float* P, int64_t n_users, const float* Q,
+                                            int64_t n_items, const float* W2, const float* b2,
+                                            const float* w3, const float* b3, const float* Z,
+                                            const float* p_col, const float* tau, int32_t* counts,
+                                            int32_t* cand_items, float* cand_scores, int64_t cap,
+                                            void* stream);
+/* Z[r] = sum over the columns of expf(scores[r][c]), in a fixed order (one block per row). */
+int gnnrec_exp_rowsum_f32(const float* scores, int64_t ld, int64_t n_rows, int64_t n_cols,
+                          float* Z, void* stream);
+/* scores[r][c] = expf(scores[r][c]) / Z[r] + p[c], in place. */
+int gnnrec_rating_rows_f32(float* scores, int64_t ld, int64_t n_rows, int64_t n_cols,
+                           const float* Z, const float* p, void* stream);
+/* thr[u] = tau[u] - 2 delta_u, rounded down; delta_u = e^(1 + eps) ((e^eps - 1) + 2^-20) / Z[u]
+ * + 2^-22 |pmax[0]| bounds |Ra - R| (eps of gnnrec_score_bf16_filter; pmax: the largest p). */
+int gnnrec_rating_thresholds_f32(const float* tau, const float* Z, const float* pmax,
+                                 int64_t n_rows, float* thr, void* stream);
+/* gnnrec_mask_excluded_f32 for a table whose column c stands for item col_ids[c] (int32,
+ * strictly ascending): excluded items that are among the columns become -inf. */
+int gnnrec_mask_excluded_mapped_f32(float* scores, int64_t ld, int64_t n_rows, int64_t n_cols,
+                                    const int32_t* col_ids, const int64_t* user_rows,
+                                    const int64_t* exclude_indptr, const int32_t* exclude_indices,
+                                    void* stream);
+/* gnnrec_score_bf16_store with Ra(u, c) = expf(a(u, c)) / Z[u] + p_col[c] written instead of
+ * a (Z [n_users], p_col [n_items]: one value per row of `items`). */
+int gnnrec_score_bf16_store_rating(const void* users, int64_t n_users, const void* items,
+                                   int64_t n_items, int64_t dpad, const float* Z,
+                                   const float* p_col, float* out, int64_t ldo, void* stream);
+/* gnnrec_score_bf16_filter with Ra compared: item v joins row u's list where
+ * Ra(u, v) >= thr[u] (gnnrec_rating_thresholds_f32's, compared as they are). */
+int gnnrec_score_bf16_filter_rating(const void* users, int64_t n_users, const void* items,
+                                    int64_t n_items, int64_t dpad, const float* Z,
+                                    const float* p_col, const float* thr, int32_t* counts,
+                                    int32_t* cand_items, int64_t cap, void* stream);
+/* gnnrec_topk_candidates_f32 ranking by R = expf(score) / Z[r] + p[item] (Z per batch row,
+ * p per item): out_vals are the R values. */
+int gnnrec_topk_candidates_rating_f32(const int32_t* counts, const int32_t* cand_items,
+                                      int64_t cap, int64_t n_rows, const int64_t* user_rows,
+                                      const float* h_user, int64_t ldu, const float* h_item,
+                                      int64_t ldi, int64_t d, const int64_t* exclude_indptr,
+                                      const int32_t* exclude_indices, const float* Z,
+                                      const float* p, int64_t k, float* out_vals,
+                                      int64_t* out_idx, void* stream);
+
 /* ---- f2: projection backward (training step) -----------------------------
  * Replace torch autograd of the reference's nn.Linear layers and the
  * relu/normalise epilogue when train_model calls loss.backward()
