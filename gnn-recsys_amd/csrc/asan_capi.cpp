@@ -128,6 +128,34 @@ static void validation() {
         "mask null list");
   CHECK(gnnrec_mask_excluded_f32(nullptr, 9, 0, 9, nullptr, nullptr, nullptr, nullptr) == GNNREC_OK,
         "mask empty");
+  // the exhaustive top-k over score rows (topk.hip), the one the candidate paths rest on
+  CHECK(gnnrec_topk_rows_f32(f16, 9, 3, 9, 0, nullptr, nullptr, f16, l16, nullptr) ==
+            GNNREC_EINVAL && err_has("k must be in [1, 2^20] (got 0)"),
+        "topk rows k = 0");
+  CHECK(gnnrec_topk_rows_f32(f16, 9, 3, 9, ((int64_t)1 << 20) + 1, nullptr, nullptr, f16, l16,
+                             nullptr) == GNNREC_EINVAL && err_has("k must be in [1, 2^20]"),
+        "topk rows k > 2^20");
+  CHECK(gnnrec_topk_rows_f32(f16, 8, 3, 9, 4, nullptr, nullptr, f16, l16, nullptr) ==
+            GNNREC_EINVAL && err_has("bad pointers / ld"),
+        "topk rows ld < n_cols");
+  CHECK(gnnrec_topk_rows_f32(f16, 9, 3, 9, 4, nullptr, nullptr, nullptr, l16, nullptr) ==
+            GNNREC_EINVAL && err_has("bad pointers / ld"),
+        "topk rows null out_vals");
+  CHECK(gnnrec_topk_rows_f32(f16, 9, 3, 9, 4, nullptr, nullptr, f16, nullptr, nullptr) ==
+            GNNREC_EINVAL && err_has("bad pointers / ld"),
+        "topk rows null out_idx");
+  CHECK(gnnrec_topk_rows_f32(nullptr, 9, 3, 9, 4, nullptr, nullptr, f16, l16, nullptr) ==
+            GNNREC_EINVAL,
+        "topk rows null scores");
+  CHECK(gnnrec_topk_rows_f32(f16, 9, 3, 9, 4, l16, nullptr, f16, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("indptr without indices"),
+        "topk rows exclusion");
+  CHECK(gnnrec_topk_rows_f32(f16, 9, -1, 9, 4, nullptr, nullptr, f16, l16, nullptr) ==
+            GNNREC_EINVAL && err_has("negative size"),
+        "topk rows negative n_rows");
+  CHECK(gnnrec_topk_rows_f32(nullptr, 9, 0, 9, 4, nullptr, nullptr, nullptr, nullptr, nullptr) ==
+            GNNREC_OK,
+        "topk rows empty");
   CHECK(gnnrec_topk_candidates_f32(i16, i16, 64, 3, nullptr, f16, 16, f16, 16, 16, nullptr,
                                    nullptr, 65, f16, l16, nullptr) == GNNREC_EINVAL &&
             err_has("k must be"),

@@ -672,15 +672,34 @@ void topk_rows(const Tensor& scores, int64_t k, const optional<Tensor>& exclude_
   dev(exclude_indices, "exclude_indices", at::kLong);
   dev(out_vals, "out_vals", at::kFloat);
   dev(out_idx, "out_idx", at::kLong);
-  const int64_t n_rows = scores.size(0), n_cols = scores.size(1);
-  TORCH_CHECK_VALUE(out_vals.numel() == n_rows * k && out_idx.numel() == n_rows * k,
-                    "out_vals / out_idx must be [n_rows, k]");
   const int64_t lds = ld(scores, "scores");
+  const int64_t n_rows = scores.size(0), n_cols = scores.size(1);
+  TORCH_CHECK_VALUE(k >= 1, "k must be at least 1, got ", k);
+  // the kernel writes row r at out + r * k: a view with any other layout (a column slice of a
+  // wider result table) would be written in the wrong elements
+  TORCH_CHECK_VALUE(out_vals.dim() == 2 && out_vals.size(0) == n_rows && out_vals.size(1) == k &&
+                        out_vals.is_contiguous(),
+                    "out_vals must be a contiguous [", n_rows, ", ", k, "], got ",
+                    out_vals.sizes(), " with strides ", out_vals.strides());
+  TORCH_CHECK_VALUE(out_idx.dim() == 2 && out_idx.size(0) == n_rows && out_idx.size(1) == k &&
+                        out_idx.is_contiguous(),
+                    "out_idx must be a contiguous [", n_rows, ", ", k, "], got ", out_idx.sizes(),
+                    " with strides ", out_idx.strides());
+  bool lists = has(exclude_indptr);
+  if (lists) {  // the kernel reads exclude_indptr[row] and [row + 1] for every row
+    TORCH_CHECK_VALUE(exclude_indptr->is_contiguous() && exclude_indptr->numel() == n_rows + 1,
+                      "exclude_indptr must be contiguous with n_rows + 1 = ", n_rows + 1,
+                      " elements, got ", exclude_indptr->sizes());
+    TORCH_CHECK_VALUE(has(exclude_indices) && exclude_indices->is_contiguous(),
+                      "exclude_indices must be given, contiguous, with exclude_indptr");
+    lists = exclude_indices->numel() > 0;  // no entries (a null data pointer): nothing listed
+  }
   if (meta(scores)) return;
   const c10::DeviceGuard g(scores.device());
-  ck(gnnrec_topk_rows_f32(p<float>(scores), lds, n_rows, n_cols, k, p<int64_t>(exclude_indptr),
-                          p<int64_t>(exclude_indices), p<float>(out_vals), p<int64_t>(out_idx),
-                          stream_of(scores)),
+  ck(gnnrec_topk_rows_f32(p<float>(scores), lds, n_rows, n_cols, k,
+                          lists ? p<int64_t>(exclude_indptr) : nullptr,
+                          lists ? p<int64_t>(exclude_indices) : nullptr, p<float>(out_vals),
+                          p<int64_t>(out_idx), stream_of(scores)),
      "gnnrec_topk_rows_f32");
 }
 

@@ -45,7 +45,12 @@ def create_already_bought(g, bought_eids, etype='buys'):
 
 
 def topk_rows(scores: torch.Tensor, k: int, exclude_indptr=None, exclude_indices=None):
-    """Per row: k best columns by (score desc, column asc), excluded columns skipped."""
+    """Per row: k best columns by (score desc, column asc), excluded columns skipped
+    -> (vals, idx), padded with (-inf, -1) where a row has fewer than k eligible columns.
+    A -inf score is a score: its column is returned, in column order after every finite
+    one (callers that mask to -inf rewrite those indices themselves).  exclude_indptr is a
+    contiguous int64 [n_rows + 1] over exclude_indices (int64 column ids, any order,
+    duplicates and ids outside [0, n_cols) allowed).  No NaN."""
     n_rows, n_cols = scores.shape
     vals = torch.empty((n_rows, k), dtype=torch.float32, device=scores.device)
     idx = torch.empty((n_rows, k), dtype=torch.int64, device=scores.device)

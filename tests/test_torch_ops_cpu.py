@@ -106,6 +106,55 @@ def test_meta_kernels_check_shapes():
                         _meta(4, 128))
 
 
+def test_topk_rows_checks_outputs_and_lists():
+    """topk_rows writes row r of its outputs at r * k and reads exclude_indptr[r], [r + 1]:
+    outputs that are not a contiguous [n_rows, k] and lists that do not cover every row are
+    refused before anything launches; a valid call on meta tensors returns."""
+    T = _T()
+    i64 = torch.int64
+    S, k = _meta(5, 300), 7
+
+    def out(rows=5, cols=k):
+        return _meta(rows, cols), _meta(rows, cols, dtype=i64)
+    T.topk_rows(S, k, None, None, *out())
+    T.topk_rows(S, k, _meta(6, dtype=i64), _meta(40, dtype=i64), *out())
+    T.topk_rows(S, k, _meta(6, dtype=i64), _meta(0, dtype=i64), *out())  # every list empty
+    T.topk_rows(_meta(5, 304)[:, 1:301], k, None, None, *out())  # a view of a wider table
+    T.topk_rows(S, k, None, None, _meta(7, k)[1:6], _meta(7, k, dtype=i64)[1:6])  # whole rows
+    wide_v, wide_i = out(cols=k + 3)
+    with pytest.raises(ValueError, match="out_vals must be a contiguous"):
+        T.topk_rows(S, k, None, None, wide_v[:, :k], out()[1])    # a column slice
+    with pytest.raises(ValueError, match="out_idx must be a contiguous"):
+        T.topk_rows(S, k, None, None, out()[0], wide_i[:, 3:])
+    with pytest.raises(ValueError, match="out_vals must be a contiguous"):
+        T.topk_rows(S, k, None, None, _meta(k, 5).t(), out()[1])  # transposed
+    with pytest.raises(ValueError, match="out_vals must be a contiguous"):
+        T.topk_rows(S, k, None, None, _meta(5 * k), out()[1])     # the right numel, 1-D
+    with pytest.raises(ValueError, match="out_idx must be a contiguous"):
+        T.topk_rows(S, k, None, None, out()[0], out(rows=k, cols=5)[1])
+    with pytest.raises(ValueError, match="out_vals must be a contiguous"):
+        T.topk_rows(S, k, None, None, *out(rows=4))
+    with pytest.raises(ValueError, match="out_idx must be Long"):
+        T.topk_rows(S, k, None, None, out()[0], _meta(5, k, dtype=torch.int32))
+    with pytest.raises(ValueError, match=r"exclude_indptr must be contiguous with n_rows \+ 1"):
+        T.topk_rows(S, k, _meta(5, dtype=i64), _meta(40, dtype=i64), *out())   # one short
+    with pytest.raises(ValueError, match=r"exclude_indptr must be contiguous with n_rows \+ 1"):
+        T.topk_rows(S, k, _meta(7, dtype=i64), _meta(40, dtype=i64), *out())
+    with pytest.raises(ValueError, match=r"exclude_indptr must be contiguous with n_rows \+ 1"):
+        T.topk_rows(S, k, _meta(12, dtype=i64)[::2], _meta(40, dtype=i64), *out())
+    with pytest.raises(ValueError, match="exclude_indices must be given"):
+        T.topk_rows(S, k, _meta(6, dtype=i64), None, *out())
+    with pytest.raises(ValueError, match="exclude_indices must be given"):
+        T.topk_rows(S, k, _meta(6, dtype=i64), _meta(80, dtype=i64)[::2], *out())
+    with pytest.raises(ValueError, match="exclude_indices must be Long"):
+        T.topk_rows(S, k, _meta(6, dtype=i64), _meta(40, dtype=torch.int32), *out())
+    for bad_k in (0, -3):
+        with pytest.raises(ValueError, match="k must be at least 1"):
+            T.topk_rows(S, bad_k, None, None, _meta(5, 0), _meta(5, 0, dtype=i64))
+    with pytest.raises(ValueError, match="unit column stride"):
+        T.topk_rows(_meta(300, 5).t(), k, None, None, *out())
+
+
 def test_cpu_tensors_are_refused():
     T = _T()
     with pytest.raises(ValueError, match="HIP device tensor"):
