@@ -338,6 +338,72 @@ static void validation() {
             err_has("null CSR"),
         "remove_edges null indices with a CSR asked for");
 #undef RM_EDGES
+  // edge insertion (csr_merge.hip): every refusal comes before the first memset or launch; the
+  // empty call (no old edges, no batch) still writes the status and indptr', so its host side
+  // is the workspace query, which must give room whatever it is asked
+  CHECK(gnnrec_csr_add_edges_workspace_bytes(0, 0) > 0 &&
+            gnnrec_csr_add_edges_workspace_bytes(-5, 3) ==
+                gnnrec_csr_add_edges_workspace_bytes(0, 3) &&
+            gnnrec_csr_add_edges_workspace_bytes(0, -3) == gnnrec_csr_add_edges_workspace_bytes(0, 0),
+        "add_edges empty workspace");
+  CHECK(gnnrec_csr_add_edges_workspace_bytes(33, 4) >=
+            33 * (8 + 8 + 4 + 8 + 4) + 5 * 8 + gnnrec_csr_build_workspace_bytes(33, 4),
+        "add_edges workspace covers its parts");
+  CHECK(gnnrec_csr_add_edges_workspace_bytes(1000, 1000000) < 16 * 1000000,
+        "add_edges workspace follows the batch and the rows, not the relation");
+  const size_t aws = gnnrec_csr_add_edges_workspace_bytes(10, 7);
+#define ADD_EDGES(ip, ix, E, n_src, n_dst, sn, dn, n, ws, wsb, ipo, ixo, st) \
+  gnnrec_csr_add_edges(ip, ix, l16, E, n_src, n_dst, sn, dn, n, ws, wsb, ipo, ixo, l16, st, nullptr)
+  CHECK(ADD_EDGES(l16, i16, -1, 9, 7, l16, l16, 10, p16, aws, l16, i16, l16) == GNNREC_EINVAL &&
+            err_has("negative"),
+        "add_edges negative E");
+  CHECK(ADD_EDGES(l16, i16, 100, 9, 7, l16, l16, -1, p16, aws, l16, i16, l16) == GNNREC_EINVAL &&
+            err_has("negative"),
+        "add_edges negative n");
+  CHECK(ADD_EDGES(l16, i16, 100, -9, 7, l16, l16, 10, p16, aws, l16, i16, l16) == GNNREC_EINVAL,
+        "add_edges negative n_src");
+  CHECK(ADD_EDGES(l16, i16, 100, 9, -7, l16, l16, 10, p16, aws, l16, i16, l16) == GNNREC_EINVAL,
+        "add_edges negative n_dst");
+  CHECK(ADD_EDGES(l16, i16, (int64_t)1 << 31, 9, 7, l16, l16, 10, p16, aws, l16, i16, l16) ==
+            GNNREC_EINVAL && err_has("int32"),
+        "add_edges E range");
+  CHECK(ADD_EDGES(l16, i16, ((int64_t)1 << 31) - 10, 9, 7, l16, l16, 10, p16, aws, l16, i16,
+                  l16) == GNNREC_EINVAL && err_has("int32"),
+        "add_edges E + n range");
+  CHECK(ADD_EDGES(l16, i16, 100, (int64_t)1 << 31, 7, l16, l16, 10, p16, aws, l16, i16, l16) ==
+            GNNREC_EINVAL && err_has("int32"),
+        "add_edges n_src range");
+  CHECK(ADD_EDGES(l16, i16, 100, 9, (int64_t)1 << 31, l16, l16, 10, p16, aws, l16, i16, l16) ==
+            GNNREC_EINVAL && err_has("int32"),
+        "add_edges n_dst range");
+  CHECK(ADD_EDGES(l16, i16, 100, 9, 7, l16, l16, 10, p16, aws, l16, i16, nullptr) ==
+            GNNREC_EINVAL && err_has("status"),
+        "add_edges null status");
+  CHECK(ADD_EDGES(nullptr, nullptr, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0, l16, nullptr, l16) ==
+            GNNREC_EINVAL && err_has("workspace"),
+        "add_edges empty call without workspace");
+  CHECK(ADD_EDGES(l16, i16, 100, 9, 7, l16, l16, 10, p16, aws, nullptr, i16, l16) ==
+            GNNREC_EINVAL && err_has("indptr_out"),
+        "add_edges null indptr_out");
+  CHECK(ADD_EDGES(l16, i16, 0, 9, 0, l16, l16, 10, p16, aws, l16, i16, l16) == GNNREC_EINVAL &&
+            err_has("edges between"),
+        "add_edges edges without rows");
+  CHECK(ADD_EDGES(l16, nullptr, 100, 9, 7, l16, l16, 10, p16, aws, l16, i16, l16) ==
+            GNNREC_EINVAL && err_has("null CSR"),
+        "add_edges null indices");
+  CHECK(ADD_EDGES(nullptr, i16, 100, 9, 7, l16, l16, 10, p16, aws, l16, i16, l16) ==
+            GNNREC_EINVAL && err_has("null CSR"),
+        "add_edges null indptr");
+  CHECK(ADD_EDGES(l16, i16, 100, 9, 7, l16, nullptr, 10, p16, aws, l16, i16, l16) ==
+            GNNREC_EINVAL && err_has("null batch"),
+        "add_edges null dst_new");
+  CHECK(ADD_EDGES(l16, i16, 100, 9, 7, l16, l16, 10, p16, aws, l16, nullptr, l16) ==
+            GNNREC_EINVAL && err_has("null output"),
+        "add_edges null indices_out");
+  CHECK(ADD_EDGES(l16, i16, 100, 9, 7, l16, l16, 10, p16, aws - 1, l16, i16, l16) ==
+            GNNREC_EINVAL && err_has("workspace"),
+        "add_edges short workspace");
+#undef ADD_EDGES
 }
 
 // the four fused aggregate+project entries (spmm_project.hip, spmm_pair_mfma.hip): every

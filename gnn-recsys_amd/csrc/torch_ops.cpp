@@ -1356,6 +1356,47 @@ void csr_remove_edges(const Tensor& src, const Tensor& dst, const Tensor& indptr
      "gnnrec_csr_remove_edges");
 }
 
+// add_edges of one relation: the batch merged into the cached CSR (csr_merge.hip)
+void csr_add_edges(const Tensor& indptr, const Tensor& indices, const Tensor& eids,
+                   const Tensor& src_new, const Tensor& dst_new, int64_t n_src, int64_t n_dst,
+                   Tensor& ws, Tensor& indptr_out, Tensor& indices_out, Tensor& eids_out,
+                   Tensor& status) {
+  const OneDevice one_device_;
+  dev(indptr, "indptr", at::kLong);
+  dev(indices, "indices", at::kInt);
+  dev(eids, "eids", at::kLong);
+  dev(src_new, "src_new", at::kLong);
+  dev(dst_new, "dst_new", at::kLong);
+  dev(ws, "workspace", at::kByte);
+  dev(indptr_out, "indptr_out", at::kLong);
+  dev(indices_out, "indices_out", at::kInt);
+  dev(eids_out, "eids_out", at::kLong);
+  dev(status, "status", at::kLong);
+  const int64_t E = eids.numel(), n = dst_new.numel();
+  TORCH_CHECK_VALUE(n_src >= 0 && n_dst >= 0, "csr_add_edges: negative node count");
+  TORCH_CHECK_VALUE(indptr.dim() == 1 && indptr.numel() == n_dst + 1 && indices.dim() == 1 &&
+                        eids.dim() == 1 && indices.numel() == E && indptr.is_contiguous() &&
+                        indices.is_contiguous() && eids.is_contiguous(),
+                    "csr_add_edges: the CSR must be indptr [n_dst+1], indices [E], eids [E], "
+                    "contiguous");
+  TORCH_CHECK_VALUE(src_new.dim() == 1 && dst_new.dim() == 1 && src_new.numel() == n &&
+                        src_new.is_contiguous() && dst_new.is_contiguous(),
+                    "csr_add_edges: src_new and dst_new must be contiguous 1-D tensors of one "
+                    "length");
+  TORCH_CHECK_VALUE(indptr_out.numel() == n_dst + 1 && indices_out.numel() == E + n &&
+                        eids_out.numel() == E + n && status.numel() == 2 &&
+                        indptr_out.is_contiguous() && indices_out.is_contiguous() &&
+                        eids_out.is_contiguous() && status.is_contiguous(),
+                    "csr_add_edges: output sizes");
+  if (meta(indptr)) return;
+  const c10::DeviceGuard g(indptr.device());
+  ck(gnnrec_csr_add_edges(p<int64_t>(indptr), p<int32_t>(indices), p<int64_t>(eids), E, n_src,
+                          n_dst, p<int64_t>(src_new), p<int64_t>(dst_new), n, ws.data_ptr(),
+                          ws.nbytes(), p<int64_t>(indptr_out), p<int32_t>(indices_out),
+                          p<int64_t>(eids_out), p<int64_t>(status), stream_of(indptr)),
+     "gnnrec_csr_add_edges");
+}
+
 // ---------------------------------------------------------------- f2 fused relation
 // One ConvLayer relation of a TRAINING step (sum / mean aggregation), forward and backward
 // each as ONE dispatcher call that issues every launch from C++ (gnnrec/autograd.py
@@ -2135,6 +2176,9 @@ int64_t cos_denominator_parts(int64_t n_items) { return gnnrec_cos_denominator_p
 int64_t csr_remove_edges_workspace_bytes(int64_t E, int64_t n_dst) {
   return (int64_t)gnnrec_csr_remove_edges_workspace_bytes(E, n_dst);
 }
+int64_t csr_add_edges_workspace_bytes(int64_t n_new, int64_t n_dst) {
+  return (int64_t)gnnrec_csr_add_edges_workspace_bytes(n_new, n_dst);
+}
 int64_t sddmm_cos_backward_workspace_bytes(int64_t E, int64_t n_src, int64_t n_dst, int64_t d,
                                            int64_t groups, int64_t K) {
   if (groups > 0)
@@ -2255,6 +2299,9 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor rm, Tensor(a!) workspace, Tensor(b!) src_out, Tensor(c!) dst_out, "
         "Tensor(d!) kept_eids, Tensor(e!) indptr_out, Tensor(f!) indices_out, "
         "Tensor(g!) eids_out, Tensor(h!) status) -> ()");
+  m.def("csr_add_edges(Tensor indptr, Tensor indices, Tensor eids, Tensor src_new, "
+        "Tensor dst_new, int n_src, int n_dst, Tensor(a!) workspace, Tensor(b!) indptr_out, "
+        "Tensor(c!) indices_out, Tensor(d!) eids_out, Tensor(e!) status) -> ()");
   m.def("add_(Tensor(a!) a, Tensor b) -> ()");
   m.def("tree_sum_(Tensor(a!) a, Tensor[] rest) -> ()");
   m.def("lstm_step(Tensor P, Tensor indptr, Tensor indices, Tensor order, int t, int n_act, "
@@ -2320,6 +2367,8 @@ TORCH_LIBRARY(gnnrec, m) {
   m.def("cos_denominator_parts(int n_items) -> int", &cos_denominator_parts);
   m.def("csr_remove_edges_workspace_bytes(int n_edges, int n_dst) -> int",
         &csr_remove_edges_workspace_bytes);
+  m.def("csr_add_edges_workspace_bytes(int n_new, int n_dst) -> int",
+        &csr_add_edges_workspace_bytes);
   m.def("sddmm_cos_backward_workspace_bytes(int n_edges, int n_src, int n_dst, int d, "
         "int groups=0, int K=0) -> int", &sddmm_cos_backward_workspace_bytes);
   m.def("margin_loss_blocks(int n_pos) -> int", &margin_loss_blocks);
@@ -2373,6 +2422,7 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("csr_from_keys", &csr_from_keys);               \
   m.impl("csr_build", &csr_build);                       \
   m.impl("csr_remove_edges", &csr_remove_edges);         \
+  m.impl("csr_add_edges", &csr_add_edges);               \
   m.impl("add_", &add_);                                 \
   m.impl("tree_sum_", &tree_sum_);                       \
   m.impl("lstm_step", &lstm_step);                       \

@@ -142,6 +142,11 @@ SIGNATURES = {
     # (src, dst, indptr, indices, eids, E, n_dst, rm, R, ws, ws_bytes, 6 outputs, status, stream)
     "gnnrec_csr_remove_edges": (_INT, [_P, _P, _P, _P, _P, _I64, _I64, _P, _I64, _P, _U64,
                                        _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gnnrec_csr_add_edges_workspace_bytes": (_U64, [_I64, _I64]),
+    # (indptr, indices, eids, E, n_src, n_dst, src_new, dst_new, n, ws, ws_bytes, 3 outputs,
+    #  status, stream)
+    "gnnrec_csr_add_edges": (_INT, [_P, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _U64,
+                                    _P, _P, _P, _P, _P]),
     "gnnrec_csr_has_edges": (_INT, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P]),
     "gnnrec_add_f32": (_INT, [_P, _P, _P, _I64, _P]),
     "gnnrec_tree_sum_f32": (_INT, [_P, _INT, _I64, _P, _P]),

@@ -31,6 +31,14 @@ NID = "_ID"
 EID = "_ID"
 CEType = Tuple[str, str, str]
 
+# HeteroGraph.add_edges on a device graph merges a batch into the cached CSRs
+# (gnnrec_csr_add_edges) while the batch is at most this share of the relation's old edge
+# count, and rebuilds them (gnnrec_csr_build) above it: both give the same bits, only time
+# decides.  Measured up to a batch of 100 % of E, where add_edges by merge still beat both
+# rebuilds in every run while the merge of ONE relation alone only tied its rebuild; larger
+# batches are unmeasured, so they rebuild (profiles/add_edges_ab.md).
+ADD_EDGES_REBUILD_SHARE = 1.0
+
 
 class LazyRows:
     """Rows of a table at ids, gathered when first read (ops.gather_rows; a negative id gives
@@ -499,6 +507,166 @@ class HeteroGraph:
         self._csr_edata.pop(ce, None)
         self._csr_edata.pop(("_member",) + ce, None)
         self._edge_rec.pop(ce, None)
+
+    @staticmethod
+    def _grown_frame(frame, data, old: int, n: int, device, what: str) -> dict:
+        """Every field of `frame` (rows 0..old-1) with n more rows: those of data[k] where
+        given, zeros of the field's dtype and trailing shape otherwise; a key the frame lacks
+        becomes a new field with zeros for the old rows.  Checks everything before it builds
+        anything: a wrong row count, dtype or trailing shape raises ValueError."""
+        given = {}
+        for k, t in (data or {}).items():
+            t = torch.as_tensor(t, device=device)
+            if t.dim() < 1 or t.shape[0] != n:
+                raise ValueError(f"{what}: data[{k!r}] must have {n} rows, got shape "
+                                 f"{tuple(t.shape)}")
+            if k in frame:
+                cur = frame[k]
+                if t.dtype != cur.dtype:
+                    raise ValueError(f"{what}: data[{k!r}] is {t.dtype}, the field is "
+                                     f"{cur.dtype}")
+                if t.shape[1:] != cur.shape[1:]:
+                    raise ValueError(f"{what}: data[{k!r}] has trailing shape "
+                                     f"{tuple(t.shape[1:])}, the field has "
+                                     f"{tuple(cur.shape[1:])}")
+            given[k] = t
+        out = {}
+        for k, cur in frame.items():
+            add = given[k] if k in given else cur.new_zeros((n,) + tuple(cur.shape[1:]))
+            out[k] = torch.cat([cur, add])
+        for k, t in given.items():
+            if k not in frame:
+                out[k] = torch.cat([t.new_zeros((old,) + tuple(t.shape[1:])), t])
+        return out
+
+    @staticmethod
+    def _merge_csr_host(csr, u, v, n_dst: int):
+        """The rule of gnnrec_csr_add_edges with host tensor ops: a row's new edges follow its
+        old ones, so batch slot t (in the batch's own CSR order) lands at the old end of its
+        row plus t, and old slot j moves up by the batch slots of the rows before its own."""
+        indptr, indices, ids = csr
+        E, n = int(ids.numel()), int(u.numel())
+        ipb, ixb, eb = build_csr(u, v, n_dst)
+        P = indptr[v[eb] + 1]
+        j = torch.arange(E, dtype=torch.int64)
+        old_pos = j + torch.searchsorted(P, j, right=True)
+        new_pos = P + torch.arange(n, dtype=torch.int64)
+        indices2 = torch.empty(E + n, dtype=torch.int32)
+        ids2 = torch.empty(E + n, dtype=torch.int64)
+        indices2[old_pos], ids2[old_pos] = indices, ids
+        indices2[new_pos], ids2[new_pos] = ixb, eb + E
+        return indptr + ipb, indices2, ids2
+
+    def add_edges(self, u, v, data=None, etype=None) -> None:
+        """DGL's add_edges, in place: the edges u[i] -> v[i] join relation `etype` with the
+        edge ids E .. E+n-1, in the order given.  Every edge-data tensor of the relation grows
+        by n rows — those of data[k] where given, zeros of the field's dtype and trailing shape
+        otherwise; a key of `data` the relation lacks becomes a new field with zeros for the
+        old edges.  A wrong row count, dtype or trailing shape raises ValueError.  Node data and
+        the other relations (a reverse relation included) are untouched; n == 0 is a no-op.
+
+        Unlike DGL, an id at or beyond the node count raises ValueError and leaves the graph as
+        it was: nodes are never created implicitly (one bad id cannot silently grow a table) —
+        call add_nodes first.  DGL itself is not available to test against here, so parity with
+        its add_edges beyond what this text states is not pinned.
+
+        On a HIP device the COO is concatenated and the relation's cached in-CSR and
+        source-major CSR are each replaced by gnnrec_csr_add_edges (the batch's CSR merged into
+        the cached one — no sort of the old edges; bitwise what build_csr gives on the whole
+        COO); a CSR that is not cached stays unbuilt.  A batch above ADD_EDGES_REBUILD_SHARE
+        of the old edge count rebuilds the cached CSRs instead (the same bits).  A graph in
+        host memory applies the same rule with host tensor ops.  The relation's edge data in
+        CSR order, its packed edge records and its membership CSR are dropped and rebuilt on
+        next use.  Tensors are replaced, never written: a clone taken before is unaffected.
+
+        Loaders and samplers built on this graph BEFORE the call hold edge ids and per-edge
+        scratch of the old numbering: build them after the last change."""
+        if etype is None and len(self.canonical_etypes) != 1:
+            raise ValueError("add_edges: etype is needed on a graph with several relations")
+        ce = self.to_canonical_etype(etype if etype is not None else self.canonical_etypes[0])
+        s, d = self._coo[ce]
+        u = torch.as_tensor(u, dtype=torch.int64, device=s.device).reshape(-1)
+        v = torch.as_tensor(v, dtype=torch.int64, device=s.device).reshape(-1)
+        if u.numel() != v.numel():
+            raise ValueError(f"add_edges: {u.numel()} source ids, {v.numel()} destination ids")
+        E, n = int(s.numel()), int(u.numel())
+        if n == 0:
+            return
+        n_src, n_dst = self._num_nodes[ce[0]], self._num_nodes[ce[2]]
+        edata = self._grown_frame(self._edata[ce], data, E, n, s.device, "add_edges")
+        csr, ocsr = self._csr.get(ce), self._out_csr.get(ce)
+        merge = s.is_cuda and n <= ADD_EDGES_REBUILD_SHARE * max(E, 1)
+        if not (merge and (csr is not None or ocsr is not None)):
+            # (the merge validates on the device and reports through its status words)
+            if bool(((u < 0) | (u >= n_src) | (v < 0) | (v >= n_dst)).any()):
+                raise ValueError(f"add_edges: a node id lies outside [0, {n_src}) x "
+                                 f"[0, {n_dst}); add_nodes first")
+        s2, d2 = torch.cat([s, u]), torch.cat([d, v])
+        if not s.is_cuda:
+            csr2 = self._merge_csr_host(csr, u, v, n_dst) if csr is not None else None
+            ocsr2 = self._merge_csr_host(ocsr, v, u, n_src) if ocsr is not None else None
+        elif merge:
+            try:
+                csr2 = ops.csr_add_edges(csr, u, v, n_src, n_dst) if csr is not None else None
+                ocsr2 = ops.csr_add_edges(ocsr, v, u, n_dst, n_src) if ocsr is not None else None
+            except ValueError:
+                raise ValueError(f"add_edges: a node id lies outside [0, {n_src}) x "
+                                 f"[0, {n_dst}); add_nodes first") from None
+        else:
+            csr2 = build_csr(s2, d2, n_dst) if csr is not None else None
+            ocsr2 = build_csr(d2, s2, n_src) if ocsr is not None else None
+        self._coo[ce] = (s2, d2)
+        for k, t in edata.items():
+            self._edata[ce][k] = t
+        if csr2 is not None:
+            self._csr[ce] = csr2
+        if ocsr2 is not None:
+            self._out_csr[ce] = ocsr2
+        self._csr_edata.pop(ce, None)
+        self._csr_edata.pop(("_member",) + ce, None)
+        self._edge_rec.pop(ce, None)
+
+    def add_nodes(self, num: int, data=None, ntype=None) -> None:
+        """DGL's add_nodes, in place: `num` more nodes of type `ntype` (needed on a graph with
+        several types), without edges.  Every node-data tensor of the type grows by num rows —
+        those of data[k] where given, zeros otherwise; an unknown key becomes a new field with
+        zeros for the old nodes; a wrong row count, dtype or trailing shape raises ValueError.
+        Cached in-CSRs of relations ending in the type, and source-major CSRs of relations
+        starting in it, get num more (empty) rows; the membership CSRs of relations touching
+        the type are dropped; caches whose contents do not change are kept.  Tensors are
+        replaced, never written: a clone taken before is unaffected."""
+        if ntype is None:
+            if len(self.ntypes) != 1:
+                raise ValueError("add_nodes: ntype is needed on a graph with several node types")
+            ntype = self.ntypes[0]
+        if ntype not in self._num_nodes:
+            raise ValueError(f"add_nodes: no node type {ntype!r}")
+        num = int(num)
+        if num < 0:
+            raise ValueError(f"add_nodes: num = {num}")
+        if num == 0:
+            return
+        N = self._num_nodes[ntype]
+        ndata = self._grown_frame(self._ndata[ntype], data, N, num, self.device, "add_nodes")
+
+        def more_rows(csr):
+            indptr, indices, ids = csr
+            E = int(ids.numel())
+            indptr2 = torch.cat([indptr, indptr.new_full((num,), E)])
+            if hasattr(indptr, "_gnnrec_nnz"):
+                indptr2._gnnrec_nnz = E
+            return indptr2, indices, ids
+
+        self._num_nodes[ntype] = N + num
+        for k, t in ndata.items():
+            self._ndata[ntype][k] = t
+        for ce in self.canonical_etypes:
+            if ce[2] == ntype and ce in self._csr:
+                self._csr[ce] = more_rows(self._csr[ce])
+            if ce[0] == ntype and ce in self._out_csr:
+                self._out_csr[ce] = more_rows(self._out_csr[ce])
+            if ntype in (ce[0], ce[2]):
+                self._csr_edata.pop(("_member",) + ce, None)
 
     def to(self, device):
         g = HeteroGraph({ce: (s.to(device), d.to(device)) for ce, (s, d) in self._coo.items()},

@@ -355,6 +355,45 @@ def csr_remove_edges(src: torch.Tensor, dst: torch.Tensor, rm: torch.Tensor, csr
     return fit(src_o), fit(dst_o), fit(kept), new_csr
 
 
+def csr_add_edges(csr, src_new: torch.Tensor, dst_new: torch.Tensor, n_src: int, n_dst: int):
+    """DGL's add_edges on one relation's dst-major CSR (gnnrec_csr_add_edges: the batch's own
+    CSR merged into the cached one; the old edges are not sorted again).  csr = (indptr,
+    indices, eids) as csr_build gives it, (src_new, dst_new) the int64 batch, which takes the
+    edge ids E .. E+n-1 in the order given.  -> (indptr', indices', eids'), bit for bit
+    csr_build of the concatenated COO.  An id outside [0, n_src) / [0, n_dst) raises
+    ValueError (the one readback of the call: two status words)."""
+    T = _T()
+    indptr, indices, eids = csr
+    for t, n, dt in ((indptr, "indptr", torch.int64), (indices, "indices", torch.int32),
+                     (eids, "eids", torch.int64), (src_new, "src_new", torch.int64),
+                     (dst_new, "dst_new", torch.int64)):
+        _dev(t, n, dt)
+    if src_new.shape != dst_new.shape or src_new.dim() != 1:
+        raise ValueError("csr_add_edges: src_new and dst_new must be 1-D tensors of one length")
+    if indptr.numel() != n_dst + 1 or indices.numel() != eids.numel():
+        raise ValueError("csr_add_edges: the CSR must be indptr [n_dst+1], indices [E], eids [E]")
+    dev, E, n = indptr.device, eids.numel(), dst_new.numel()
+    if n and (n_src <= 0 or n_dst <= 0):
+        raise ValueError(f"csr_add_edges: {n} edges between {n_src} and {n_dst} nodes")
+    indptr, indices, eids = indptr.contiguous(), indices.contiguous(), eids.contiguous()
+    src_new, dst_new = src_new.contiguous(), dst_new.contiguous()
+    indptr_o = torch.empty(n_dst + 1, dtype=torch.int64, device=dev)
+    indices_o = torch.empty(E + n, dtype=torch.int32, device=dev)
+    eids_o = torch.empty(E + n, dtype=torch.int64, device=dev)
+    status = torch.empty(2, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(int(T.csr_add_edges_workspace_bytes(n, n_dst)), 1), dtype=torch.uint8,
+                     device=dev)
+    T.csr_add_edges(indptr, indices, eids, src_new, dst_new, n_src, n_dst, ws, indptr_o,
+                    indices_o, eids_o, status)
+    if dev.type != "meta":
+        _total, bad = status.tolist()
+        if bad:
+            raise ValueError(f"csr_add_edges: a node id lies outside [0, {n_src}) x "
+                             f"[0, {n_dst})")
+    indptr_o._gnnrec_nnz = E + n
+    return indptr_o, indices_o, eids_o
+
+
 def membership_csr(src: torch.Tensor, dst: torch.Tensor, n_src: int, n_dst: int):
     """The dst-major CSR of (src, dst) with every row's source ids ascending — what
     has_edges searches.  Two stable radix sorts of the library (gnnrec_csr_build): by source

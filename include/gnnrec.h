@@ -898,6 +898,25 @@ int gnnrec_csr_remove_edges(const int64_t* src, const int64_t* dst, const int64_
                             int64_t* kept_eids, int64_t* indptr_out, int32_t* indices_out,
                             int64_t* eids_out, int64_t* status, void* stream);
 
+/* DGLGraph.add_edges on one relation's cached CSR: the batch (src_new, dst_new [n_new]) is
+ * appended to the relation with the edge ids n_edges .. n_edges + n_new - 1, in the order
+ * given.  Inputs: the relation's dst-major CSR as gnnrec_csr_build gives it (indptr [n_dst+1],
+ * indices, eids [n_edges]; ignored when n_edges == 0) and the batch.  Outputs: indptr_out
+ * [n_dst+1], indices_out, eids_out [n_edges + n_new] — bit for bit gnnrec_csr_build of the
+ * concatenated COO, by a merge (the CSR keeps a row in edge-id order, so a row's new edges
+ * follow its old ones): the batch alone is sorted, every old slot is read and written once.
+ * status[2] (device): {n_edges + n_new, bad}; bad != 0 when some src_new[i] lies outside
+ * [0, n_src) or some dst_new[i] outside [0, n_dst) — then status[0] = n_edges and no other
+ * output is written; no kernel indexes with an id before it is validated.  The status is the
+ * call's only readback, and the caller's.  n_edges + n_new, n_src, n_dst < 2^31.  Workspace
+ * from gnnrec_csr_add_edges_workspace_bytes (about 52 B per BATCH edge + 8 B per row). */
+size_t gnnrec_csr_add_edges_workspace_bytes(int64_t n_new, int64_t n_dst);
+int gnnrec_csr_add_edges(const int64_t* indptr, const int32_t* indices, const int64_t* eids,
+                         int64_t n_edges, int64_t n_src, int64_t n_dst, const int64_t* src_new,
+                         const int64_t* dst_new, int64_t n_new, void* workspace,
+                         size_t workspace_bytes, int64_t* indptr_out, int32_t* indices_out,
+                         int64_t* eids_out, int64_t* status, void* stream);
+
 /* K10 — DGLGraph.has_edges_between(u, v, etype) (reference src/train/run.py:95-101,160-166,
  * the false-negative mask; DGL 0.5.2 [ext]: `_CAPI_DGLHeteroHasEdgesBetween`): out[i] = 1
  * when some edge u[i] -> v[i] exists, else 0; ids outside [0, n_src) / [0, n_dst) give 0.
