@@ -404,6 +404,54 @@ static void validation() {
             GNNREC_EINVAL && err_has("workspace"),
         "add_edges short workspace");
 #undef ADD_EDGES
+  // the dirty-set frontier (frontier.hip) and the row scatter (rows.hip): every refusal comes
+  // before the first memset or launch
+  CHECK(gnnrec_frontier_mark_workspace_bytes(0) > 0 &&
+            gnnrec_frontier_mark_workspace_bytes(-4) == gnnrec_frontier_mark_workspace_bytes(0),
+        "frontier_mark empty workspace");
+  CHECK(gnnrec_frontier_mark_workspace_bytes(1000) >=
+            1001 * 8 + (size_t)gnnrec_scan_workspace_bytes(1000),
+        "frontier_mark workspace covers its parts");
+  const size_t fws = gnnrec_frontier_mark_workspace_bytes(10);
+#define FRONTIER(rows, n, ip, ix, E, n_src, n_dst, mark, ws, wsb, st) \
+  gnnrec_frontier_mark(rows, n, nullptr, ip, ix, E, n_src, n_dst, mark, ws, wsb, st, nullptr)
+  CHECK(FRONTIER(l16, -1, l16, i16, 100, 9, 7, i16, p16, fws, l16) == GNNREC_EINVAL &&
+            err_has("negative"),
+        "frontier_mark negative n");
+  CHECK(FRONTIER(l16, 10, l16, i16, (int64_t)1 << 31, 9, 7, i16, p16, fws, l16) ==
+            GNNREC_EINVAL && err_has("int32"),
+        "frontier_mark E range");
+  CHECK(FRONTIER(l16, 10, l16, i16, 100, 9, (int64_t)1 << 31, i16, p16, fws, l16) ==
+            GNNREC_EINVAL && err_has("int32"),
+        "frontier_mark n_dst range");
+  CHECK(FRONTIER(l16, 10, l16, i16, 100, 9, 7, i16, p16, fws, nullptr) == GNNREC_EINVAL &&
+            err_has("status"),
+        "frontier_mark null status");
+  CHECK(FRONTIER(nullptr, 10, l16, i16, 100, 9, 7, i16, p16, fws, l16) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "frontier_mark null rows");
+  CHECK(FRONTIER(l16, 10, l16, nullptr, 100, 9, 7, i16, p16, fws, l16) == GNNREC_EINVAL &&
+            err_has("null indices"),
+        "frontier_mark null indices");
+  CHECK(FRONTIER(l16, 10, l16, i16, 100, 9, 7, nullptr, p16, fws, l16) == GNNREC_EINVAL &&
+            err_has("mark"),
+        "frontier_mark null mark");
+  CHECK(FRONTIER(l16, 10, l16, i16, 100, 9, 7, i16, p16, fws - 1, l16) == GNNREC_EINVAL &&
+            err_has("workspace"),
+        "frontier_mark short workspace");
+#undef FRONTIER
+  CHECK(gnnrec_scatter_rows(p16, 16, l16, -1, 16, p16, 16, 5, nullptr) == GNNREC_EINVAL &&
+            err_has("negative"),
+        "scatter_rows negative n");
+  CHECK(gnnrec_scatter_rows(p16, 16, l16, 0, 16, p16, 16, 5, nullptr) == GNNREC_OK &&
+            gnnrec_scatter_rows(nullptr, 16, nullptr, 3, 16, nullptr, 16, 0, nullptr) == GNNREC_OK,
+        "scatter_rows empty problems");
+  CHECK(gnnrec_scatter_rows(p16, 16, nullptr, 3, 16, p16, 16, 5, nullptr) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "scatter_rows null idx");
+  CHECK(gnnrec_scatter_rows(p16, 8, l16, 3, 16, p16, 16, 5, nullptr) == GNNREC_EINVAL &&
+            err_has("row stride"),
+        "scatter_rows stride below the row width");
 }
 
 // the four fused aggregate+project entries (spmm_project.hip, spmm_pair_mfma.hip): every

@@ -4,43 +4,53 @@
 // Rows are moved in the widest unit their alignment allows (16, 8, 4 or 1 B), one
 // unit per thread, consecutive threads on consecutive units of a row — so a 512-B
 // feature row is one coalesced 16-B-per-lane sweep and 8-B edge ids pack 8 rows per
-// 64 B.
+// 64 B.  gnnrec_scatter_rows is the same kernel with the indexed side swapped: the write-back
+// of an incremental refresh's recomputed rows (inference.IncrementalEmbeddings).
 #include "common.hpp"
 
 namespace gnnrec {
 namespace {
 
-template <typename U>
+// SCATTER: the inverse, dst[idx[i]] = src[i] (gnnrec_scatter_rows) — the same sweep with the
+// indexed side swapped; a row whose id lies outside [0, bound) is skipped, never written.
+template <typename U, bool SCATTER>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const char* __restrict__ src,
                                                           int64_t src_ld,
                                                           const int64_t* __restrict__ idx,
                                                           int64_t n, int64_t units_per_row,
-                                                          char* __restrict__ dst, int64_t dst_ld) {
+                                                          char* __restrict__ dst, int64_t dst_ld,
+                                                          int64_t bound) {
   const int64_t total = n * units_per_row;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
        t += (int64_t)gridDim.x * blockDim.x) {
     const int64_t row = t / units_per_row, u = t - row * units_per_row;
     const int64_t r = idx[row];
-    U* d = reinterpret_cast<U*>(dst + row * dst_ld) + u;
-    if (r < 0) {  // a padding slot of a static-shape block: a zero row
-      *d = U{};
-      continue;
+    if constexpr (SCATTER) {
+      if (r < 0 || r >= bound) continue;
+      *(reinterpret_cast<U*>(dst + r * dst_ld) + u) =
+          *(reinterpret_cast<const U*>(src + row * src_ld) + u);
+    } else {
+      U* d = reinterpret_cast<U*>(dst + row * dst_ld) + u;
+      if (r < 0) {  // a padding slot of a static-shape block: a zero row
+        *d = U{};
+        continue;
+      }
+      *d = *(reinterpret_cast<const U*>(src + r * src_ld) + u);
     }
-    *d = *(reinterpret_cast<const U*>(src + r * src_ld) + u);
   }
 }
 
-template <typename U>
+template <typename U, bool SCATTER = false>
 int launch(const void* src, int64_t src_ld, const int64_t* idx, int64_t n, int64_t row_bytes,
-           void* dst, int64_t dst_ld, hipStream_t s) {
+           void* dst, int64_t dst_ld, hipStream_t s, int64_t bound = 0) {
   const int64_t upr = row_bytes / (int64_t)sizeof(U);
   const int64_t total = n * upr;
   int64_t blocks = (total + 255) / 256;
   if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(gather_rows_kernel<U>, dim3((unsigned)blocks), dim3(256), 0, s,
+  hipLaunchKernelGGL((gather_rows_kernel<U, SCATTER>), dim3((unsigned)blocks), dim3(256), 0, s,
                      static_cast<const char*>(src), src_ld, idx, n, upr, static_cast<char*>(dst),
-                     dst_ld);
-  return check_launch("gnnrec_gather_rows");
+                     dst_ld, bound);
+  return check_launch(SCATTER ? "gnnrec_scatter_rows" : "gnnrec_gather_rows");
 }
 
 }  // namespace
@@ -63,6 +73,26 @@ extern "C" int gnnrec_gather_rows(const void* src, int64_t src_ld_bytes, const i
   if ((al & 7u) == 0) return launch<uint64_t>(src, src_ld_bytes, idx, n, row_bytes, dst, dst_ld_bytes, s);
   if ((al & 3u) == 0) return launch<uint32_t>(src, src_ld_bytes, idx, n, row_bytes, dst, dst_ld_bytes, s);
   return launch<uint8_t>(src, src_ld_bytes, idx, n, row_bytes, dst, dst_ld_bytes, s);
+}
+
+extern "C" int gnnrec_scatter_rows(const void* src, int64_t src_ld_bytes, const int64_t* idx,
+                                   int64_t n, int64_t row_bytes, void* dst, int64_t dst_ld_bytes,
+                                   int64_t dst_rows, void* stream) {
+  GNNREC_REQUIRE(n >= 0 && row_bytes >= 0 && dst_rows >= 0, "gnnrec_scatter_rows: negative size");
+  if (n == 0 || row_bytes == 0 || dst_rows == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(src && idx && dst, "gnnrec_scatter_rows: null pointer");
+  GNNREC_REQUIRE(src_ld_bytes >= row_bytes && dst_ld_bytes >= row_bytes,
+                 "gnnrec_scatter_rows: row stride below the row width");
+  const uintptr_t al = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) |
+                       (uintptr_t)src_ld_bytes | (uintptr_t)dst_ld_bytes | (uintptr_t)row_bytes;
+  hipStream_t s = as_stream(stream);
+  if ((al & 15u) == 0)
+    return launch<uint4, true>(src, src_ld_bytes, idx, n, row_bytes, dst, dst_ld_bytes, s, dst_rows);
+  if ((al & 7u) == 0)
+    return launch<uint64_t, true>(src, src_ld_bytes, idx, n, row_bytes, dst, dst_ld_bytes, s, dst_rows);
+  if ((al & 3u) == 0)
+    return launch<uint32_t, true>(src, src_ld_bytes, idx, n, row_bytes, dst, dst_ld_bytes, s, dst_rows);
+  return launch<uint8_t, true>(src, src_ld_bytes, idx, n, row_bytes, dst, dst_ld_bytes, s, dst_rows);
 }
 
 // ---- many gathers in one launch (a sampled batch's edge data + input features) ----

@@ -1397,6 +1397,36 @@ void csr_add_edges(const Tensor& indptr, const Tensor& indices, const Tensor& ei
      "gnnrec_csr_add_edges");
 }
 
+// the destinations of the out-edges of the listed source rows, as marks (frontier.hip)
+void frontier_mark(const Tensor& rows, const optional<Tensor>& n_rows, const Tensor& indptr,
+                   const Tensor& indices, Tensor& mark, Tensor& ws, Tensor& status) {
+  const OneDevice one_device_;
+  dev(rows, "rows", at::kLong);
+  dev(n_rows, "n_rows", at::kLong);
+  dev(indptr, "indptr", at::kLong);
+  dev(indices, "indices", at::kInt);
+  dev(mark, "mark", at::kInt);
+  dev(ws, "workspace", at::kByte);
+  dev(status, "status", at::kLong);
+  TORCH_CHECK_VALUE(rows.dim() == 1 && rows.is_contiguous(),
+                    "frontier_mark: rows must be a contiguous 1-D tensor");
+  TORCH_CHECK_VALUE(!has(n_rows) || n_rows->numel() == 1,
+                    "frontier_mark: n_rows is one device count");
+  TORCH_CHECK_VALUE(indptr.dim() == 1 && indptr.numel() >= 1 && indices.dim() == 1 &&
+                        indptr.is_contiguous() && indices.is_contiguous(),
+                    "frontier_mark: the CSR must be indptr [n_src+1], indices [E], contiguous");
+  TORCH_CHECK_VALUE(mark.dim() == 1 && mark.is_contiguous() && status.numel() == 2 &&
+                        status.is_contiguous(),
+                    "frontier_mark: mark [n_dst] and status [2], contiguous");
+  if (meta(rows)) return;
+  const c10::DeviceGuard g(rows.device());
+  ck(gnnrec_frontier_mark(p<int64_t>(rows), rows.numel(), p<int64_t>(n_rows), p<int64_t>(indptr),
+                          p<int32_t>(indices), indices.numel(), indptr.numel() - 1, mark.numel(),
+                          p<int32_t>(mark), ws.data_ptr(), ws.nbytes(), p<int64_t>(status),
+                          stream_of(rows)),
+     "gnnrec_frontier_mark");
+}
+
 // ---------------------------------------------------------------- f2 fused relation
 // One ConvLayer relation of a TRAINING step (sum / mean aggregation), forward and backward
 // each as ONE dispatcher call that issues every launch from C++ (gnnrec/autograd.py
@@ -2179,6 +2209,9 @@ int64_t csr_remove_edges_workspace_bytes(int64_t E, int64_t n_dst) {
 int64_t csr_add_edges_workspace_bytes(int64_t n_new, int64_t n_dst) {
   return (int64_t)gnnrec_csr_add_edges_workspace_bytes(n_new, n_dst);
 }
+int64_t frontier_mark_workspace_bytes(int64_t n_rows) {
+  return (int64_t)gnnrec_frontier_mark_workspace_bytes(n_rows);
+}
 int64_t sddmm_cos_backward_workspace_bytes(int64_t E, int64_t n_src, int64_t n_dst, int64_t d,
                                            int64_t groups, int64_t K) {
   if (groups > 0)
@@ -2302,6 +2335,8 @@ TORCH_LIBRARY(gnnrec, m) {
   m.def("csr_add_edges(Tensor indptr, Tensor indices, Tensor eids, Tensor src_new, "
         "Tensor dst_new, int n_src, int n_dst, Tensor(a!) workspace, Tensor(b!) indptr_out, "
         "Tensor(c!) indices_out, Tensor(d!) eids_out, Tensor(e!) status) -> ()");
+  m.def("frontier_mark(Tensor rows, Tensor? n_rows, Tensor indptr, Tensor indices, "
+        "Tensor(a!) mark, Tensor(b!) workspace, Tensor(c!) status) -> ()");
   m.def("add_(Tensor(a!) a, Tensor b) -> ()");
   m.def("tree_sum_(Tensor(a!) a, Tensor[] rest) -> ()");
   m.def("lstm_step(Tensor P, Tensor indptr, Tensor indices, Tensor order, int t, int n_act, "
@@ -2369,6 +2404,7 @@ TORCH_LIBRARY(gnnrec, m) {
         &csr_remove_edges_workspace_bytes);
   m.def("csr_add_edges_workspace_bytes(int n_new, int n_dst) -> int",
         &csr_add_edges_workspace_bytes);
+  m.def("frontier_mark_workspace_bytes(int n_rows) -> int", &frontier_mark_workspace_bytes);
   m.def("sddmm_cos_backward_workspace_bytes(int n_edges, int n_src, int n_dst, int d, "
         "int groups=0, int K=0) -> int", &sddmm_cos_backward_workspace_bytes);
   m.def("margin_loss_blocks(int n_pos) -> int", &margin_loss_blocks);
@@ -2423,6 +2459,7 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("csr_build", &csr_build);                       \
   m.impl("csr_remove_edges", &csr_remove_edges);         \
   m.impl("csr_add_edges", &csr_add_edges);               \
+  m.impl("frontier_mark", &frontier_mark);               \
   m.impl("add_", &add_);                                 \
   m.impl("tree_sum_", &tree_sum_);                       \
   m.impl("lstm_step", &lstm_step);                       \

@@ -350,6 +350,38 @@ void gather_rows(const Tensor& src, const Tensor& idx, Tensor& out) {
      "gnnrec_gather_rows");
 }
 
+// the inverse: dst[idx[i]] = src[i] (idx strictly ascending; ids outside dst's rows are skipped)
+void scatter_rows(const Tensor& src, const Tensor& idx, Tensor& dst) {
+  const OneDevice one_device_;
+  dev(idx, "idx", at::kLong);
+  TORCH_CHECK_VALUE(src.is_cuda() || src.is_meta(),
+                    "src: expected a device tensor (there is no CPU path)");
+  same_dev(src, "src");
+  same_dev(dst, "dst");
+  TORCH_CHECK_VALUE(src.dim() >= 1 && dst.dim() == src.dim() &&
+                        dst.scalar_type() == src.scalar_type() && idx.is_contiguous() &&
+                        src.size(0) == idx.numel() && src.is_contiguous(),
+                    "scatter_rows: src [n, ...] contiguous, of dst's dtype and rank, contiguous "
+                    "idx [n]");
+  int64_t inner = 1;
+  for (int64_t k = dst.dim() - 1; k >= 1; --k) {
+    TORCH_CHECK_VALUE(dst.size(k) == src.size(k), "scatter_rows: row shapes differ");
+    TORCH_CHECK_VALUE(dst.size(k) <= 1 || dst.stride(k) == inner,
+                      "scatter_rows: dst rows must be contiguous (stride ", dst.stride(k),
+                      " in dim ", k, ")");
+    inner *= dst.size(k);
+  }
+  TORCH_CHECK_VALUE(dst.size(0) <= 1 || dst.stride(0) >= inner,
+                    "scatter_rows: dst rows overlap");
+  if (meta(src)) return;
+  const c10::DeviceGuard g(src.device());
+  const int64_t es = src.element_size();
+  ck(gnnrec_scatter_rows(src.data_ptr(), inner * es, p<int64_t>(idx), idx.numel(), inner * es,
+                         dst.data_ptr(), (dst.size(0) > 1 ? dst.stride(0) : inner) * es,
+                         dst.size(0), stream_of(src)),
+     "gnnrec_scatter_rows");
+}
+
 // several row gathers in one launch (gnnrec_gather_rows_batch): out[j] = src[j][idx[j]]
 void gather_rows_batch(at::TensorList src, at::TensorList idx, at::TensorList out,
                        at::TensorList n_dev) {
@@ -826,6 +858,7 @@ TORCH_LIBRARY_FRAGMENT(gnnrec, m) {
   m.def("set_prefix_pos(Tensor prefix, Tensor(a!) prefix_pos) -> ()");
   m.def("clear_prefix_pos(Tensor prefix, Tensor(a!) prefix_pos) -> ()");
   m.def("gather_rows(Tensor src, Tensor idx, Tensor(a!) out) -> ()");
+  m.def("scatter_rows(Tensor src, Tensor idx, Tensor(a!) dst) -> ()");
   m.def("edge_batch_pairs(Tensor[] rel_src, Tensor[] rel_dst, int[] src_type, int[] dst_type, "
         "Tensor[] batch, int[] neg_order, int K, int[] n_nodes, Tensor[] prefix_pos, "
         "Tensor[] marks) -> (Tensor[], Tensor[], Tensor[], Tensor[], Tensor[])");
@@ -859,6 +892,7 @@ TORCH_LIBRARY_FRAGMENT(gnnrec, m) {
   m.impl("set_prefix_pos", &set_prefix_pos);             \
   m.impl("clear_prefix_pos", &clear_prefix_pos);         \
   m.impl("gather_rows", &gather_rows);                   \
+  m.impl("scatter_rows", &scatter_rows);                 \
   m.impl("gather_rows_batch", &gather_rows_batch)
 
 // HIP tensors dispatch under the CUDA key in ROCm PyTorch.

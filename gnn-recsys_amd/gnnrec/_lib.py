@@ -125,6 +125,7 @@ SIGNATURES = {
                                     _I64, _P, _I64, _P, _I64, _I64, _INT, _INT, _P, _F32,
                                     _P, _I64, _P]),
     "gnnrec_gather_rows": (_INT, [_P, _I64, _P, _I64, _I64, _P, _I64, _P]),
+    "gnnrec_scatter_rows": (_INT, [_P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P]),
     "gnnrec_gather_rows_batch": (_INT, [_P, _INT, _P]),
     "gnnrec_copy_batch": (_INT, [_P, _P, _P, _INT, _P]),
     # (plan*, seed_cap*, edge_cap*, node_cap*, workspace_bytes*) / (plan*, stream)
@@ -147,6 +148,10 @@ SIGNATURES = {
     #  status, stream)
     "gnnrec_csr_add_edges": (_INT, [_P, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _U64,
                                     _P, _P, _P, _P, _P]),
+    "gnnrec_frontier_mark_workspace_bytes": (_U64, [_I64]),
+    # (rows, n, n_dev, indptr, indices, E, n_src, n_dst, mark, ws, ws_bytes, status, stream)
+    "gnnrec_frontier_mark": (_INT, [_P, _I64, _P, _P, _P, _I64, _I64, _I64, _P, _P, _U64, _P,
+                                    _P]),
     "gnnrec_csr_has_edges": (_INT, [_P, _P, _I64, _I64, _P, _P, _I64, _P, _P]),
     "gnnrec_add_f32": (_INT, [_P, _P, _P, _I64, _P]),
     "gnnrec_tree_sum_f32": (_INT, [_P, _INT, _I64, _P, _P]),

@@ -25,14 +25,16 @@ collectives overlap the user-side aggregation (async RCCL work handles).
 """
 from __future__ import annotations
 
+import contextlib
 import os
+import time
 from typing import Dict, List, Optional
 
 import torch
 
 from . import _lib, ops
 from .dist import Exchange, degree_ranges, even_ranges, multi_rank, padded_shard
-from .graph import HeteroGraph, build_csr
+from .graph import HeteroGraph, LazyRows, RelGraph, _FrameDict, build_csr
 
 
 # --------------------------------------------------------- single process ---
@@ -65,6 +67,449 @@ def get_embeddings(g, out_dim: int, trained_model, nodeloader_test, num_batches_
         for ntype in h.keys():
             y[ntype][output_nodes[ntype]] = h[ntype]
     return y
+
+
+# ------------------------------------------------ incremental refresh (§21) ---
+class RefreshStats:
+    """What one IncrementalEmbeddings.refresh() did.  rows[l][ntype]: rows of layer l's table
+    recomputed (l = 0: re-embedded input rows; the table's row count where the whole layer
+    ran); whole_layer[l][ntype]: the whole layer ran for that type instead of the row path;
+    whole_pass: the full pass ran (first use, invalidate(), a changed weight or a relation
+    whose kernel route changed)."""
+
+    def __init__(self, n_layers: int, whole_pass: bool = False):
+        self.rows: List[Dict[str, int]] = [{} for _ in range(n_layers + 1)]
+        self.whole_layer: List[Dict[str, bool]] = [{} for _ in range(n_layers + 1)]
+        self.whole_pass = whole_pass
+
+    def __repr__(self):
+        return (f"RefreshStats(whole_pass={self.whole_pass}, rows={self.rows}, "
+                f"whole_layer={self.whole_layer})")
+
+
+class _TypeView:
+    """The graph interface HeteroGraphConv.forward reads, over the relations INTO one node
+    type: the whole graph's relation list and edge counts (so the same relations are active
+    and the two-relation launch fires as in the whole pass) with the RelGraphs handed in —
+    the whole relations, or the CSR rows of a dirty list."""
+
+    is_block = True
+
+    def __init__(self, g: HeteroGraph, rels: Dict[tuple, RelGraph]):
+        self._g, self._rels = g, rels
+        self.canonical_etypes = [ce for ce in g.canonical_etypes if ce in rels]
+
+    def num_edges(self, ce) -> int:
+        return self._g.num_edges(ce)
+
+    def rel_graph(self, ce) -> RelGraph:
+        return self._rels[ce]
+
+
+class _Dirty:
+    """D_l of one node type: its marks, and the ascending id list unless it is every row."""
+
+    __slots__ = ("mark", "ids", "count", "all", "huge")
+
+    def __init__(self, mark, ids, count: int, all_rows: bool):
+        self.mark, self.ids, self.count, self.all = mark, ids, count, all_rows
+        self.huge = False  # a dirty row above ROW_PATH_MAX_DEG in-edges in some relation
+
+
+# Largest dirty share of a layer's rows at which the row path still beat the whole layer in
+# every run of the threshold sweep: 0.5 won (13.0 against 14.9 ms), 0.75 lost
+# (profiles/refresh_ab.md; DESIGN §21)
+DEFAULT_MAX_DIRTY_FRAC = 0.5
+# A dirty row with more in-edges than this sends its type to the whole layer: the row
+# extraction (the sampler's count / fill) copies a row with one wave, and a Zipf head item's
+# 34.7M-edge row alone took 620 ms that way (profiles/refresh_ab.md)
+ROW_PATH_MAX_DEG = 1 << 18
+
+
+class IncrementalEmbeddings:
+    """full_graph_embeddings kept up to date under graph edits by recomputing only the rows an
+    edit can reach.  One device, one process, model.eval().
+
+        inc = IncrementalEmbeddings(g, model)      # runs the full pass once
+        inc.add_edges(u, v, etype='buys'); inc.add_edges(v, u, etype='bought-by')
+        stats = inc.refresh()                      # inc.h is what a fresh full pass gives
+
+    layers = [h0, ..., hL] as {ntype: table}; h0 = model.embed(feats) (or the feature tables
+    themselves without an embedding layer), h = layers[-1].  After refresh() every table is
+    torch.equal to the same layer of a full pass over a freshly built graph with the same
+    edges.  refresh() writes the tables IN PLACE, so a consumer holding inc.h['user'] sees the
+    new rows; only add_nodes replaces the tables of its type (one concatenation each).
+
+    The mutation methods wrap the HeteroGraph calls of the same name (same arguments and
+    errors; a call that raises records nothing) and record on the device what they touched.
+    Both directions of a relation pair are edited with two calls, as on the graph.  A caller
+    who edits the graph directly names the rows with mark().  feats given explicitly: the
+    tables set_features / add_nodes maintain are those (the graph's 'features' otherwise).
+
+    Dirty sets: S[T] rows whose input changed or that were added, E[T] destinations of an
+    added / removed edge or rows named by mark(); D_0 = S, D_l[T] = D_{l-1}[T] | E[T] |
+    out_R(D_{l-1}[A]) over every relation R: A -> T of the edited graph.  Layer l recomputes
+    exactly D_l[T], through a CSR of those rows that takes the whole relation's kernel route
+    (ops.Route).  Above max_dirty_frac of a type's rows (0: always; 1: never) the whole layer
+    runs for that type and D_l[T] becomes every row; an LSTM reducer always takes the whole
+    layer (its step order depends on the whole relation's degree order), and so does a type
+    with a dirty row above ROW_PATH_MAX_DEG in-edges (D_l[T] stays as it is).  The whole pass
+    runs when a model parameter changed (ops._wkey), after invalidate(), or when an edit
+    moved a relation across a routing threshold (edges per row, the pre-projection's row
+    ratio, a heavy row, empty / non-empty)."""
+
+    def __init__(self, g: HeteroGraph, model, feats: Optional[Dict[str, torch.Tensor]] = None,
+                 embedding_layer: Optional[bool] = None,
+                 max_dirty_frac: Optional[float] = None):
+        if not isinstance(g, HeteroGraph) or torch.device(g.device).type != 'cuda':
+            raise ValueError("IncrementalEmbeddings: expected a graph on a HIP device (there is "
+                             "no CPU path)")
+        self._own_feats = feats is not None
+        feats = dict(feats) if feats is not None else g.ndata['features']
+        for nt, t in feats.items():
+            if not t.is_cuda:
+                raise ValueError(f"IncrementalEmbeddings: feats[{nt!r}]: expected a device "
+                                 f"tensor (there is no CPU path)")
+        if model.training:
+            raise ValueError("IncrementalEmbeddings: model.eval() first (inference only)")
+        self.g, self.model = g, model
+        self._feats = feats
+        self.embedding_layer = model.embedding_layer if embedding_layer is None \
+            else bool(embedding_layer)
+        self.max_dirty_frac = DEFAULT_MAX_DIRTY_FRAC if max_dirty_frac is None \
+            else float(max_dirty_frac)
+        if not 0.0 <= self.max_dirty_frac <= 1.0:
+            raise ValueError("IncrementalEmbeddings: max_dirty_frac must lie in [0, 1]")
+        dev = g.device
+        self._S = {nt: torch.zeros(g.num_nodes(nt), dtype=torch.int32, device=dev)
+                   for nt in g.ntypes}
+        self._E = {nt: torch.zeros_like(m) for nt, m in self._S.items()}
+        # gnnrec_mark_ids' prefix table: nothing is a prefix node here
+        self._prefix = {nt: torch.full((g.num_nodes(nt),), -1, dtype=torch.int64, device=dev)
+                        for nt in g.ntypes}
+        self.layers: List[Dict[str, torch.Tensor]] = []
+        self._stale, self._dirty = True, False
+        self._keys = self._routes = None
+        self._huge: Dict[tuple, torch.Tensor] = {}
+        self.phase_ms: Optional[dict] = None
+        self.refresh()
+
+    @property
+    def h(self) -> Dict[str, torch.Tensor]:
+        return self.layers[-1]
+
+    # ---- recording ----------------------------------------------------------
+    def _ids(self, ids, n: int, what: str) -> torch.Tensor:
+        ids = torch.as_tensor(ids, dtype=torch.int64, device=self.g.device).reshape(-1)
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n):
+            raise ValueError(f"{what}: an id lies outside [0, {n})")
+        return ids.contiguous()
+
+    def _record(self, store, ntype: str, ids: torch.Tensor) -> None:
+        """ids (validated, on the device) into the type's seed marks: no host synchronisation."""
+        if ids.numel():
+            _lib.torch_ops().mark_ids(ids, self._prefix[ntype], store[ntype])
+            self._dirty = True
+
+    def add_edges(self, u, v, data=None, etype=None) -> None:
+        """HeteroGraph.add_edges, and the destinations recorded."""
+        g = self.g
+        g.add_edges(u, v, data=data, etype=etype)
+        ce = g.to_canonical_etype(etype if etype is not None else g.canonical_etypes[0])
+        v = torch.as_tensor(v, dtype=torch.int64, device=g.device).reshape(-1)
+        self._record(self._E, ce[2], v.contiguous())
+
+    def remove_edges(self, eids, etype=None) -> None:
+        """HeteroGraph.remove_edges, and the removed edges' destinations (read before the
+        removal) recorded."""
+        g = self.g
+        if etype is None and len(g.canonical_etypes) != 1:
+            raise ValueError("remove_edges: etype is needed on a graph with several relations")
+        ce = g.to_canonical_etype(etype if etype is not None else g.canonical_etypes[0])
+        E = g.num_edges(ce)
+        rm = torch.as_tensor(eids, dtype=torch.int64, device=g.device).reshape(-1)
+        if rm.numel() and (int(rm.min()) < 0 or int(rm.max()) >= E):
+            raise ValueError(f"remove_edges: an edge id lies outside [0, {E})")
+        v = ops.gather_rows(g.all_edges(etype=ce)[1], rm.contiguous()) if rm.numel() else rm
+        g.remove_edges(rm, etype=ce)
+        self._record(self._E, ce[2], v)
+
+    def add_nodes(self, num: int, data=None, ntype=None) -> None:
+        """HeteroGraph.add_nodes; the type's cached tables, marks and (own) feature table
+        grow by `num` rows — one concatenation each, the only call that REPLACES tables —
+        and the new rows are recorded as changed inputs."""
+        g = self.g
+        g.add_nodes(num, data=data, ntype=ntype)
+        num = int(num)
+        if num == 0:
+            return
+        nt = ntype if ntype is not None else g.ntypes[0]
+        N, dev = g.num_nodes(nt) - num, g.device
+        if self._own_feats:
+            if nt in self._feats:
+                cur = self._feats[nt]
+                new = (data or {}).get('features')
+                new = cur.new_zeros((num,) + tuple(cur.shape[1:])) if new is None else \
+                    torch.as_tensor(new, dtype=cur.dtype, device=dev)
+                self._feats[nt] = torch.cat([cur, new])
+        else:
+            self._feats = g.ndata['features']
+        for tables in self.layers[1 if not self.embedding_layer else 0:]:
+            if nt in tables:
+                t = tables[nt]
+                tables[nt] = torch.cat([t, t.new_zeros((num,) + tuple(t.shape[1:]))])
+        if not self.embedding_layer and self.layers:
+            self.layers[0] = dict(self._feats)
+        for store in (self._S, self._E):
+            store[nt] = torch.cat([store[nt], store[nt].new_zeros(num)])
+        self._prefix[nt] = torch.cat([self._prefix[nt], self._prefix[nt].new_full((num,), -1)])
+        self._record(self._S, nt, torch.arange(N, N + num, dtype=torch.int64, device=dev))
+
+    def set_features(self, ntype: str, ids, rows) -> None:
+        """feats[ntype][ids] = rows (distinct ids), recorded as changed inputs."""
+        if ntype not in self._feats:
+            raise ValueError(f"set_features: no features of node type {ntype!r}")
+        table = self._feats[ntype]
+        ids = self._ids(ids, table.shape[0], "set_features")
+        rows = torch.as_tensor(rows, dtype=table.dtype, device=table.device)
+        if tuple(rows.shape) != (ids.numel(),) + tuple(table.shape[1:]):
+            raise ValueError(f"set_features: rows must be {(ids.numel(),) + tuple(table.shape[1:])}"
+                             f", got {tuple(rows.shape)}")
+        table.index_copy_(0, ids, rows)
+        self._record(self._S, ntype, ids)
+
+    def mark(self, ntype: str, ids, inputs: bool = False) -> None:
+        """The caller edited the graph directly: the in-edges of these rows changed (and, with
+        inputs=True, their input features: the rows are re-embedded too)."""
+        if ntype not in self._S:
+            raise ValueError(f"mark: no node type {ntype!r}")
+        ids = self._ids(ids, self._S[ntype].numel(), "mark")
+        self._record(self._E, ntype, ids)
+        if inputs:
+            self._record(self._S, ntype, ids)
+
+    def invalidate(self) -> None:
+        """The next refresh() runs the whole pass."""
+        self._stale = True
+
+    # ---- refresh --------------------------------------------------------------
+    def _weight_keys(self):
+        return tuple(ops._wkey(p) for p in self.model.parameters())
+
+    def _relation_routes(self):
+        """Per relation, the whole CSR's Route and what of it the kernel choice reads."""
+        g, routes, sig = self.g, {}, {}
+        for ce in g.canonical_etypes:
+            if g.num_edges(ce) == 0:
+                sig[ce] = None
+                continue
+            ip = g.in_csr(ce)[0]
+            r = ops.relation_route(ip)
+            routes[ce] = r
+            self._huge.pop(ce, None)
+            if r.has_split:  # the heavy rows are listed already: those above the cap
+                heavy = ops.split_plan(ip, ops.DEFAULT_SPLIT)[0]
+                huge = heavy[(ip[heavy + 1] - ip[heavy]) > ROW_PATH_MAX_DEG]
+                if huge.numel():
+                    self._huge[ce] = huge
+            sig[ce] = (r.avg_deg >= ops.FUSED_MIN_DEG, 2 * g.num_nodes(ce[0]) <= r.n_dst,
+                       r.has_split)
+        return routes, sig
+
+    def _embed_rows(self, nt: str, x: torch.Tensor) -> torch.Tensor:
+        mod = getattr(self.model, nt + "_embed", None) if nt in ('user', 'item', 'sport') else None
+        return x if mod is None else mod(x)
+
+    def _full_pass(self) -> RefreshStats:
+        g, model = self.g, self.model
+        if not self._own_feats:
+            self._feats = g.ndata['features']
+        h = model.embed(self._feats) if self.embedding_layer else dict(self._feats)
+        new = [h]
+        for layer in model.layers:
+            h = layer(g, h)
+            new.append(h)
+        stats = RefreshStats(len(model.layers), whole_pass=True)
+        for l, tables in enumerate(new):
+            old = self.layers[l] if l < len(self.layers) else {}
+            for nt, t in tables.items():
+                if (l > 0 or self.embedding_layer) and nt in old and old[nt].shape == t.shape:
+                    tables[nt] = old[nt].copy_(t)  # in place: a held table sees the new rows
+                stats.rows[l][nt] = int(t.shape[0])
+                stats.whole_layer[l][nt] = True
+        self.layers = new
+        return stats
+
+    def _scan_counts(self, marks, statuses=(), extra=()):
+        """Ranks of every type's marks and, in ONE transfer, their counts, the status words
+        of the frontier calls and the one-element tensors of `extra`."""
+        ranks = {nt: ops.exclusive_scan(m) for nt, m in marks.items()}
+        words = torch.cat([r[-1:] for r in ranks.values()] + [s for s, _a, _b in statuses] +
+                          [t.to(torch.int64) for t in extra]).tolist()
+        n = len(ranks)
+        for i, (_s, n_src, n_dst) in enumerate(statuses):
+            ops.frontier_status(words[n + 2 * i:n + 2 * i + 2], n_src, n_dst)
+        return ranks, dict(zip(ranks.keys(), words[:n])), words[n + 2 * len(statuses):]
+
+    def _dirty_sets(self, marks, ranks, counts):
+        """{ntype: _Dirty} of one layer; a type above max_dirty_frac becomes every row."""
+        T, out, frac = _lib.torch_ops(), {}, self.max_dirty_frac
+        for nt, m in marks.items():
+            n, c = m.numel(), counts[nt]
+            if c > 0 and (frac == 0.0 or c > frac * n):
+                out[nt] = _Dirty(m.fill_(1), None, n, True)
+                continue
+            ids = torch.empty(c, dtype=torch.int64, device=m.device)
+            if c:
+                T.compact_marked(m, ranks[nt], ids)
+            out[nt] = _Dirty(m, ids, c, False)
+        return out
+
+    def _row_rels(self, todo, routes):
+        """The CSR rows of every (type, dirty list) of one layer, per relation into the type,
+        with global source ids and ONE transfer for all their sizes."""
+        g, T = self.g, _lib.torch_ops()
+        jobs = []
+        for nt, rows, ces in todo:
+            for ce in ces:
+                ip, _ix, eid = g.in_csr(ce)
+                jobs.append((nt, ce, rows, ops.sample_count(ip, eid, rows, -1)))
+        totals = torch.cat([o[-1:] for *_k, o in jobs]).tolist() if jobs else []
+        rels: Dict[str, Dict[tuple, RelGraph]] = {}
+        for (nt, ce, rows, o_ip), total in zip(jobs, totals):
+            ip, ix, eid = g.in_csr(ce)
+            dev = rows.device
+            # (a slice of a non-empty buffer: a relation whose dirty rows have no in-edge
+            # still runs for its self term, and the launch wants non-null arrays)
+            src = torch.empty(max(total, 1), dtype=torch.int64, device=dev)[:total]
+            sub_eid = torch.empty(max(total, 1), dtype=torch.int64, device=dev)[:total]
+            if total:
+                T.sample_fill(ip, ix, eid, None, rows, -1, 0, o_ip, src, sub_eid, None)
+            sub_ix = torch.empty(max(total, 1), dtype=torch.int32, device=dev)[:total]
+            sub_ix.copy_(src)
+            ops.pin_route(o_ip, routes[ce], total)
+            edata = _FrameDict({k: LazyRows(v, sub_eid) for k, v in g._edata[ce].lazy_items()
+                                if not isinstance(v, LazyRows)})
+            rels.setdefault(nt, {})[ce] = RelGraph(ce, o_ip, sub_ix, g.num_nodes(ce[0]),
+                                                   rows.numel(), edata, sub_eid)
+        return rels
+
+    def _next_dirty(self, D):
+        """D_l from D_{l-1}: D_l[T] = D_{l-1}[T] | E[T] | out_R(D_{l-1}[A]) over the relations
+        R: A -> T.  One transfer: every type's count and every frontier call's status."""
+        g = self.g
+        marks = {nt: torch.bitwise_or(d.mark, self._E[nt]) for nt, d in D.items()}
+        statuses = []
+        for ce in g.canonical_etypes:
+            a = D[ce[0]]
+            if g.num_edges(ce) == 0 or a.count == 0:
+                continue
+            if a.all:  # every source row: the destinations with an in-edge
+                ip = g.in_csr(ce)[0]
+                marks[ce[2]] |= (ip[1:] > ip[:-1]).to(torch.int32)
+            else:
+                oip, oix, _ = g.out_csr(ce)
+                statuses.append((ops.frontier_mark(a.ids, oip, oix, marks[ce[2]], check=False),
+                                 oip.numel() - 1, marks[ce[2]].numel()))
+        huge = [(ce[2], marks[ce[2]][rows].sum().reshape(1)) for ce, rows in self._huge.items()]
+        ranks, counts, hit = self._scan_counts(marks, statuses, [t for _nt, t in huge])
+        D = self._dirty_sets(marks, ranks, counts)
+        for (nt, _t), v in zip(huge, hit):
+            D[nt].huge |= bool(v)
+        return D
+
+    @contextlib.contextmanager
+    def _phase(self, name: str):
+        """With `phase_ms` set to a dict (a measurement, tools/bench_refresh.py): the part's
+        time between two device synchronisations, added to phase_ms[name]."""
+        if self.phase_ms is None:
+            yield
+            return
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        try:
+            yield
+        finally:
+            torch.cuda.synchronize()
+            self.phase_ms[name] = self.phase_ms.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
+
+    @torch.no_grad()
+    def refresh(self) -> RefreshStats:
+        """Bring every table of `layers` up to date with the graph, the features and the
+        recorded edits; -> RefreshStats."""
+        g, model = self.g, self.model
+        if model.training:
+            raise ValueError("IncrementalEmbeddings.refresh: model.eval() first")
+        L = len(model.layers)
+        full = self._stale or self._weight_keys() != self._keys
+        if not full and not self._dirty:
+            return RefreshStats(L)
+        with self._phase("routes"):
+            routes, sig = self._relation_routes()
+        if full or sig != self._routes:
+            stats = self._full_pass()
+            self._keys, self._routes = self._weight_keys(), sig
+            return self._clean(stats)
+        stats = RefreshStats(L)
+        # D_0 = S: re-embed
+        with self._phase("marks"):
+            marks = {nt: m.clone() for nt, m in self._S.items()}
+            ranks, counts, _ = self._scan_counts(marks)
+            D = self._dirty_sets(marks, ranks, counts)
+        for nt, d in D.items():
+            if nt not in self.layers[0] or d.count == 0:
+                continue
+            stats.rows[0][nt], stats.whole_layer[0][nt] = d.count, d.all
+            if not self.embedding_layer:
+                continue  # h0 IS the feature table
+            table = self.layers[0][nt]
+            if d.all:
+                with self._phase("layers"):
+                    table.copy_(self._embed_rows(nt, self._feats[nt]))
+                continue
+            with self._phase("rows"):
+                x = ops.gather_rows(self._feats[nt], d.ids)
+            with self._phase("layers"):
+                x = self._embed_rows(nt, x)
+            with self._phase("rows"):
+                ops.scatter_rows(table, d.ids, x)
+        for l, layer in enumerate(model.layers, start=1):
+            h_prev, tables = self.layers[l - 1], self.layers[l]
+            with self._phase("marks"):
+                D = self._next_dirty(D)
+            todo = []
+            for nt, d in D.items():
+                if nt not in tables or d.count == 0:
+                    continue
+                ces = [ce for ce in g.canonical_etypes
+                       if ce[2] == nt and g.num_edges(ce) and ce[0] in h_prev]
+                whole = d.all or d.huge or any(
+                    layer.mods[ce[1]]._aggre_type.startswith('lstm') for ce in ces)
+                stats.whole_layer[l][nt] = whole
+                stats.rows[l][nt] = tables[nt].shape[0] if whole else d.count
+                if whole:
+                    with self._phase("layers"):
+                        view = _TypeView(g, {ce: g.rel_graph(ce) for ce in ces})
+                        tables[nt].copy_(layer(view, (h_prev, {nt: h_prev[nt]}))[nt])
+                else:
+                    todo.append((nt, d.ids, ces))
+            with self._phase("rows"):
+                subs = self._row_rels(todo, routes)
+                selfs = {nt: ops.gather_rows(h_prev[nt], D[nt].ids) for nt in subs}
+            with self._phase("layers"):
+                outs = {nt: layer(_TypeView(g, sub), (h_prev, {nt: selfs[nt]}))[nt]
+                        for nt, sub in subs.items()}
+            with self._phase("rows"):
+                for nt, out in outs.items():
+                    ops.scatter_rows(tables[nt], D[nt].ids, out)
+        return self._clean(stats)
+
+    def _clean(self, stats: RefreshStats) -> RefreshStats:
+        for store in (self._S, self._E):
+            for m in store.values():
+                m.zero_()
+        self._stale = self._dirty = False
+        return stats
 
 
 # ------------------------------------------------------------- sharded ------

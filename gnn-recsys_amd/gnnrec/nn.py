@@ -136,7 +136,8 @@ class ConvLayer(nn.Module):
         h_neigh, h_self = x
         preagg, weighted, reduce = self._plan(graph)
         if reduce not in ('sum', 'mean') or self._dropout_active() or \
-                not ops.preproject_pays(h_neigh.shape[0], graph.n_dst, reduce):
+                not ops.preproject_pays(h_neigh.shape[0],
+                                        ops.routed_n_dst(graph.indptr, graph.n_dst), reduce):
             return None
         m = ops.gemm(h_neigh, self.fc_preagg.weight, relu=True) if preagg else h_neigh
         if not ops.can_spmm_project(graph.indptr, m, h_self, self.fc_self.weight,

@@ -13,7 +13,7 @@ import collections
 import contextlib
 import os
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -394,6 +394,44 @@ def csr_add_edges(csr, src_new: torch.Tensor, dst_new: torch.Tensor, n_src: int,
     return indptr_o, indices_o, eids_o
 
 
+def frontier_mark(rows: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor,
+                  mark: torch.Tensor, n_rows: Optional[torch.Tensor] = None,
+                  check: bool = True) -> torch.Tensor:
+    """mark[indices[p]] = 1 for every slot p of the listed rows of a SOURCE-major CSR
+    (gnnrec_frontier_mark): the destinations of the out-edges of `rows` (ascending, distinct
+    int64 ids), without a neighbour list and balanced by edge.  mark int32 [n_dst] is written
+    in place (words not marked keep their value); n_rows (one device int64, optional): only
+    the first min(n_rows, len(rows)) rows count.  -> the two status words (device).  check:
+    read them back and raise ValueError on a row outside [0, n_src) — nothing is marked then —
+    or a neighbour id outside [0, n_dst); check=False leaves the readback to the caller."""
+    T = _T()
+    for t, n, dt in ((rows, "rows", torch.int64), (indptr, "indptr", torch.int64),
+                     (indices, "indices", torch.int32), (mark, "mark", torch.int32)):
+        _dev(t, n, dt)
+    if n_rows is not None:
+        _dev(n_rows, "n_rows", torch.int64)
+    if rows.dim() != 1 or mark.dim() != 1 or not mark.is_contiguous():
+        raise ValueError("frontier_mark: rows and mark must be 1-D, mark contiguous")
+    dev = rows.device
+    status = torch.empty(2, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(int(T.frontier_mark_workspace_bytes(rows.numel())), 1),
+                     dtype=torch.uint8, device=dev)
+    T.frontier_mark(rows.contiguous(), n_rows, indptr.contiguous(), indices.contiguous(), mark, ws,
+                    status)
+    if check and dev.type != "meta":
+        frontier_status(status, indptr.numel() - 1, mark.numel())
+    return status
+
+
+def frontier_status(status, n_src: int, n_dst: int) -> None:
+    """Raise ValueError on the status words of a frontier_mark call (a tensor or two ints)."""
+    bad_row, bad_nbr = status.tolist() if isinstance(status, torch.Tensor) else status
+    if bad_row:
+        raise ValueError(f"frontier_mark: a listed row lies outside [0, {n_src})")
+    if bad_nbr:
+        raise ValueError(f"frontier_mark: a neighbour id lies outside [0, {n_dst})")
+
+
 def membership_csr(src: torch.Tensor, dst: torch.Tensor, n_src: int, n_dst: int):
     """The dst-major CSR of (src, dst) with every row's source ids ascending — what
     has_edges searches.  Two stable radix sorts of the library (gnnrec_csr_build): by source
@@ -763,7 +801,11 @@ def can_spmm_project(indptr, X, H, W_self, W_neigh, split: Optional[int] = DEFAU
         # library's own alignment check is what refuses a misaligned view, loudly)
         if not torch.compiler.is_compiling() and t.data_ptr() % 16:
             return False
-    if split and split_plan(indptr, split) is not None:
+    route = getattr(indptr, "_gnnrec_route", None)
+    if route is not None and split == DEFAULT_SPLIT:
+        if route.has_split:  # a row subset follows the whole relation's heavy rows
+            return False
+    elif split and split_plan(indptr, split) is not None:
         return False
     # below FUSED_MIN_DEG edges per row the VALU kernel's per-row weight reads bound it and
     # the MFMA variant takes the relation (C5 bought-by, 10 edges/row: VALU-fused 18.0 ms,
@@ -778,10 +820,42 @@ def fused_preprojects(indptr, X, H, reduce: str, avg_deg: Optional[float] = None
     """A fused launch that can_spmm_project accepted runs the pre-projected form: the MFMA
     variant, a linear reduce and a source table at most half the destination count."""
     return fused_variant(indptr, avg_deg) == "mfma" and preproject_pays(
-        X.shape[0], indptr.numel() - 1, reduce)
+        X.shape[0], routed_n_dst(indptr, indptr.numel() - 1), reduce)
 
 
 FUSED_MIN_DEG = 24
+
+
+class Route(NamedTuple):
+    """The whole relation's figures the kernel choice depends on, hung on the indptr of a
+    CSR that holds only some of its rows (`indptr._gnnrec_route`, pin_route): a row computes
+    from its own inputs alone, so a subset that takes the whole relation's route gives the
+    whole pass's bits (inference.IncrementalEmbeddings).  A CSR without the
+    attribute decides from itself, as ever."""
+    avg_deg: float    # edges per destination row (fused_variant)
+    n_dst: int        # destination rows (preproject_pays)
+    has_split: bool   # some row exceeds DEFAULT_SPLIT edges (can_spmm_project)
+
+
+def relation_route(indptr: torch.Tensor) -> Route:
+    """The Route of a whole relation's dst-major CSR, by the rules the helpers below apply to
+    it (a host readback for the heavy-row plan unless the CSR has one cached)."""
+    n = indptr.numel() - 1
+    avg = _nnz(indptr) / n if n else float(FUSED_MIN_DEG)
+    return Route(avg, n, split_plan(indptr, DEFAULT_SPLIT) is not None)
+
+
+def pin_route(indptr: torch.Tensor, route: Route, nnz: int) -> torch.Tensor:
+    """Mark `indptr` (a row subset's CSR of `nnz` edges) to take `route`."""
+    indptr._gnnrec_nnz = int(nnz)
+    indptr._gnnrec_route = route
+    return indptr
+
+
+def routed_n_dst(indptr: torch.Tensor, n_dst: int) -> int:
+    """The destination count to route by: the pinned whole relation's, else n_dst."""
+    route = getattr(indptr, "_gnnrec_route", None)
+    return n_dst if route is None else route.n_dst
 
 
 def fused_variant(indptr, avg_deg: Optional[float] = None) -> str:
@@ -792,8 +866,12 @@ def fused_variant(indptr, avg_deg: Optional[float] = None) -> str:
     rank picks the same kernel); default this CSR's own (spmm_project's `variant` forces
     one)."""
     if avg_deg is None:
-        n = indptr.numel() - 1
-        avg_deg = _nnz(indptr) / n if n else float(FUSED_MIN_DEG)
+        route = getattr(indptr, "_gnnrec_route", None)
+        if route is not None:
+            avg_deg = route.avg_deg
+        else:
+            n = indptr.numel() - 1
+            avg_deg = _nnz(indptr) / n if n else float(FUSED_MIN_DEG)
     return "valu" if avg_deg >= FUSED_MIN_DEG else "mfma"
 
 
@@ -1306,6 +1384,20 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     out = torch.empty((idx.numel(),) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
     _T().gather_rows(src, idx.contiguous(), out)
     return out
+
+
+def scatter_rows(dst: torch.Tensor, idx: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
+    """The inverse of gather_rows, in place: dst[idx[i]] = src[i] (gnnrec_scatter_rows) for a
+    device tensor of any dtype whose rows are contiguous.  idx is strictly ascending int64 —
+    no two rows collide; an id outside dst's rows is skipped.  -> dst."""
+    _dev(idx, "idx", torch.int64)
+    if not (dst.is_cuda or dst.is_meta):
+        raise ValueError("dst: expected a device tensor (there is no CPU path)")
+    if dst.dim() == 0 or src.dim() != dst.dim() or src.dtype != dst.dtype or \
+            src.shape[1:] != dst.shape[1:] or src.shape[0] != idx.numel():
+        raise ValueError("scatter_rows: src must be [len(idx), ...] of dst's dtype and row shape")
+    _T().scatter_rows(src.contiguous(), idx.contiguous(), dst)
+    return dst
 
 
 def sddmm_cos(src: torch.Tensor, dst: torch.Tensor, Hs: torch.Tensor,

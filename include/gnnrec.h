@@ -917,6 +917,26 @@ int gnnrec_csr_add_edges(const int64_t* indptr, const int32_t* indices, const in
                          size_t workspace_bytes, int64_t* indptr_out, int32_t* indices_out,
                          int64_t* eids_out, int64_t* status, void* stream);
 
+/* The dirty-set frontier of an incremental embedding refresh: mark[indices[p]] = 1 for every
+ * slot p of the listed rows of one relation's SOURCE-major CSR (indptr [n_src+1], indices
+ * [n_edges], the destinations) — the destinations of the out-edges of a set of source rows,
+ * without a neighbour list.  rows [n_rows]: ascending, distinct int64 ids; n_rows_dev
+ * (device, may be NULL): only the first min(*n_rows_dev, n_rows) count, so the call can be
+ * queued before the list's size reaches the host.  mark: int32 [n_dst], the format
+ * gnnrec_compact_marked reads; words not marked keep their value.  The work is balanced by
+ * edge: a scan of the listed rows' degrees, then a fixed grid of waves over 512-slot tiles of
+ * the concatenated ranges, bounded by the scan's total on the device (no readback).
+ * status[2] (device): {bad row, bad neighbour}.  A listed id outside [0, n_src) sets
+ * status[0] and nothing else is written; a neighbour id outside [0, n_dst) is skipped and sets
+ * status[1]; indptr values are clamped to [0, n_edges].  The status is the call's only
+ * readback, and the caller's.  n_edges, n_src, n_dst < 2^31.  Workspace from
+ * gnnrec_frontier_mark_workspace_bytes (8 B per listed row + the scan's). */
+size_t gnnrec_frontier_mark_workspace_bytes(int64_t n_rows);
+int gnnrec_frontier_mark(const int64_t* rows, int64_t n_rows, const int64_t* n_rows_dev,
+                         const int64_t* indptr, const int32_t* indices, int64_t n_edges,
+                         int64_t n_src, int64_t n_dst, int32_t* mark, void* workspace,
+                         size_t workspace_bytes, int64_t* status, void* stream);
+
 /* K10 — DGLGraph.has_edges_between(u, v, etype) (reference src/train/run.py:95-101,160-166,
  * the false-negative mask; DGL 0.5.2 [ext]: `_CAPI_DGLHeteroHasEdgesBetween`): out[i] = 1
  * when some edge u[i] -> v[i] exists, else 0; ids outside [0, n_src) / [0, n_dst) give 0.
@@ -1012,6 +1032,13 @@ typedef struct gnnrec_gather_job {
 int gnnrec_gather_rows_batch(const gnnrec_gather_job* jobs, int n_jobs, void* stream);
 int gnnrec_gather_rows(const void* src, int64_t src_ld_bytes, const int64_t* idx, int64_t n,
                        int64_t row_bytes, void* dst, int64_t dst_ld_bytes, void* stream);
+/* The inverse: dst row idx[i] = src row i for i < n (the in-place write-back of the rows an
+ * incremental refresh recomputed).  idx is strictly ascending, so no two rows collide; an
+ * idx[i] outside [0, dst_rows) is skipped, never written.  The same kernel as the gather
+ * with the indexed side swapped: 16-B accesses where the alignment allows. */
+int gnnrec_scatter_rows(const void* src, int64_t src_ld_bytes, const int64_t* idx, int64_t n,
+                        int64_t row_bytes, void* dst, int64_t dst_ld_bytes, int64_t dst_rows,
+                        void* stream);
 
 /* Up to GNNREC_COPY_MAX_JOBS contiguous device copies dst[j] <- src[j] (bytes[j]) in one
  * launch: a static-shape batch handed into the buffers a captured training step replays
