@@ -137,32 +137,25 @@ def _to_ratings(sc, c0, rating):
     ops.rating_rows_(sc, Zc, p)
 
 
-def _rows_exact(h_user, h_item, k, rows, exclude, vals, idx, out_pos, rating=None):
-    """The fallback, always exact: every item scored with the fp32 cosine for the user rows
-    `rows` (int64 device tensor), excluded items masked to -inf, topk_rows; results into
-    vals/idx at rows `out_pos`.  rating = (Z [len(rows)] or None, p [n_items]): the score rows
-    become R = expf(score) / Z + p first (Z None: summed from the rows, g = the score)."""
-    n_items, dev = h_item.shape[0], h_item.device
+def _rows_exact(scorer, k, rows, exclude, vals, idx, out_pos, Z=None):
+    """The fallback, always exact: every item scored in fp32 by the scorer's head for the
+    user rows `rows` (int64 device tensor), in chunks of 2^26 / n_items rows, excluded items
+    masked to -inf, topk_rows; results into vals/idx at rows `out_pos`.  With a popularity
+    the score rows become R = expf(score) / Z + p first (Z [len(rows)]; None: summed from the
+    rows, g = the score)."""
+    n_items = scorer.h_item.shape[0]
     if rows.numel() == 0:
         return
     if n_items == 0:
         vals[out_pos] = float('-inf')
         idx[out_pos] = -1
         return
-    all_items = torch.arange(n_items, device=dev)
-    grouped = ops.cos_grouped_ok(h_user, h_item)
     step = max(1, (1 << 26) // n_items)
     for c0 in range(0, rows.numel(), step):
         r = rows[c0:c0 + step].contiguous()
-        G = r.numel()
-        dst = all_items.repeat(G)
-        if grouped:
-            _, sc = ops.sddmm_cos_grouped(r, None, n_items, dst, h_user, h_item)
-        else:
-            sc = ops.sddmm_cos(r.repeat_interleave(n_items), dst, h_user, h_item)
-        sc = sc.view(G, n_items)
-        if rating is not None:
-            _to_ratings(sc, c0, rating)
+        sc = scorer.score_rows(r)
+        if scorer.p is not None:
+            _to_ratings(sc, c0, (Z, scorer.p))
         if exclude is not None:
             ops.mask_excluded(sc, r, exclude[0], exclude[1])
         v, i = topk_rows(sc, k)
@@ -172,12 +165,100 @@ def _rows_exact(h_user, h_item, k, rows, exclude, vals, idx, out_pos, rating=Non
         idx[pos] = i
 
 
-class _MlpHead:
+# ---- the scorers: what _recommend and _rows_exact need of a head, and nothing else ----------
+#   fast_ok                     does the fast path (and the denominator kernel) exist here
+#   prepare(m, pop_sample)      once per call on the fast path: the item table the filter
+#                               reads and the rows of the threshold sample; sets col_ids
+#   batch(rows) -> st           per-batch state, st[1] the rows' Z (None without popularity)
+#   sample_scores(st)           scores (ratings) of the sample columns [B, sample]
+#   keep(st, tau, counts, cap)  one pass over all items -> the kept candidates
+#   rank(st, kept, counts, rows, k, ex0, ex1, vals, idx)
+#   score_rows(r)               exhaustive fp32 score rows [len(r), n_items]
+#   denominators_of(rows)       with popularity: Z of a batch of rows
+# Each is built once per call from (h_user, h_item[, head]) and p (popularity * weight, or
+# None); whether it scores or rates is the scorer's business: p is a property of the input.
+class _Scorer:
+    col_ids = None      # item id per sample column (int32); None: the columns are a prefix
+
+    def _take_sample(self, table, m, pop_sample):
+        """self.sample = the threshold sample's rows of `table`: the prefix [0, m) as a view,
+        or with popularity the prefix and the popular items, gathered (both once per call)."""
+        if self.p is None:
+            self.sample = table[:m]
+            return
+        self.col_ids = _popular_sample(self.p, m, pop_sample)
+        cols = self.col_ids.to(torch.int64)
+        self.p_col = self.p[cols].contiguous()
+        self.sample = table[cols].contiguous()
+
+
+class _CosHead(_Scorer):
+    """The cosine head behind the bf16 MFMA prefilter (rating: §19)."""
+
+    def __init__(self, h_user, h_item, p=None):
+        d = h_item.shape[1]
+        self.h_user, self.h_item, self.p = h_user, h_item, p
+        self.fast_ok = d % 4 == 0 and 4 <= d <= REC_MAX_D    # the widths of the MFMA kernels
+        if p is not None and self.fast_ok and h_item.shape[0]:
+            self.items_f32 = ops.normalize_rows_f32(h_item)      # converted once per call
+
+    def prepare(self, m, pop_sample):
+        self.items_bf = ops.normalize_rows_bf16(self.h_item)     # converted once per call
+        self._take_sample(self.items_bf, m, pop_sample)
+        if self.p is not None:
+            self.pmax = self.p.max().reshape(1)
+
+    def denominators_of(self, rows):
+        return ops.cos_denominators(ops.normalize_rows_f32(self.h_user, rows), self.items_f32)
+
+    def batch(self, rows):
+        Zb = None if self.p is None else self.denominators_of(rows)
+        return ops.normalize_rows_bf16(self.h_user, rows), Zb
+
+    def sample_scores(self, st):
+        if self.p is None:
+            return ops.score_bf16_store(st[0], self.sample)
+        return ops.score_bf16_store_rating(st[0], self.sample, st[1], self.p_col)
+
+    def keep(self, st, tau, counts, cand_cap):
+        users_bf, Zb = st
+        cand = torch.empty((tau.numel(), cand_cap), dtype=torch.int32, device=tau.device)
+        if self.p is None:    # the kernel itself subtracts 2 REC_EPS
+            ops.score_bf16_filter(users_bf, self.items_bf, tau, counts, cand)
+        else:
+            thr = ops.rating_thresholds(tau, Zb, self.pmax)   # tau - 2 delta_u, once per batch
+            ops.score_bf16_filter_rating(users_bf, self.items_bf, Zb, self.p, thr, counts, cand)
+        return cand
+
+    def rank(self, st, cand, counts, rows, k, ex0, ex1, vals, idx):
+        if self.p is None:
+            ops.topk_candidates(counts, cand, rows, self.h_user, self.h_item, k, ex0, ex1, vals,
+                                idx)
+        else:
+            ops.topk_candidates_rating(counts, cand, rows, self.h_user, self.h_item, st[1],
+                                       self.p, k, ex0, ex1, vals, idx)
+
+    def score_rows(self, r):
+        if not hasattr(self, '_all_items'):     # once per call: _rows_exact runs at most once
+            self._all_items = torch.arange(self.h_item.shape[0], device=self.h_item.device)
+            self._grouped = ops.cos_grouped_ok(self.h_user, self.h_item)
+        G, n_items = r.numel(), self.h_item.shape[0]
+        dst = self._all_items.repeat(G)
+        if self._grouped:
+            _, sc = ops.sddmm_cos_grouped(r, None, n_items, dst, self.h_user, self.h_item)
+        else:
+            sc = ops.sddmm_cos(r.repeat_interleave(n_items), dst, self.h_user, self.h_item)
+        return sc.view(G, n_items)
+
+
+class _MlpHead(_Scorer):
     """A PredictingLayer re-associated for scoring a user batch against every item:
     Q = h_item W1b^T once, P = h_user[rows] W1a^T + b1 per batch, the rest of the head in
-    ops.edge_mlp_dense_store / _filter (each score bitwise ops.edge_mlp's for the pair)."""
+    ops.edge_mlp_dense_store / _filter (each score bitwise ops.edge_mlp's for the pair).
+    The filter compares the final fp32 score (or rating): no band."""
+    fast_ok = True
 
-    def __init__(self, head, h_user, h_item):
+    def __init__(self, head, h_user, h_item, p=None):
         d = h_item.shape[1]
         W1 = head.hidden_1.weight
         if tuple(W1.shape) != (128, 2 * d):
@@ -185,7 +266,8 @@ class _MlpHead:
                              f'{tuple(W1.shape)}')
         for t in (W1, head.hidden_2.weight, head.output.weight):
             ops._dev(t, 'head weights', torch.float32)
-        self.h_user, self.W1a, self.b1 = h_user, W1[:, :d], head.hidden_1.bias
+        self.h_user, self.h_item, self.p = h_user, h_item, p
+        self.W1a, self.b1 = W1[:, :d], head.hidden_1.bias
         self.tail = (head.hidden_2.weight.detach().contiguous(),
                      head.hidden_2.bias.detach().contiguous(),
                      head.output.weight.detach().reshape(-1).contiguous(),
@@ -213,29 +295,37 @@ class _MlpHead:
         ops.edge_mlp_dense_filter_rating(P, self.Q, *self.tail, Z, p, tau, counts, cand_items,
                                          cand_scores)
 
+    # the scorer interface, on the members above
+    def prepare(self, m, pop_sample):
+        self._take_sample(self.Q, m, pop_sample)
 
-def _rows_exact_mlp(mlp, n_items, k, rows, exclude, vals, idx, out_pos, rating=None):
-    """_rows_exact for the MLP head: the dense store of `rows` over all items, in chunks of
-    2^26 / n_items rows, excluded items masked to -inf, topk_rows.  rating: as _rows_exact."""
-    if rows.numel() == 0:
-        return
-    if n_items == 0:
-        vals[out_pos] = float('-inf')
-        idx[out_pos] = -1
-        return
-    step = max(1, (1 << 26) // n_items)
-    for c0 in range(0, rows.numel(), step):
-        r = rows[c0:c0 + step].contiguous()
-        sc = mlp.store(mlp.P(r))
-        if rating is not None:
-            _to_ratings(sc, c0, rating)
-        if exclude is not None:
-            ops.mask_excluded(sc, r, exclude[0], exclude[1])
-        v, i = topk_rows(sc, k)
-        i = torch.where(v == float('-inf'), torch.full_like(i, -1), i)  # masked or past the end
-        pos = out_pos[c0:c0 + step]
-        vals[pos] = v
-        idx[pos] = i
+    def denominators_of(self, rows):
+        return self.denominators(self.P(rows))
+
+    def batch(self, rows):
+        P = self.P(rows)
+        return P, None if self.p is None else self.denominators(P)
+
+    def sample_scores(self, st):
+        if self.p is None:
+            return ops.edge_mlp_dense_store(st[0], self.sample, *self.tail)
+        return self.store_rating(st[0], self.sample, st[1], self.p_col)
+
+    def keep(self, st, tau, counts, cand_cap):
+        P, Zb = st
+        cand = torch.empty((tau.numel(), cand_cap), dtype=torch.int32, device=tau.device)
+        cand_sc = torch.empty((tau.numel(), cand_cap), dtype=torch.float32, device=tau.device)
+        if self.p is None:
+            self.filter(P, tau, counts, cand, cand_sc)
+        else:
+            self.filter_rating(P, Zb, self.p, tau, counts, cand, cand_sc)
+        return cand, cand_sc
+
+    def rank(self, st, kept, counts, rows, k, ex0, ex1, vals, idx):
+        ops.topk_scored_candidates(counts, *kept, k, rows, ex0, ex1, vals, idx)
+
+    def score_rows(self, r):
+        return self.store(self.P(r))
 
 
 def _popularity_vector(popularity, weight_popularity, n_items):
@@ -262,90 +352,52 @@ def _popular_sample(p, m, pop_sample):
     return ids.to(torch.int32)
 
 
-def _recommend_pop(h_user, h_item, k, user_rows, exclude, batch_size, m, cand_cap, head, p,
-                   pop_sample, stats, vals, idx):
-    """recommend() ranking by R(u, v) = expf(score(u, v)) / Z_u + p_v."""
-    dev = h_item.device
-    n_items, d = h_item.shape
-    U = user_rows.numel()
-    all_pos = torch.arange(U, device=dev)
-    ex0 = None if exclude is None else exclude[0]
-    ex1 = None if exclude is None else exclude[1]
-    mfma = d % 4 == 0 and 4 <= d <= REC_MAX_D      # the widths of the denominator kernel
-    if U == 0 or n_items == 0:   # nothing to rate: the padding of the exhaustive path
-        if head is not None:
-            _rows_exact_mlp(_MlpHead(head, h_user, h_item), n_items, k, user_rows, exclude, vals,
-                            idx, all_pos)
-        else:
-            _rows_exact(h_user, h_item, k, user_rows, exclude, vals, idx, all_pos)
-        return
-    fast = k <= cand_cap // 4 and (head is not None or mfma)
-    Z = torch.empty(U, dtype=torch.float32, device=dev)
-    if head is not None:
-        mlp = _MlpHead(head, h_user, h_item)
-    elif mfma:
-        items_f32 = ops.normalize_rows_f32(h_item)       # converted once per call
-    if not fast:
-        if head is not None:
+def _recommend(scorer, k, user_rows, exclude, batch_size, m, cand_cap, pop_sample, stats, vals,
+               idx):
+    """recommend()'s one driver, for either head and with or without popularity: per batch the
+    sample columns scored, the row's excluded items masked, the k-th best value taken as tau,
+    one filter pass over all items, the kept candidates ranked; after the last batch one
+    readback, and the overflowed rows redone exhaustively."""
+    dev = vals.device
+    U, n_items = user_rows.numel(), scorer.h_item.shape[0]
+    ex0, ex1 = (None, None) if exclude is None else exclude
+    # the rows' denominators, kept for the exhaustive path (which sums them from its score
+    # rows where the denominator kernel does not exist: Z None)
+    Z = None
+    if scorer.p is not None and scorer.fast_ok:
+        Z = torch.empty(U, dtype=torch.float32, device=dev)
+    if not (scorer.fast_ok and k <= cand_cap // 4 and U > 0 and n_items > 0):
+        if Z is not None and n_items > 0:
             for b0 in range(0, U, batch_size):
-                Z[b0:b0 + batch_size] = mlp.denominators(mlp.P(user_rows[b0:b0 + batch_size]))
-            _rows_exact_mlp(mlp, n_items, k, user_rows, exclude, vals, idx, all_pos, (Z, p))
-        elif mfma:
-            for b0 in range(0, U, batch_size):
-                users_f32 = ops.normalize_rows_f32(h_user, user_rows[b0:b0 + batch_size])
-                Z[b0:b0 + batch_size] = ops.cos_denominators(users_f32, items_f32)
-            _rows_exact(h_user, h_item, k, user_rows, exclude, vals, idx, all_pos, (Z, p))
-        else:  # Z from the exhaustive score rows: g is the score itself
-            _rows_exact(h_user, h_item, k, user_rows, exclude, vals, idx, all_pos, (None, p))
+                Z[b0:b0 + batch_size] = scorer.denominators_of(user_rows[b0:b0 + batch_size])
+        _rows_exact(scorer, k, user_rows, exclude, vals, idx, torch.arange(U, device=dev), Z)
         return
     stats['fast_path'] = True
-    col_ids = _popular_sample(p, m, pop_sample)            # chosen once per call
-    cols = col_ids.to(torch.int64)
-    p_col = p[cols].contiguous()
-    pmax = p.max().reshape(1)
-    stats['pop_sample'] = int(col_ids.numel()) - m
+    scorer.prepare(m, pop_sample)
+    if scorer.col_ids is not None:
+        stats['pop_sample'] = int(scorer.col_ids.numel()) - m
     counts = torch.zeros(U, dtype=torch.int32, device=dev)
-    if head is None:
-        items_bf = ops.normalize_rows_bf16(h_item)
-        sample_bf = items_bf[cols].contiguous()
-    else:
-        sample_Q = mlp.Q[cols].contiguous()
     for b0 in range(0, U, batch_size):
         rows = user_rows[b0:b0 + batch_size]
-        B = rows.numel()
-        cand = torch.empty((B, cand_cap), dtype=torch.int32, device=dev)
-        if head is None:
-            Zb = ops.cos_denominators(ops.normalize_rows_f32(h_user, rows), items_f32)
-            users_bf = ops.normalize_rows_bf16(h_user, rows)
-            s = ops.score_bf16_store_rating(users_bf, sample_bf, Zb, p_col)
-        else:
-            P = mlp.P(rows)
-            Zb = mlp.denominators(P)
-            s = mlp.store_rating(P, sample_Q, Zb, p_col)
-        Z[b0:b0 + B] = Zb
-        if exclude is not None:
-            ops.mask_excluded_mapped(s, col_ids, rows, ex0, ex1)
+        cut = slice(b0, b0 + rows.numel())
+        st = scorer.batch(rows)
+        s = scorer.sample_scores(st)
+        if Z is not None:
+            Z[cut] = st[1]
+        if exclude is not None and scorer.col_ids is None:
+            ops.mask_excluded(s, rows, ex0, ex1)
+        elif exclude is not None:
+            ops.mask_excluded_mapped(s, scorer.col_ids, rows, ex0, ex1)
         tau = topk_rows(s, k)[0][:, k - 1].contiguous()  # -inf: fewer than k eligible there
         del s
-        if head is None:
-            thr = ops.rating_thresholds(tau, Zb, pmax)     # tau - 2 delta_u, once per batch
-            ops.score_bf16_filter_rating(users_bf, items_bf, Zb, p, thr, counts[b0:b0 + B], cand)
-            ops.topk_candidates_rating(counts[b0:b0 + B], cand, rows, h_user, h_item, Zb, p, k,
-                                       ex0, ex1, vals[b0:b0 + B], idx[b0:b0 + B])
-        else:
-            cand_sc = torch.empty((B, cand_cap), dtype=torch.float32, device=dev)
-            mlp.filter_rating(P, Zb, p, tau, counts[b0:b0 + B], cand, cand_sc)
-            ops.topk_scored_candidates(counts[b0:b0 + B], cand, cand_sc, k, rows, ex0, ex1,
-                                       vals[b0:b0 + B], idx[b0:b0 + B])
+        kept = scorer.keep(st, tau, counts[cut], cand_cap)
+        scorer.rank(st, kept, counts[cut], rows, k, ex0, ex1, vals[cut], idx[cut])
     cnt = counts.cpu().numpy()                       # the call's one readback
     over = np.nonzero(cnt > cand_cap)[0]
     if over.size:
         pos = torch.from_numpy(over).to(dev)
-        if head is None:
-            _rows_exact(h_user, h_item, k, user_rows[pos], exclude, vals, idx, pos, (Z[pos], p))
-        else:
-            _rows_exact_mlp(mlp, n_items, k, user_rows[pos], exclude, vals, idx, pos,
-                            (Z[pos], p))
+        _rows_exact(scorer, k, user_rows[pos], exclude, vals, idx, pos,
+                    None if Z is None else Z[pos])
     stats.update(candidates_mean=float(cnt.mean()), candidates_max=int(cnt.max()),
                  overflow_rows=int(over.size))
 
@@ -428,7 +480,7 @@ def recommend(h_user, h_item, k, user_rows=None, exclude=None, *, batch_size=819
                          f'[1, {REC_MAX_CAP}]')
     dev = h_item.device
     h_user, h_item = h_user.contiguous(), h_item.contiguous()
-    n_items, d = h_item.shape
+    n_items, p = h_item.shape[0], None
     if popularity is not None:   # refused before any launch
         if int(pop_sample) < 0:
             raise ValueError('recommend: pop_sample must be >= 0')
@@ -451,74 +503,11 @@ def recommend(h_user, h_item, k, user_rows=None, exclude=None, *, batch_size=819
     m = min(sample, n_items)
     stats = {'candidates_mean': 0.0, 'candidates_max': 0, 'overflow_rows': 0, 'sample': m,
              'cand_cap': cand_cap, 'fast_path': False}
-    if popularity is not None:
+    if p is not None:
         stats['pop_sample'] = 0
-        _recommend_pop(h_user, h_item, k, user_rows, exclude, batch_size, m, cand_cap, head, p,
-                       pop_sample, stats, vals, idx)
-        return (idx, vals, stats) if return_stats else (idx, vals)
-    if head is not None:
-        mlp = _MlpHead(head, h_user, h_item)
-        all_pos = torch.arange(U, device=dev)
-        if not (k <= cand_cap // 4 and n_items > 0 and U > 0):
-            _rows_exact_mlp(mlp, n_items, k, user_rows, exclude, vals, idx, all_pos)
-            return (idx, vals, stats) if return_stats else (idx, vals)
-        stats['fast_path'] = True
-        counts = torch.zeros(U, dtype=torch.int32, device=dev)
-        for b0 in range(0, U, batch_size):
-            rows = user_rows[b0:b0 + batch_size]
-            B = rows.numel()
-            P = mlp.P(rows)
-            s = mlp.store(P, m)
-            if exclude is not None:
-                ops.mask_excluded(s, rows, exclude[0], exclude[1])
-            tau = topk_rows(s, k)[0][:, k - 1].contiguous()  # -inf: fewer than k eligible there
-            del s
-            cand = torch.empty((B, cand_cap), dtype=torch.int32, device=dev)
-            cand_sc = torch.empty((B, cand_cap), dtype=torch.float32, device=dev)
-            mlp.filter(P, tau, counts[b0:b0 + B], cand, cand_sc)
-            ops.topk_scored_candidates(counts[b0:b0 + B], cand, cand_sc, k, rows,
-                                       None if exclude is None else exclude[0],
-                                       None if exclude is None else exclude[1],
-                                       vals[b0:b0 + B], idx[b0:b0 + B])
-        cnt = counts.cpu().numpy()                   # the call's one readback
-        over = np.nonzero(cnt > cand_cap)[0]
-        if over.size:
-            pos = torch.from_numpy(over).to(dev)
-            _rows_exact_mlp(mlp, n_items, k, user_rows[pos], exclude, vals, idx, pos)
-        stats.update(candidates_mean=float(cnt.mean()), candidates_max=int(cnt.max()),
-                     overflow_rows=int(over.size))
-        return (idx, vals, stats) if return_stats else (idx, vals)
-    fast = (k <= cand_cap // 4 and d <= REC_MAX_D and d % 4 == 0 and d >= 4 and n_items > 0
-            and U > 0)
-    if not fast:
-        _rows_exact(h_user, h_item, k, user_rows, exclude, vals, idx, torch.arange(U, device=dev))
-        return (idx, vals, stats) if return_stats else (idx, vals)
-    stats['fast_path'] = True
-    items_bf = ops.normalize_rows_bf16(h_item)      # converted once per call
-    prefix_bf = items_bf[:m]
-    counts = torch.zeros(U, dtype=torch.int32, device=dev)
-    for b0 in range(0, U, batch_size):
-        rows = user_rows[b0:b0 + batch_size]
-        B = rows.numel()
-        users_bf = ops.normalize_rows_bf16(h_user, rows)
-        s = ops.score_bf16_store(users_bf, prefix_bf)
-        if exclude is not None:
-            ops.mask_excluded(s, rows, exclude[0], exclude[1])
-        tau = topk_rows(s, k)[0][:, k - 1].contiguous()  # -inf: fewer than k eligible there
-        del s
-        cand = torch.empty((B, cand_cap), dtype=torch.int32, device=dev)
-        ops.score_bf16_filter(users_bf, items_bf, tau, counts[b0:b0 + B], cand)
-        ops.topk_candidates(counts[b0:b0 + B], cand, rows, h_user, h_item, k,
-                            None if exclude is None else exclude[0],
-                            None if exclude is None else exclude[1],
-                            vals[b0:b0 + B], idx[b0:b0 + B])
-    cnt = counts.cpu().numpy()                       # the call's one readback
-    over = np.nonzero(cnt > cand_cap)[0]
-    if over.size:
-        pos = torch.from_numpy(over).to(dev)
-        _rows_exact(h_user, h_item, k, user_rows[pos], exclude, vals, idx, pos)
-    stats.update(candidates_mean=float(cnt.mean()), candidates_max=int(cnt.max()),
-                 overflow_rows=int(over.size))
+    scorer = _CosHead(h_user, h_item, p) if head is None else _MlpHead(head, h_user, h_item, p)
+    _recommend(scorer, k, user_rows, exclude, batch_size, m, cand_cap, pop_sample, stats, vals,
+               idx)
     return (idx, vals, stats) if return_stats else (idx, vals)
 
 
