@@ -178,6 +178,56 @@ static void validation() {
   CHECK(gnnrec_topk_candidates_f32(nullptr, nullptr, 64, 0, nullptr, nullptr, 16, nullptr, 16, 16,
                                    nullptr, nullptr, 10, nullptr, nullptr, nullptr) == GNNREC_OK,
         "candidates empty");
+  // the cached lists' merge (gnnrec_topk_update_f32): refusals, then the two empty problems
+  CHECK(gnnrec_topk_update_f32(l16, 3, l16, f16, 9, 65, i16, 40, i16, i16, 64, i16, 5, f16, 16,
+                               f16, 16, 16, nullptr, nullptr, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("k must be in [1, 64] (got 65)"),
+        "update k > 64");
+  CHECK(gnnrec_topk_update_f32(l16, 3, l16, f16, 9, 0, i16, 40, i16, i16, 64, i16, 5, f16, 16,
+                               f16, 16, 16, nullptr, nullptr, i16, nullptr) == GNNREC_EINVAL,
+        "update k = 0");
+  CHECK(gnnrec_topk_update_f32(l16, 3, l16, f16, 9, 10, i16, 40, i16, i16, 247, i16, 5, f16, 16,
+                               f16, 16, 16, nullptr, nullptr, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("cap must be"),
+        "update cap > slots - k");
+  CHECK(gnnrec_topk_update_f32(l16, 3, l16, f16, 9, 10, i16, 40, i16, i16, 0, i16, 5, f16, 16,
+                               f16, 16, 16, nullptr, nullptr, i16, nullptr) == GNNREC_EINVAL,
+        "update cap = 0");
+  CHECK(gnnrec_topk_update_f32(l16, 3, l16, f16, 9, 10, i16, 40, i16, i16, 64, i16, 5, f16, 18,
+                               f16, 18, 18, nullptr, nullptr, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("d %"),
+        "update d");
+  CHECK(gnnrec_topk_update_f32(l16, 3, l16, f16, 9, 10, i16, 40, i16, i16, 64, i16, 5, f16, 12,
+                               f16, 16, 16, nullptr, nullptr, i16, nullptr) == GNNREC_EINVAL,
+        "update stride < d");
+  CHECK(gnnrec_topk_update_f32(l16, 3, l16, f16, 9, 10, i16, (int64_t)1 << 31, i16, i16, 64, i16,
+                               5, f16, 16, f16, 16, 16, nullptr, nullptr, i16, nullptr) ==
+            GNNREC_EINVAL && err_has("int32"),
+        "update item ids");
+  CHECK(gnnrec_topk_update_f32(l16, -1, l16, f16, 9, 10, i16, 40, i16, i16, 64, i16, 5, f16, 16,
+                               f16, 16, 16, nullptr, nullptr, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("bad size"),
+        "update negative rows");
+  CHECK(gnnrec_topk_update_f32(l16, 3, l16, f16, 9, 10, i16, 40, i16, i16, 64, i16, 5, f16, 16,
+                               f16, 16, 16, nullptr, nullptr, nullptr, nullptr) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "update null redo");
+  CHECK(gnnrec_topk_update_f32(l16, 3, l16, f16, 9, 10, i16, 40, i16, i16, 64, i16, 5,
+                               reinterpret_cast<float*>(4), 16, f16, 16, 16, nullptr, nullptr, i16,
+                               nullptr) == GNNREC_EINVAL && err_has("aligned"),
+        "update alignment");
+  CHECK(gnnrec_topk_update_f32(l16, 3, l16, f16, 9, 10, i16, 40, i16, i16, 64, i16, 5, f16, 16,
+                               f16, 16, 16, l16, nullptr, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("indptr without indices"),
+        "update exclusion");
+  CHECK(gnnrec_topk_update_f32(nullptr, 0, nullptr, nullptr, 9, 10, nullptr, 40, nullptr, nullptr,
+                               64, nullptr, 5, nullptr, 16, nullptr, 16, 16, nullptr, nullptr,
+                               nullptr, nullptr) == GNNREC_OK,
+        "update no rows");
+  CHECK(gnnrec_topk_update_f32(nullptr, 3, nullptr, nullptr, 9, 10, nullptr, 40, nullptr, nullptr,
+                               64, nullptr, 0, nullptr, 16, nullptr, 16, 16, nullptr, nullptr,
+                               nullptr, nullptr) == GNNREC_OK,
+        "update no dirty item");
   // the MLP head's dense scoring (heads.hip) and scored-candidate ranking
   CHECK(gnnrec_edge_mlp_dense_store_f32(reinterpret_cast<float*>(20), 4, f16, 9, f16, f16, f16,
                                         f16, f16, 9, nullptr) == GNNREC_EINVAL &&

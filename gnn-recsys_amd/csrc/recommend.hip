@@ -20,6 +20,9 @@
 //   topk_scored_candidates  the same strike and ranking of (item, score) pairs that need no
 //                         rescoring: the MLP head's, whose filter (heads.hip) compares and
 //                         keeps the final fp32 score
+//   topk_update           f1e: a cached list merged, in place, with the dirty items the filter
+//                         kept after a refresh, where the result is provably the exact list
+//                         (one wave per row)
 //
 // THE BOUND.  bf16 has unit roundoff 2^-8: |bf16(û) - û| <= 2^-8 |û| as vectors, and the same
 // for v̂.  With |û| = |v̂| = 1 (up to fp32 rounding) Cauchy-Schwarz gives
@@ -570,6 +573,175 @@ __global__ __launch_bounds__(256) void topk_scored_candidates_kernel(
   rank_and_emit(ids, sc, n, k, b, out_v, out_i, &n_valid, tid);
 }
 
+// ---------------------------------------------------------------- update ----
+// f1e: a clean user's cached top-k list brought up to date after a refresh
+// that rewrote the item rows marked in item_mark, in place.  One WAVE per row, four rows per
+// block: a row holds its k entries and the handful of dirty items the filter kept
+// (tau = the list's last score), and the kernel runs for every clean user, most of whom
+// leave after reading k marks and one count.  The block-wide strike_excluded /
+// rank_and_emit above spend 256 threads and their barriers on a row; their wave forms are
+// kept apart here because sharing them would make those kernels branch on the caller
+// (barrier or none, strided by 256 or by 64, emit or decide first); better() and
+// cos_pair_vec4 are shared.  Rows are wave-private: no __syncthreads anywhere.
+//
+// Per row u = rows[b], with kappa = (score, id) of the list's last real entry:
+//   the list's clean entries keep their cached scores, its dirty entries are dropped;
+//   the candidates (columns of the dirty-item list) become item ids, the ones in u's
+//   exclusion row are struck, the rest rescored with the fp32 cosine;
+//   SETTLED when the old list was padded (no clean eligible item lies outside it, and
+//   tau = -inf kept every dirty item), or when k entries remain and the k-th is not worse
+//   than kappa (everything outside the merged set ranks after kappa): the k best are
+//   written; otherwise redo[u] = 1 and the row stays as it was.
+// NaN scores, cached or rescored, are outside the contract, as for recommend(): better() is
+// not a total order with them, and two entries could then claim one rank (never an address
+// outside the row).
+constexpr int kUpdSlots = 256;  // LDS list slots per wave: k kept entries + cap candidates
+constexpr int kUpdMaxK = 64;    // one lane per cached entry
+
+// the wave's LDS writes before, its reads after: the hardware keeps one wave's LDS
+// operations in order, this keeps the compiler from moving them across
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int LPR>
+__global__ __launch_bounds__(256) void topk_update_kernel(
+    const int64_t* __restrict__ rows, int64_t B, int64_t* __restrict__ idx,
+    float* __restrict__ vals, int64_t n_users, int k, const int* __restrict__ item_mark,
+    int64_t n_items, const int* __restrict__ counts, const int* __restrict__ cand, int cap,
+    const int* __restrict__ dirty_ids, int64_t nd, const float* __restrict__ Hu, int64_t ldu,
+    const float* __restrict__ Hi, int64_t ldi, int d, const int64_t* __restrict__ ex_ptr,
+    const int32_t* __restrict__ ex_idx, int* __restrict__ redo) {
+  __shared__ int s_ids[4][kUpdSlots];
+  __shared__ float s_sc[4][kUpdSlots];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t b = (int64_t)blockIdx.x * 4 + wave;
+  if (b >= B) return;  // wave-uniform, as every exit below
+  const int64_t u = rows[b];
+  if (u < 0 || u >= n_users) return;
+  int* ids = s_ids[wave];
+  float* sc = s_sc[wave];
+  // 1. the cached entries (lane e holds entry e), their marks, the count
+  int my_id = -1;
+  float my_v = -INFINITY;
+  bool dirty = false;
+  if (lane < k) {
+    const int64_t c = idx[u * k + lane];
+    my_v = vals[u * k + lane];
+    if (c >= 0) {
+      my_id = (int)c;
+      dirty = c >= n_items || item_mark[c] != 0;  // an id past the table: dropped, never read
+    }
+  }
+  const int cnt = counts[b];
+  const unsigned long long real_m = __ballot(my_id >= 0);
+  const unsigned long long dirty_m = __ballot(dirty);
+  if (dirty_m == 0 && cnt == 0) return;  // nothing of this row changed: left unwritten
+  if (cnt < 0 || cnt > cap) {            // more candidates than slots: the caller re-ranks
+    if (lane == 0) redo[u] = 1;
+    return;
+  }
+  const int n_real = __popcll(real_m);  // real entries come first: the list is padded behind
+  const bool padded = n_real < k;
+  // kappa, read before anything is overwritten (unused when the list is empty)
+  const int last = n_real > 0 ? n_real - 1 : 0;
+  const float kap_s = __shfl(my_v, last);
+  const int kap_id = __shfl(my_id, last);
+  // 2. the kept entries, compacted, then the candidates as item ids
+  const bool keep = my_id >= 0 && !dirty;
+  const unsigned long long keep_m = __ballot(keep);
+  const int n_keep = __popcll(keep_m);
+  if (keep) {
+    const int pos = __popcll(keep_m & ((1ull << lane) - 1ull));
+    ids[pos] = my_id;
+    sc[pos] = my_v;
+  }
+  for (int i = lane; i < cnt; i += kWave) {
+    const int col = cand[b * cap + i];
+    int item = -1;
+    if (col >= 0 && col < nd) {
+      item = dirty_ids[col];
+      if (item < 0 || item >= n_items) item = -1;
+    }
+    ids[n_keep + i] = item;
+    sc[n_keep + i] = -INFINITY;
+  }
+  const int n = n_keep + cnt;  // <= k + cap <= kUpdSlots
+  wave_lds_sync();
+  // the candidates found in the user's exclusion row are struck (the kept entries were
+  // eligible before and still are): 64 exclusion ids per round in the lanes, each
+  // candidate compared with all of them at once.  The row may be unsorted and of any
+  // length; nothing is staged.
+  if (ex_ptr && cnt > 0) {
+    const int64_t e0 = ex_ptr[u], e1 = ex_ptr[u + 1];
+    for (int64_t base = e0; base < e1; base += kWave) {  // wave-uniform trip count
+      const int ex = base + lane < e1 ? ex_idx[base + lane] : -1;
+      for (int i = 0; i < cnt; ++i) {
+        const int c = ids[n_keep + i];  // one address: a broadcast read
+        if (c < 0) continue;            // wave-uniform
+        if (__ballot(ex == c) != 0 && lane == 0) ids[n_keep + i] = -1;
+      }
+      wave_lds_sync();
+    }
+  }
+  // 3. the surviving candidates rescored by lane groups, as topk_candidates_kernel does;
+  // every lane of the wave calls cos_pair_vec4 (its DPP sums read their neighbours)
+  constexpr int NPW = kWave / LPR;
+  const int grp = lane / LPR, gl = lane % LPR;
+  const float* pu = Hu + u * ldu;
+  for (int i0 = 0; i0 < cnt; i0 += NPW) {  // wave-uniform bound
+    const int i = i0 + grp;
+    const int c = i < cnt ? ids[n_keep + i] : -1;
+    const bool ok = c >= 0;
+    const float r = cos_pair_vec4<LPR>(pu, Hi + (int64_t)(ok ? c : 0) * ldi, d, gl, ok);
+    if (gl == LPR - 1 && ok) sc[n_keep + i] = r;
+  }
+  wave_lds_sync();
+  // 4. ranks: ids are distinct (candidates are dirty, kept entries clean), so the order is
+  // total; a lane owns slots lane, lane + 64, ...
+  constexpr int PASSES = kUpdSlots / kWave;
+  int rank[PASSES];
+  int n_valid = 0;
+  bool kth_ok = false;  // the entry of rank k - 1 is not worse than kappa
+#pragma unroll
+  for (int p = 0; p < PASSES; ++p) {
+    const int i = p * kWave + lane;
+    rank[p] = -1;
+    const int c = i < n ? ids[i] : -1;
+    if (c >= 0) {
+      const float v = sc[i];
+      int r = 0;
+      for (int j = 0; j < n; ++j) {
+        const int cj = ids[j];
+        r += (cj >= 0 && better(sc[j], cj, v, c)) ? 1 : 0;
+      }
+      rank[p] = r;
+      if (r == k - 1) kth_ok = !better(kap_s, kap_id, v, c);
+    }
+    n_valid += __popcll(__ballot(c >= 0));
+  }
+  // 5. the settle test against the OLD key, before any write
+  const bool settled = padded || __ballot(kth_ok) != 0;
+  if (!settled) {
+    if (lane == 0) redo[u] = 1;
+    return;
+  }
+#pragma unroll
+  for (int p = 0; p < PASSES; ++p) {
+    const int i = p * kWave + lane;
+    if (rank[p] >= 0 && rank[p] < k) {
+      vals[u * k + rank[p]] = sc[i];
+      idx[u * k + rank[p]] = ids[i];
+    }
+  }
+  for (int r = n_valid + lane; r < k; r += kWave) {  // only a padded list can come up short
+    vals[u * k + r] = -INFINITY;
+    idx[u * k + r] = -1;
+  }
+}
+
 int check_score_args(const char* fn, const void* U, int64_t B, const void* V, int64_t n,
                      int64_t dpad) {
   GNNREC_REQUIRE(B >= 0 && n >= 0, "%s: negative size", fn);
@@ -778,4 +950,45 @@ extern "C" int gnnrec_topk_scored_candidates_f32(const int32_t* counts, const in
                      as_stream(stream), counts, cand_items, cand_scores, (int)cap, user_rows,
                      exclude_indptr, exclude_indices, (int)k, out_vals, out_idx);
   return check_launch("gnnrec_topk_scored_candidates_f32");
+}
+
+extern "C" int gnnrec_topk_update_f32(const int64_t* rows, int64_t n_rows, int64_t* idx,
+                                      float* vals, int64_t n_users, int64_t k,
+                                      const int32_t* item_mark, int64_t n_items,
+                                      const int32_t* counts, const int32_t* cand_cols,
+                                      int64_t cap, const int32_t* dirty_ids, int64_t n_dirty,
+                                      const float* h_user, int64_t ldu, const float* h_item,
+                                      int64_t ldi, int64_t d, const int64_t* exclude_indptr,
+                                      const int32_t* exclude_indices, int32_t* redo,
+                                      void* stream) {
+  using namespace gnnrec;
+  const char* fn = "gnnrec_topk_update_f32";
+  GNNREC_REQUIRE(n_rows >= 0 && n_users >= 0 && n_items >= 0 && n_dirty >= 0 &&
+                     (n_rows + 3) / 4 < (int64_t(1) << 31),
+                 "%s: bad size", fn);
+  GNNREC_REQUIRE(n_items < (int64_t(1) << 31), "%s: item ids must fit int32", fn);
+  GNNREC_REQUIRE(k >= 1 && k <= kUpdMaxK, "%s: k must be in [1, %d] (got %lld)", fn, kUpdMaxK,
+                 (long long)k);
+  GNNREC_REQUIRE(cap >= 1 && cap <= kUpdSlots - k, "%s: cap must be in [1, %d - k] (got %lld)",
+                 fn, kUpdSlots, (long long)cap);
+  GNNREC_REQUIRE(d >= 4 && d % 4 == 0 && ldu % 4 == 0 && ldi % 4 == 0 && ldu >= d && ldi >= d,
+                 "%s: needs d %% 4 == 0 and row strides that are multiples of 4 and >= d", fn);
+  if (n_rows == 0 || n_dirty == 0) return GNNREC_OK;  // no dirty item: no list can change
+  GNNREC_REQUIRE(rows && idx && vals && item_mark && counts && cand_cols && dirty_ids && h_user &&
+                     h_item && redo,
+                 "%s: null pointer", fn);
+  GNNREC_REQUIRE(aligned16(h_user) && aligned16(h_item), "%s: tables must be 16-byte aligned", fn);
+  GNNREC_REQUIRE(!exclude_indptr || exclude_indices, "%s: exclusion indptr without indices", fn);
+  hipStream_t s = as_stream(stream);
+  const dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
+#define GNNREC_LAUNCH_UPD(LPR)                                                                  \
+  hipLaunchKernelGGL((topk_update_kernel<LPR>), grid, block, 0, s, rows, n_rows, idx, vals,     \
+                     n_users, (int)k, item_mark, n_items, counts, cand_cols, (int)cap,          \
+                     dirty_ids, n_dirty, h_user, ldu, h_item, ldi, (int)d, exclude_indptr,      \
+                     exclude_indices, redo)
+  if (d <= 64) GNNREC_LAUNCH_UPD(16);  // the lane groups of gnnrec_sddmm_cos_f32
+  else if (d <= 128) GNNREC_LAUNCH_UPD(32);
+  else GNNREC_LAUNCH_UPD(64);
+#undef GNNREC_LAUNCH_UPD
+  return check_launch(fn);
 }

@@ -845,6 +845,66 @@ void topk_candidates_f32(const Tensor& counts, const Tensor& cand_items,
      "gnnrec_topk_candidates_f32");
 }
 
+// f1e: cached lists merged with the dirty items the filter kept (gnnrec_topk_update_f32)
+void topk_update(const Tensor& rows, Tensor& idx, Tensor& vals, const Tensor& item_mark,
+                 const Tensor& counts, const Tensor& cand_cols, const Tensor& dirty_ids,
+                 const Tensor& h_user, const Tensor& h_item,
+                 const optional<Tensor>& exclude_indptr, const optional<Tensor>& exclude_indices,
+                 Tensor& redo) {
+  const OneDevice one_device_;
+  dev(rows, "rows", at::kLong);
+  dev(idx, "idx", at::kLong);
+  dev(vals, "vals", at::kFloat);
+  dev(item_mark, "item_mark", at::kInt);
+  dev(counts, "counts", at::kInt);
+  dev(cand_cols, "cand_cols", at::kInt);
+  dev(dirty_ids, "dirty_ids", at::kInt);
+  dev(h_user, "h_user", at::kFloat);
+  dev(h_item, "h_item", at::kFloat);
+  dev(exclude_indptr, "exclude_indptr", at::kLong);
+  dev(exclude_indices, "exclude_indices", at::kInt);
+  dev(redo, "redo", at::kInt);
+  const int64_t ldu = ld(h_user, "h_user"), ldi = ld(h_item, "h_item"), d = h_user.size(1);
+  const int64_t n_users = h_user.size(0), n_items = h_item.size(0), B = rows.numel();
+  TORCH_CHECK_VALUE(idx.dim() == 2 && idx.size(0) == n_users && idx.is_contiguous() &&
+                        vals.sizes() == idx.sizes() && vals.is_contiguous(),
+                    "idx / vals must be contiguous [n_users = ", n_users, ", k], got ",
+                    idx.sizes(), " and ", vals.sizes());
+  const int64_t k = idx.size(1);
+  TORCH_CHECK_VALUE(k >= 1 && k <= 64, "k must be in [1, 64], got ", k);
+  TORCH_CHECK_VALUE(cand_cols.dim() == 2 && cand_cols.size(0) == B && cand_cols.is_contiguous() &&
+                        counts.numel() == B && counts.is_contiguous() && rows.is_contiguous(),
+                    "rows / counts must be contiguous [", B, "] and cand_cols a contiguous [", B,
+                    ", cap], got ", cand_cols.sizes());
+  const int64_t cap = cand_cols.size(1);
+  TORCH_CHECK_VALUE(cap >= 1 && cap <= 256 - k, "cand_cols: cap must be in [1, 256 - k = ",
+                    256 - k, "], got ", cap);
+  TORCH_CHECK_VALUE(h_item.size(1) == d && d >= 4 && d % 4 == 0 && ldu % 4 == 0 && ldi % 4 == 0,
+                    "h_user / h_item must share a feature size that is a multiple of 4 (and row "
+                    "strides too), got ", h_user.sizes(), " and ", h_item.sizes());
+  TORCH_CHECK_VALUE(item_mark.numel() == n_items && item_mark.is_contiguous(),
+                    "item_mark must be contiguous [n_items = ", n_items, "]");
+  TORCH_CHECK_VALUE(dirty_ids.dim() == 1 && dirty_ids.is_contiguous(),
+                    "dirty_ids must be a contiguous list");
+  TORCH_CHECK_VALUE(redo.numel() == n_users && redo.is_contiguous(),
+                    "redo must be contiguous [n_users = ", n_users, "]");
+  TORCH_CHECK_VALUE(has(exclude_indptr) == has(exclude_indices),
+                    "exclude_indptr and exclude_indices come together");
+  TORCH_CHECK_VALUE(!has(exclude_indptr) ||
+                        (exclude_indptr->numel() == n_users + 1 &&
+                         exclude_indptr->is_contiguous() && exclude_indices->is_contiguous()),
+                    "exclude_indptr must be a contiguous [n_user_rows + 1] over h_user's rows");
+  if (meta(rows)) return;
+  const c10::DeviceGuard g(rows.device());
+  ck(gnnrec_topk_update_f32(p<int64_t>(rows), B, p<int64_t>(idx), p<float>(vals), n_users, k,
+                            p<int32_t>(item_mark), n_items, p<int32_t>(counts),
+                            p<int32_t>(cand_cols), cap, p<int32_t>(dirty_ids), dirty_ids.numel(),
+                            p<float>(h_user), ldu, p<float>(h_item), ldi, d,
+                            p<int64_t>(exclude_indptr), p<int32_t>(exclude_indices),
+                            p<int32_t>(redo), stream_of(rows)),
+     "gnnrec_topk_update_f32");
+}
+
 // ---------------------------------------------------------------- f1d popularity ratings
 // a per-row / per-column fp32 vector of a rating launch: contiguous, n entries
 void rating_vec(const Tensor& t, const char* name, int64_t n) {
@@ -2294,6 +2354,13 @@ TORCH_LIBRARY(gnnrec, m) {
   m.def("topk_candidates_f32(Tensor counts, Tensor cand_items, Tensor? user_rows, Tensor h_user, "
         "Tensor h_item, Tensor? exclude_indptr, Tensor? exclude_indices, int k, "
         "Tensor(a!) out_vals, Tensor(b!) out_idx) -> ()");
+  // one function under two names: topk_update, and the C entry's name like its neighbours
+  m.def("topk_update(Tensor rows, Tensor(a!) idx, Tensor(b!) vals, Tensor item_mark, "
+        "Tensor counts, Tensor cand_cols, Tensor dirty_ids, Tensor h_user, Tensor h_item, "
+        "Tensor? exclude_indptr, Tensor? exclude_indices, Tensor(c!) redo) -> ()");
+  m.def("topk_update_f32(Tensor rows, Tensor(a!) idx, Tensor(b!) vals, Tensor item_mark, "
+        "Tensor counts, Tensor cand_cols, Tensor dirty_ids, Tensor h_user, Tensor h_item, "
+        "Tensor? exclude_indptr, Tensor? exclude_indices, Tensor(c!) redo) -> ()");
   m.def("edge_mlp_dense_denominators_f32(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, "
         "Tensor b3, Tensor(a!) parts) -> ()");
   m.def("fold_partials_f32(Tensor parts, Tensor(a!) Z) -> ()");
@@ -2438,6 +2505,8 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("score_bf16_filter", &score_bf16_filter);       \
   m.impl("mask_excluded_f32", &mask_excluded_f32);       \
   m.impl("topk_candidates_f32", &topk_candidates_f32);   \
+  m.impl("topk_update", &topk_update);                   \
+  m.impl("topk_update_f32", &topk_update);               \
   m.impl("edge_mlp_dense_denominators_f32", &edge_mlp_dense_denominators); \
   m.impl("fold_partials_f32", &fold_partials_f32);       \
   m.impl("edge_mlp_dense_store_rating_f32", &edge_mlp_dense_store_rating); \

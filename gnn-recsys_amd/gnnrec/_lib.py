@@ -175,6 +175,10 @@ SIGNATURES = {
                                           _P, _I64, _P, _P, _P]),
     "gnnrec_topk_scored_candidates_f32": (_INT, [_P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _P,
                                                  _P, _P]),
+    # (rows, n_rows, idx, vals, n_users, k, item_mark, n_items, counts, cand_cols, cap,
+    #  dirty_ids, n_dirty, h_user, ldu, h_item, ldi, d, ex_indptr, ex_indices, redo, stream)
+    "gnnrec_topk_update_f32": (_INT, [_P, _I64, _P, _P, _I64, _I64, _P, _I64, _P, _P, _I64, _P,
+                                      _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P]),
     # popularity-weighted ratings (csrc/recommend_pop.hip, csrc/recommend.hip)
     "gnnrec_normalize_rows_f32": (_INT, [_P, _I64, _I64, _I64, _P, _P, _I64, _P]),
     "gnnrec_cos_denominator_parts": (_I64, [_I64]),

@@ -28,7 +28,7 @@ from __future__ import annotations
 import contextlib
 import os
 import time
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -75,12 +75,17 @@ class RefreshStats:
     recomputed (l = 0: re-embedded input rows; the table's row count where the whole layer
     ran); whole_layer[l][ntype]: the whole layer ran for that type instead of the row path;
     whole_pass: the full pass ran (first use, invalidate(), a changed weight or a relation
-    whose kernel route changed)."""
+    whose kernel route changed).  final_dirty[ntype]: the rows of the LAST layer's table that
+    can differ from before the refresh, as (mark int32 [n_rows], ids int64 ascending) device
+    tensors — the last layer's dirty set D_L; None: every row (the whole pass, or a type
+    above max_dirty_frac); a type that is absent: none of its rows.  A type that took the
+    whole layer for a huge row or the LSTM reducer keeps its D_L."""
 
     def __init__(self, n_layers: int, whole_pass: bool = False):
         self.rows: List[Dict[str, int]] = [{} for _ in range(n_layers + 1)]
         self.whole_layer: List[Dict[str, bool]] = [{} for _ in range(n_layers + 1)]
         self.whole_pass = whole_pass
+        self.final_dirty: Dict[str, Optional[Tuple[torch.Tensor, torch.Tensor]]] = {}
 
     def __repr__(self):
         return (f"RefreshStats(whole_pass={self.whole_pass}, rows={self.rows}, "
@@ -139,6 +144,9 @@ class IncrementalEmbeddings:
     torch.equal to the same layer of a full pass over a freshly built graph with the same
     edges.  refresh() writes the tables IN PLACE, so a consumer holding inc.h['user'] sees the
     new rows; only add_nodes replaces the tables of its type (one concatenation each).
+    `generation` counts the refreshes that wrote anything (a consumer that keeps state derived
+    from the tables compares it with the value it last saw), and each one reports the rows of
+    the last layer it rewrote in RefreshStats.final_dirty.
 
     The mutation methods wrap the HeteroGraph calls of the same name (same arguments and
     errors; a call that raises records nothing) and record on the device what they touched.
@@ -192,6 +200,7 @@ class IncrementalEmbeddings:
         self._keys = self._routes = None
         self._huge: Dict[tuple, torch.Tensor] = {}
         self.phase_ms: Optional[dict] = None
+        self.generation = 0
         self.refresh()
 
     @property
@@ -444,10 +453,12 @@ class IncrementalEmbeddings:
         full = self._stale or self._weight_keys() != self._keys
         if not full and not self._dirty:
             return RefreshStats(L)
+        self.generation += 1
         with self._phase("routes"):
             routes, sig = self._relation_routes()
         if full or sig != self._routes:
             stats = self._full_pass()
+            stats.final_dirty = {nt: None for nt in self.layers[-1]}
             self._keys, self._routes = self._weight_keys(), sig
             return self._clean(stats)
         stats = RefreshStats(L)
@@ -502,6 +513,9 @@ class IncrementalEmbeddings:
             with self._phase("rows"):
                 for nt, out in outs.items():
                     ops.scatter_rows(tables[nt], D[nt].ids, out)
+        # D is D_L now (each layer's marks are tensors of their own: handed out as they are)
+        stats.final_dirty = {nt: None if d.all else (d.mark, d.ids) for nt, d in D.items()
+                             if nt in self.layers[-1] and d.count}
         return self._clean(stats)
 
     def _clean(self, stats: RefreshStats) -> RefreshStats:

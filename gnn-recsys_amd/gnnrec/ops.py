@@ -1964,6 +1964,38 @@ def topk_candidates(counts: torch.Tensor, cand_items: torch.Tensor,
     return out_vals, out_idx
 
 
+UPDATE_SLOTS = 256   # gnnrec_topk_update_f32: k list entries + cap candidates per row
+UPDATE_MAX_K = 64
+
+
+def topk_update(rows: torch.Tensor, idx: torch.Tensor, vals: torch.Tensor,
+                item_mark: torch.Tensor, counts: torch.Tensor, cand_cols: torch.Tensor,
+                dirty_ids: torch.Tensor, h_user: torch.Tensor, h_item: torch.Tensor,
+                redo: torch.Tensor, exclude_indptr: Optional[torch.Tensor] = None,
+                exclude_indices: Optional[torch.Tensor] = None) -> None:
+    """The cached lists idx / vals [n_users, k] of the clean user rows `rows`, in place, after
+    a refresh that rewrote the item rows marked in item_mark [n_items] (int32; dirty_ids
+    int32, ascending, lists them): per row the list's dirty entries dropped, its candidates
+    (counts / cand_cols [B, cap] of score_bf16_filter over the dirty items' bf16 table with
+    tau = the list's last score; columns are positions in dirty_ids) minus the user's
+    excluded items rescored with the fp32 cosine of the refreshed tables, and the k best
+    written where that is provably the exhaustive ranking's list.  The other
+    rows, and rows with counts > cap, get redo[user] = 1 (int32 [n_users], zeroed by the
+    caller) and stay as they were.  k <= UPDATE_MAX_K, cap <= UPDATE_SLOTS - k."""
+    _dev(rows, "rows", torch.int64)
+    _dev(idx, "idx", torch.int64)
+    _dev(vals, "vals", torch.float32)
+    _dev(item_mark, "item_mark", torch.int32)
+    _dev(counts, "counts", torch.int32)
+    _dev(cand_cols, "cand_cols", torch.int32)
+    _dev(dirty_ids, "dirty_ids", torch.int32)
+    _dev(h_user, "h_user", torch.float32)
+    _dev(h_item, "h_item", torch.float32)
+    _dev(redo, "redo", torch.int32)
+    _T().topk_update(rows, idx, vals, item_mark, counts, cand_cols, dirty_ids, h_user, h_item,
+                     exclude_indptr, exclude_indices, redo)
+
+
 # ---- f1c: many-user top-k for the MLP head (csrc/heads.hip, csrc/recommend.hip) ----
 def _dense_mlp_operands(P, Q, W2, b2, w3, b3):
     for t, n in ((P, "P"), (Q, "Q"), (W2, "W2"), (b2, "b2"), (w3, "w3"), (b3, "b3")):

@@ -20,7 +20,9 @@ the MLP head's score instead, exactly and again without a score matrix (DESIGN.m
 """
 from __future__ import annotations
 
+import contextlib
 import math
+import time
 from collections import defaultdict
 
 import numpy as np
@@ -533,6 +535,241 @@ def recommend_for_graph(g, h, k, user_ids=None, etype='bought-by', use_popularit
     if user_ids is not None:
         user_ids = torch.as_tensor(user_ids, dtype=torch.int64, device=dev)
     return recommend(h['user'], h['item'], k, user_ids, exclude, **kw)
+
+
+# ---- cached lists kept current after a refresh ---------------
+# Largest dirty share of the item rows at which update_recommendations still runs the merge;
+# above it the whole call re-ranks.  The sweep found no crossover up to its largest share: at
+# 0.76 of the items (and 0.75 of the users) dirty every run of the update still beat every run
+# of a full re-rank, 294 against 330 ms (profiles/live_recs_ab.md); nothing above
+# that share is measured
+LIVE_MAX_DIRTY_FRAC = 0.75
+
+
+@contextlib.contextmanager
+def _phase(phase_ms, name):
+    """With a dict: the part's time between two device synchronisations, added to
+    phase_ms[name] (a measurement, tools/bench_live_recs.py)."""
+    if phase_ms is None:
+        yield
+        return
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    try:
+        yield
+    finally:
+        torch.cuda.synchronize()
+        phase_ms[name] = phase_ms.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
+
+
+def no_dirty_rows(n_rows, device):
+    """The final_dirty entry of a type none of whose rows changed: (zero marks, no ids)."""
+    return (torch.zeros(n_rows, dtype=torch.int32, device=device),
+            torch.empty(0, dtype=torch.int64, device=device))
+
+
+def _dirty_entry(entry, n_rows, what):
+    if entry is None:
+        return None
+    mark, ids = entry
+    ops._dev(mark, f'{what} marks', torch.int32)
+    ops._dev(ids, f'{what} ids', torch.int64)
+    if mark.numel() != n_rows:
+        raise ValueError(f'{what} marks must have {n_rows} entries, got {mark.numel()}')
+    return mark.contiguous(), ids.reshape(-1).contiguous()
+
+
+def _marked_ids(mark, count):
+    """The ascending ids of the `count` non-zero entries of an int32 mark table."""
+    ids = torch.empty(count, dtype=torch.int64, device=mark.device)
+    if count:
+        _lib.torch_ops().compact_marked(mark, ops.exclusive_scan(mark), ids)
+    return ids
+
+
+def update_recommendations(idx, vals, h_user, h_item, dirty_users, dirty_items, exclude=None, *,
+                           batch_size=8192, max_dirty_frac=None, return_stats=False,
+                           phase_ms=None, **recommend_kw):
+    """The cached lists of EVERY user brought up to date, in place, after a refresh of the
+    embedding tables: idx / vals [n_users, k] (row r = user r) as recommend(h_user_old,
+    h_item_old, k, None, exclude_old) returned them become, bit for bit in both, what
+    recommend(h_user, h_item, k, None, exclude) returns now.  Cosine head, no popularity.
+
+    dirty_users / dirty_items: the rows the refresh rewrote, RefreshStats.final_dirty's entries
+    — (mark int32 [n_rows], ids int64 ascending) device tensors, or None for every row
+    (no_dirty_rows(n, device) for none); a row is dirty where its mark is non-zero, and ids
+    lists exactly those rows (its length is the count the call relies on: nothing reads the
+    device to check it).  Every other row of the tables, and the exclusion row
+    of every user outside dirty_users, must be bitwise what the lists were computed from.
+
+    A clean user's score against a clean item has not changed (the cosine reads the two rows
+    and nothing else), so its list can only change through dirty items.  Per batch of clean
+    users: the dirty items (normalised, bf16, once per call) are filtered against
+    tau = the list's last score (the bf16 filter of recommend(): every dirty item scoring
+    >= tau is kept), and ops.topk_update merges the kept ones into the list — dropping the
+    list's own dirty entries — where the merged list is provably the exact one (DESIGN.md
+    §22: the old list was padded, or k entries remain and the k-th is not worse than the old
+    last entry).  The rows it cannot settle, the rows whose candidates exceed the slots, and
+    the dirty users are re-ranked by one recommend(..., user_rows=...) call, so the result
+    never depends on the merge.
+
+    The whole call re-ranks (stats['full']) when either dirty entry is None, more than
+    max_dirty_frac (default LIVE_MAX_DIRTY_FRAC) of the items are dirty, k > 64, or
+    recommend's own fast path does not apply (d % 4 != 0, d > REC_MAX_D).  recommend_kw
+    (sample, cand_cap, pop_sample) goes to recommend; head= and popularity= are refused (with
+    popularity every user's denominator changes with any item; the MLP head has no merge yet).
+
+    The host reads the device once (the size of the redo set and the count statistics, one
+    transfer) apart from what the recommend call reads.  -> None, or with return_stats the
+    dict: clean_rows, dirty_users, dirty_items, redo_rows (clean rows the merge handed back,
+    overflowed ones included), overflow_rows (their candidates exceeded the slots),
+    candidates_max (kept dirty items of a row, counted past the cap), full.  Rows left
+    untouched are not counted (it would take a gather of every list's marks).
+
+    phase_ms: for measurements only (tools/bench_live_recs.py).  With a dict, the device is
+    synchronised around every part and the parts' times are added to its keys 'filter',
+    'merge' and 'rerank' in ms; None (the default) synchronises nothing."""
+    if recommend_kw.get('head') is not None or recommend_kw.get('popularity') is not None:
+        raise ValueError('update_recommendations: the cosine head without popularity only '
+                         '(head= / popularity= are refused)')
+    ops._dev(h_user, 'h_user', torch.float32)
+    ops._dev(h_item, 'h_item', torch.float32)
+    ops._dev(idx, 'idx', torch.int64)
+    ops._dev(vals, 'vals', torch.float32)
+    if h_user.dim() != 2 or h_item.dim() != 2 or h_user.shape[1] != h_item.shape[1]:
+        raise ValueError(f'h_user / h_item must be 2-D with one feature size, got '
+                         f'{tuple(h_user.shape)} and {tuple(h_item.shape)}')
+    n_users, d = h_user.shape
+    n_items = h_item.shape[0]
+    if idx.dim() != 2 or idx.shape[0] != n_users or idx.shape[1] < 1 or \
+            vals.shape != idx.shape or not (idx.is_contiguous() and vals.is_contiguous()):
+        raise ValueError(f'idx / vals must be contiguous [n_users = {n_users}, k], got '
+                         f'{tuple(idx.shape)} and {tuple(vals.shape)}')
+    k, batch_size = idx.shape[1], int(batch_size)
+    frac = LIVE_MAX_DIRTY_FRAC if max_dirty_frac is None else float(max_dirty_frac)
+    if batch_size < 1 or not 0.0 <= frac <= 1.0:
+        raise ValueError('update_recommendations: batch_size must be >= 1 and max_dirty_frac '
+                         'in [0, 1]')
+    du = _dirty_entry(dirty_users, n_users, 'dirty_users')
+    di = _dirty_entry(dirty_items, n_items, 'dirty_items')
+    if exclude is not None:
+        ex_ptr, ex_idx = exclude
+        ops._dev(ex_ptr, 'exclude indptr', torch.int64)
+        ops._dev(ex_idx, 'exclude indices', torch.int32)
+        if ex_ptr.numel() != n_users + 1:
+            raise ValueError(f'exclude indptr must have n_users + 1 = {n_users + 1} entries, '
+                             f'got {ex_ptr.numel()}')
+        exclude = (ex_ptr.contiguous(), ex_idx.contiguous())
+    dev = h_item.device
+    h_user, h_item = h_user.contiguous(), h_item.contiguous()
+    stats = {'clean_rows': 0, 'dirty_users': n_users, 'dirty_items': n_items, 'redo_rows': 0,
+             'overflow_rows': 0, 'candidates_max': 0, 'full': True}
+    fast = d % 4 == 0 and 4 <= d <= REC_MAX_D and k <= ops.UPDATE_MAX_K
+    if du is None or di is None or not fast or n_users == 0 or n_items == 0 or \
+            di[1].numel() > frac * n_items:
+        with _phase(phase_ms, 'rerank'):
+            i, v = recommend(h_user, h_item, k, None, exclude, batch_size=batch_size,
+                             **recommend_kw)
+            idx.copy_(i)
+            vals.copy_(v)
+        return stats if return_stats else None
+    (umark, uids), (imark, iids) = du, di
+    n_du, n_di = uids.numel(), iids.numel()
+    stats.update(clean_rows=n_users - n_du, dirty_users=n_du, dirty_items=n_di, full=False)
+    if n_du == 0 and n_di == 0:
+        return stats if return_stats else None
+    ex0, ex1 = (None, None) if exclude is None else exclude
+    todo = uids
+    if n_di and n_du < n_users:
+        cap = ops.UPDATE_SLOTS - k
+        with _phase(phase_ms, 'filter'):
+            clean = _marked_ids((umark == 0).to(torch.int32), n_users - n_du)
+            items_bf = ops.normalize_rows_bf16(h_item, iids)     # converted once per call
+            dirty_ids = iids.to(torch.int32)
+        redo = torch.zeros(n_users, dtype=torch.int32, device=dev)
+        counts = torch.zeros(clean.numel(), dtype=torch.int32, device=dev)
+        cand = torch.empty((min(batch_size, clean.numel()), cap), dtype=torch.int32, device=dev)
+        last = vals[:, k - 1]
+        for b0 in range(0, clean.numel(), batch_size):
+            rows = clean[b0:b0 + batch_size]
+            cnt, cnd = counts[b0:b0 + rows.numel()], cand[:rows.numel()]
+            with _phase(phase_ms, 'filter'):
+                users_bf = ops.normalize_rows_bf16(h_user, rows)
+                tau = last.index_select(0, rows)     # -inf for a padded list: keeps them all
+                ops.score_bf16_filter(users_bf, items_bf, tau, cnt, cnd)
+            with _phase(phase_ms, 'merge'):
+                ops.topk_update(rows, idx, vals, imark, cnt, cnd, dirty_ids, h_user, h_item,
+                                redo, ex0, ex1)
+        n_redo, n_over, c_max = torch.stack(       # the call's one readback
+            [redo.sum(), (counts > cap).sum(), counts.max()]).tolist()
+        stats.update(redo_rows=n_redo, overflow_rows=n_over, candidates_max=c_max)
+        if n_redo:
+            todo = _marked_ids(torch.bitwise_or(redo, (umark != 0).to(torch.int32)),
+                               n_redo + n_du)
+    if todo.numel():
+        with _phase(phase_ms, 'rerank'):
+            i, v = recommend(h_user, h_item, k, todo, exclude, batch_size=batch_size,
+                             **recommend_kw)
+            ops.scatter_rows(idx, todo, i)
+            ops.scatter_rows(vals, todo, v)
+    return stats if return_stats else None
+
+
+class LiveRecommendations:
+    """Every user's top-k list of a graph under edits, kept equal to recommend_for_graph on the
+    refreshed embeddings.
+
+        inc = IncrementalEmbeddings(g, model)
+        live = LiveRecommendations(inc, k=10)          # recommend_for_graph for every user
+        inc.add_edges(u, v, etype='buys'); inc.add_edges(v, u, etype='bought-by')
+        refresh_stats, update_stats = live.refresh()   # inc.refresh() + update_recommendations
+
+    idx / vals [n_users, k] stay valid and are updated in place; they are replaced (by grown
+    tensors, the new rows re-ranked as dirty users) only when users were added.  The items each
+    user has an `etype` edge from are excluded, as in recommend_for_graph.  A refresh of `inc`
+    that did not go through this object (inc.generation shows it) makes the next refresh()
+    re-rank every user.  kw (batch_size, sample, cand_cap) goes to recommend; head= and
+    popularity are refused.  phase_ms: for measurements only — set it to a dict and refresh()
+    synchronises around its parts and adds their times ('refresh', 'filter', 'merge',
+    'rerank', ms) to it."""
+
+    def __init__(self, inc, k, etype='bought-by', max_dirty_frac=None, **kw):
+        if kw.get('head') is not None or kw.get('popularity') is not None or \
+                kw.get('use_popularity'):
+            raise ValueError('LiveRecommendations: the cosine head without popularity only '
+                             '(head= / popularity are refused)')
+        self.inc, self.k, self.etype = inc, int(k), etype
+        self.max_dirty_frac, self.kw = max_dirty_frac, dict(kw)
+        self.phase_ms = None
+        self.idx, self.vals = recommend_for_graph(inc.g, inc.h, self.k, None, etype, **self.kw)
+        self._generation = inc.generation
+
+    def refresh(self):
+        """inc.refresh(), then the lists of every user brought up to date ->
+        (RefreshStats, the stats of update_recommendations)."""
+        inc = self.inc
+        skipped = inc.generation != self._generation   # a refresh this object did not see
+        with _phase(self.phase_ms, 'refresh'):
+            rstats = inc.refresh()
+        h = inc.h
+        dev, n_users, n_items = h['item'].device, h['user'].shape[0], h['item'].shape[0]
+        grown = n_users - self.idx.shape[0]
+        if grown > 0:    # users were added: their rows are dirty users, re-ranked below
+            self.idx = torch.cat([self.idx, self.idx.new_full((grown, self.k), -1)])
+            self.vals = torch.cat([self.vals, self.vals.new_full((grown, self.k),
+                                                                 float('-inf'))])
+        fd = rstats.final_dirty
+        du = di = None
+        if not skipped:
+            du = fd['user'] if 'user' in fd else no_dirty_rows(n_users, dev)
+            di = fd['item'] if 'item' in fd else no_dirty_rows(n_items, dev)
+        ex_ptr, ex_idx = inc.g.in_csr(self.etype)[:2]
+        ustats = update_recommendations(self.idx, self.vals, h['user'], h['item'], du, di,
+                                        (ex_ptr.to(dev), ex_idx.to(dev)),
+                                        max_dirty_frac=self.max_dirty_frac, return_stats=True,
+                                        phase_ms=self.phase_ms, **self.kw)
+        self._generation = inc.generation
+        return rstats, ustats
 
 
 def recs_to_metrics_device(idx, user_rows, gt_indptr, gt_indices, n_items):

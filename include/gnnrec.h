@@ -723,6 +723,33 @@ int gnnrec_topk_scored_candidates_f32(const int32_t* counts, const int32_t* cand
                                       const int32_t* exclude_indices, int64_t k, float* out_vals,
                                       int64_t* out_idx, void* stream);
 
+/* ---- f1e: cached top-k lists kept current after a refresh -------------------
+ * idx / vals [n_users, k] (int64 / fp32, contiguous) hold every user's list as
+ * gnnrec_topk_candidates_f32 ranks it (padded with (-1, -inf)) for the tables BEFORE a
+ * refresh that rewrote exactly the item rows v with item_mark[v] != 0 (int32 [n_items]) —
+ * dirty_ids[n_dirty] (int32, ascending) lists them — and left the user rows rows[0 .. n_rows)
+ * (distinct) and their exclusion rows as they were.  counts / cand_cols [n_rows, cap] come
+ * from gnnrec_score_bf16_filter over the bf16 table of the refreshed rows dirty_ids, with
+ * tau[r] = vals[rows[r]][k - 1]: cand_cols are positions in dirty_ids.  Per row, in place:
+ * the list's dirty entries are dropped, its clean entries keep their scores, the candidates
+ * not excluded for the user are rescored from the refreshed h_user / h_item (bitwise
+ * gnnrec_sddmm_cos_f32) and the k best of both are written — IF that is provably the list
+ * an exhaustive ranking of the refreshed tables gives: the old list was padded, or k
+ * entries remain and the k-th is not worse, by (score desc, item asc), than the old list's
+ * last entry.  Otherwise, and where counts[r] > cap, redo[rows[r]] = 1 (int32 [n_users],
+ * zeroed by the caller) and the row is left as it was: the caller re-ranks those rows.  A row
+ * with no dirty entry and no candidate is not written at all.  1 <= k <= 64,
+ * 1 <= cap <= 256 - k, d % 4 == 0, strides multiples of 4, 16-byte aligned tables; the
+ * exclusion CSR (both pointers may be NULL) is gnnrec_topk_candidates_f32's.  No launch when
+ * n_rows or n_dirty is 0.  DESIGN.md §22 holds the proof. */
+int gnnrec_topk_update_f32(const int64_t* rows, int64_t n_rows, int64_t* idx, float* vals,
+                           int64_t n_users, int64_t k, const int32_t* item_mark,
+                           int64_t n_items, const int32_t* counts, const int32_t* cand_cols,
+                           int64_t cap, const int32_t* dirty_ids, int64_t n_dirty,
+                           const float* h_user, int64_t ldu, const float* h_item, int64_t ldi,
+                           int64_t d, const int64_t* exclude_indptr,
+                           const int32_t* exclude_indices, int32_t* redo, void* stream);
+
 /* ---- f1d: popularity-weighted ratings (cosine head) ------------------------
  * R(u, v) = expf(score(u, v)) / Z_u + p_v, p_v = popularity[v] * weight, Z_u the sum of
  * expf(g(u, v)) over ALL items in a fixed order (csrc/rating.hpp, csrc/recommend_pop.hip,
