@@ -345,6 +345,60 @@ static void validation() {
                                                 i16, i16, f16, 0, nullptr) == GNNREC_EINVAL &&
             err_has("cap must be"),
         "dense filter rating cap");
+  // the full-ranking evaluation (rank.hip): every refusal comes before a launch
+  CHECK(gnnrec_rank_eps(128) == 544 * 0x1p-24 && gnnrec_rank_eps(100) == gnnrec_rank_eps(104) &&
+            gnnrec_rank_eps(0) == 0.0,
+        "rank eps");
+  CHECK(gnnrec_cos_scores_f32(f16, 4, f16, 9, 12, f16, 9, nullptr) == GNNREC_EINVAL &&
+            err_has("multiple of 8"),
+        "cos scores dpad");
+  CHECK(gnnrec_cos_scores_f32(f16, 4, f16, 9, 16, f16, 8, nullptr) == GNNREC_EINVAL &&
+            err_has("ldo"),
+        "cos scores ldo < n_items");
+  CHECK(gnnrec_cos_scores_f32(nullptr, 0, nullptr, 9, 16, nullptr, 9, nullptr) == GNNREC_OK,
+        "cos scores no users");
+  CHECK(gnnrec_rank_count_f32(f16, 4, f16, 9, 12, f16, i16, i16, i16, i16, 64, nullptr) ==
+            GNNREC_EINVAL && err_has("multiple of 8"),
+        "rank count dpad");
+  CHECK(gnnrec_rank_count_f32(f16, 4, f16, 9, 16, f16, i16, i16, i16, i16, 4097, nullptr) ==
+            GNNREC_EINVAL && err_has("cap must be"),
+        "rank count cap");
+  CHECK(gnnrec_rank_count_f32(f16, 4, reinterpret_cast<float*>(8), 9, 16, f16, i16, i16, i16, i16,
+                              64, nullptr) == GNNREC_EINVAL && err_has("unaligned"),
+        "rank count unaligned items");
+  CHECK(gnnrec_rank_count_f32(f16, 4, f16, 9, 16, nullptr, i16, i16, i16, i16, 64, nullptr) ==
+            GNNREC_EINVAL && err_has("null pointer"),
+        "rank count null thresholds");
+  CHECK(gnnrec_rank_count_f32(f16, 4, f16, 9, 16, f16, i16, nullptr, i16, i16, 64, nullptr) ==
+            GNNREC_EINVAL && err_has("null ahead"),
+        "rank count null ahead");
+  CHECK(gnnrec_rank_count_f32(nullptr, 0, nullptr, 9, 16, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, 64, nullptr) == GNNREC_OK,
+        "rank count no rows");
+  CHECK(gnnrec_rank_resolve_f32(l16, l16, f16, i16, i16, i16, 64, 3, f16, 16, 4, f16, 16, 9, 6,
+                                nullptr, nullptr, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("d % 4"),
+        "rank resolve d % 4");
+  CHECK(gnnrec_rank_resolve_f32(l16, l16, f16, i16, i16, i16, 0, 3, f16, 16, 4, f16, 16, 9, 16,
+                                nullptr, nullptr, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("cap must be"),
+        "rank resolve cap");
+  CHECK(gnnrec_rank_resolve_f32(l16, l16, f16, i16, i16, i16, 64, 3, f16, 16, 4, f16, 16, 9, 16,
+                                l16, nullptr, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("come together"),
+        "rank resolve indptr without indices");
+  CHECK(gnnrec_rank_resolve_f32(l16, l16, f16, i16, i16, i16, 64, 3, f16, 16, 4, f16, 16, 9, 16,
+                                nullptr, nullptr, nullptr, nullptr) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "rank resolve null rank");
+  CHECK(gnnrec_rank_resolve_f32(l16, l16, f16, i16, i16, i16, 64, 3, reinterpret_cast<float*>(8),
+                                16, 4, f16, 16, 9, 16, nullptr, nullptr, l16, nullptr) ==
+            GNNREC_EINVAL && err_has("aligned"),
+        "rank resolve unaligned table");
+  CHECK(gnnrec_rank_resolve_f32(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 64, 0,
+                                nullptr, 16, 4, nullptr, 16, 9, 16, nullptr, nullptr, nullptr,
+                                nullptr) == GNNREC_OK,
+        "rank resolve no pairs");
   // edge removal (csr_filter.hip): every refusal comes before the first memset or launch;
   // an empty problem still writes the status and indptr', so its host side is the
   // workspace query, which must give room for them

@@ -26,17 +26,11 @@
 // The partials of a batch are n_items / 1024 x n_users floats: 32 MB for 8192 users x 1M
 // items.
 //
-// THE KERNEL.  256 threads, four waves.  The block's 128 user rows are staged once into LDS
-// (64 KB: 128 rows x 128 columns, 16-B chunks xor-swizzled by the row so that the 16 lanes of
-// a ds_read_b128 phase fall into distinct bank groups without padding; wider tables are
-// staged 128 columns at a time) and every wave multiplies all of them (4 x 32 rows, 64
-// accumulator registers) with a 32-item subtile whose rows it loads straight from the table,
-// 16 B per lane and k-step.  Both tables are stored with each group of 8 columns permuted to
-// [0, 2, 4, 6, 1, 3, 5, 7] (normalize_rows_f32): lane half h's 16-B load at 8 s + 4 h then
-// holds k = 8 s + h + 2 j, j = 0..3 — the operand of the j-th of four consecutive MFMAs, k
-// ascending.  Rows and items past the end read a clamped (valid) row and are masked in the
-// epilogue.  The epilogue writes nothing but the partials.
+// THE KERNEL.  The tile loop (staging, swizzle, operand order, the clamped loads past the end)
+// is cos_tile.hpp's, shared with the full-ranking count pass (rank.hip); this kernel's epilogue
+// adds expf of the lane's column into the row registers and writes nothing but the partials.
 #include "common.hpp"
+#include "cos_tile.hpp"
 #include "rating.hpp"
 #include <algorithm>
 #include <cmath>
@@ -44,15 +38,9 @@
 namespace gnnrec {
 namespace {
 
-constexpr int kZItems = 1024;  // items per partial
-constexpr int kZK = 128;       // columns staged at a time
-constexpr int kZMaxD = 2048;
 constexpr double kRecEpsD = 0.0078125 + 0.00048828125;  // recommend.hip's eps = 2^-7 + 2^-11
 constexpr double kRatingRound = 0x1p-20;  // fp32 rounding of expf and the divide, both sides
 constexpr double kRatingSlack = 0x1p-22;  // fp32 rounding of the add, both sides, per unit of p
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------ normalise ----
 // One wave per row, the sum of squares and the divide of normalize_rows_bf16's 16-B path (the
@@ -93,86 +81,19 @@ __global__ __launch_bounds__(256, 2) void cos_denominator_kernel(
     const float* __restrict__ U, int64_t B, const float* __restrict__ V, int64_t n, int dpad,
     int64_t n_ut, float* __restrict__ part) {
   __shared__ f32x4 sA[128 * 32];  // [row][chunk ^ (row & 31)]; the wave sums at the end
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l31 = lane & 31, h = lane >> 5;
   const int64_t ut = (int64_t)blockIdx.x % n_ut, pi = (int64_t)blockIdx.x / n_ut;
-  const int nkc = (dpad + kZK - 1) / kZK;
   float rs[4][16];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) rs[i][r] = 0.f;
-  for (int it = 0; it < kZItems / 128; ++it) {
-    if (pi * kZItems + (int64_t)it * 128 >= n) break;  // block-uniform: nothing left to add
-    const int64_t c = pi * kZItems + (int64_t)(it * 4 + wave) * 32 + l31;
-    const float* pb = V + min(c, n - 1) * dpad + 4 * h;
-    f32x16 acc[4];
+  cos_tile_loop(U, B, V, n, dpad, ut, pi, sA, [&](const f32x16(&acc)[4], int64_t) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    for (int kc = 0; kc < nkc; ++kc) {
-      const int k0 = kc * kZK;
-      const int ks = min(kZK, dpad - k0) / 8;  // dpad % 8 == 0
-      if (nkc > 1 || it == 0) {  // block-uniform
-        __syncthreads();         // the previous chunk's reads are done
-#pragma unroll 4
-        for (int p = 0; p < 16; ++p) {
-          const int idx = tid + p * 256, row = idx >> 5, ch = idx & 31;
-          const int64_t r = min(ut * 128 + row, B - 1);  // past the end: a valid row, masked later
-          f32x4 v = {0.f, 0.f, 0.f, 0.f};
-          if (k0 + ch * 4 < dpad) v = *reinterpret_cast<const f32x4*>(U + r * dpad + k0 + ch * 4);
-          sA[row * 32 + (ch ^ (row & 31))] = v;
-        }
-        __syncthreads();
-      }
-      // the item rows, 8 k-steps (256 B a row) at a time: every load of a half in flight
-      // before its first MFMA needs one
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        f32x4 b[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-          if (half * 8 + s < ks) b[s] = *reinterpret_cast<const f32x4*>(pb + k0 + 64 * half + 8 * s);
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-          if (half * 8 + s < ks) {  // wave-uniform
-            f32x4 a[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-              a[i] = sA[(i * 32 + l31) * 32 + ((2 * (half * 8 + s) + h) ^ l31)];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-              for (int i = 0; i < 4; ++i)
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][j], b[s][j], acc[i], 0, 0, 0);
-          }
-        }
-      }
-    }
-    if (c < n) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) rs[i][r] += expf(acc[i][r]);
-    }
-  }
-  // C layout: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-  __syncthreads();  // every wave's reads of the staged rows are done: sA becomes the sums
-  float* red = reinterpret_cast<float*>(sA);
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float x = rs[i][r];
-#pragma unroll
-      for (int off = 1; off < 32; off <<= 1) x += __shfl_xor(x, off);
-      if (l31 == 0) red[wave * 128 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] = x;
-    }
-  __syncthreads();
-  const int64_t row = ut * 128 + tid;
-  if (tid < 128 && row < B)
-    part[pi * B + row] = ((red[tid] + red[128 + tid]) + red[256 + tid]) + red[384 + tid];
+      for (int r = 0; r < 16; ++r) rs[i][r] += expf(acc[i][r]);
+  });
+  fold_tile_rows(rs, reinterpret_cast<float*>(sA), B, ut, pi, part);
 }
 
 // Z[u] = the row's partials folded in index order.

@@ -960,6 +960,112 @@ void cos_denominators(const Tensor& users, const Tensor& items, Tensor& parts, T
      "gnnrec_cos_denominators_f32");
 }
 
+// ---------------------------------------------------------------- f1f full-ranking evaluation
+// the two normalize_rows_f32 tables of an MFMA pass -> dpad
+int64_t f32_tables(const Tensor& users, const Tensor& items) {
+  dev(users, "users", at::kFloat);
+  dev(items, "items", at::kFloat);
+  TORCH_CHECK_VALUE(users.dim() == 2 && items.dim() == 2 && users.is_contiguous() &&
+                        items.is_contiguous(),
+                    "users / items must be contiguous 2-D fp32 tables");
+  const int64_t dpad = users.size(1);
+  TORCH_CHECK_VALUE(items.size(1) == dpad && dpad >= 8 && dpad % 8 == 0 && dpad <= 2048,
+                    "users / items must share a dpad that is a multiple of 8 in [8, 2048], got ",
+                    users.size(1), " and ", items.size(1));
+  return dpad;
+}
+
+void cos_scores(const Tensor& users, const Tensor& items, Tensor& out) {
+  const OneDevice one_device_;
+  const int64_t dpad = f32_tables(users, items);
+  dev(out, "out", at::kFloat);
+  const int64_t B = users.size(0), n = items.size(0);
+  const int64_t ldo = ld(out, "out");
+  TORCH_CHECK_VALUE(out.size(0) == B && out.size(1) == n, "out must be [", B, ", ", n, "], got ",
+                    out.sizes());
+  if (meta(users)) return;
+  const c10::DeviceGuard g(users.device());
+  ck(gnnrec_cos_scores_f32(p<float>(users), B, p<float>(items), n, dpad, p<float>(out), ldo,
+                           stream_of(users)),
+     "gnnrec_cos_scores_f32");
+}
+
+void rank_count(const Tensor& users, const Tensor& items, const Tensor& thr, Tensor& parts,
+                Tensor& ahead, Tensor& band_counts, Tensor& band_items) {
+  const OneDevice one_device_;
+  const int64_t dpad = f32_tables(users, items);
+  dev(thr, "thr", at::kFloat);
+  dev(parts, "parts", at::kInt);
+  dev(ahead, "ahead", at::kInt);
+  dev(band_counts, "band_counts", at::kInt);
+  dev(band_items, "band_items", at::kInt);
+  const int64_t B = users.size(0), n = items.size(0);
+  TORCH_CHECK_VALUE(thr.numel() == B && ahead.numel() == B && band_counts.numel() == B &&
+                        thr.is_contiguous() && ahead.is_contiguous() &&
+                        band_counts.is_contiguous(),
+                    "thr / ahead / band_counts must be contiguous [", B, "]");
+  TORCH_CHECK_VALUE(band_items.dim() == 2 && band_items.size(0) == B && band_items.is_contiguous(),
+                    "band_items must be a contiguous [", B, ", cap], got ", band_items.sizes());
+  const int64_t cap = band_items.size(1);
+  TORCH_CHECK_VALUE(cap >= 1 && cap <= 4096, "band_items: cap must be in [1, 4096], got ", cap);
+  const int64_t n_part = gnnrec_cos_denominator_parts(n);
+  TORCH_CHECK_VALUE(parts.numel() >= n_part * B && parts.is_contiguous(),
+                    "parts must hold ", n_part, " x ", B, " int32, got ", parts.sizes());
+  if (meta(users)) return;
+  const c10::DeviceGuard g(users.device());
+  ck(gnnrec_rank_count_f32(p<float>(users), B, p<float>(items), n, dpad, p<float>(thr),
+                           p<int32_t>(parts), p<int32_t>(ahead), p<int32_t>(band_counts),
+                           p<int32_t>(band_items), cap, stream_of(users)),
+     "gnnrec_rank_count_f32");
+}
+
+void rank_resolve(const Tensor& users, const Tensor& items, const Tensor& thr, const Tensor& ahead,
+                  const Tensor& band_counts, const Tensor& band_items, const Tensor& h_user,
+                  const Tensor& h_item, const optional<Tensor>& exclude_indptr,
+                  const optional<Tensor>& exclude_indices, Tensor& rank) {
+  const OneDevice one_device_;
+  dev(users, "users", at::kLong);
+  dev(items, "items", at::kLong);
+  dev(thr, "thr", at::kFloat);
+  dev(ahead, "ahead", at::kInt);
+  dev(band_counts, "band_counts", at::kInt);
+  dev(band_items, "band_items", at::kInt);
+  dev(h_user, "h_user", at::kFloat);
+  dev(h_item, "h_item", at::kFloat);
+  dev(exclude_indptr, "exclude_indptr", at::kLong);
+  dev(exclude_indices, "exclude_indices", at::kInt);
+  dev(rank, "rank", at::kLong);
+  const int64_t P = users.numel();
+  TORCH_CHECK_VALUE(items.numel() == P && thr.numel() == P && ahead.numel() == P &&
+                        band_counts.numel() == P && rank.numel() == P && users.is_contiguous() &&
+                        items.is_contiguous() && thr.is_contiguous() && ahead.is_contiguous() &&
+                        band_counts.is_contiguous() && rank.is_contiguous(),
+                    "users / items / thr / ahead / band_counts / rank must be contiguous [", P,
+                    "]");
+  TORCH_CHECK_VALUE(band_items.dim() == 2 && band_items.size(0) == P && band_items.is_contiguous(),
+                    "band_items must be a contiguous [", P, ", cap], got ", band_items.sizes());
+  const int64_t cap = band_items.size(1);
+  TORCH_CHECK_VALUE(cap >= 1 && cap <= 4096, "band_items: cap must be in [1, 4096], got ", cap);
+  const int64_t ldu = ld(h_user, "h_user"), ldi = ld(h_item, "h_item"), d = h_user.size(1);
+  TORCH_CHECK_VALUE(h_item.size(1) == d && d >= 4 && d % 4 == 0 && ldu % 4 == 0 && ldi % 4 == 0,
+                    "h_user / h_item must share a feature size that is a multiple of 4 (and row "
+                    "strides too), got ", h_user.sizes(), " and ", h_item.sizes());
+  TORCH_CHECK_VALUE(has(exclude_indptr) == has(exclude_indices),
+                    "exclude_indptr and exclude_indices come together");
+  TORCH_CHECK_VALUE(!has(exclude_indptr) ||
+                        (exclude_indptr->numel() == h_user.size(0) + 1 &&
+                         exclude_indptr->is_contiguous() && exclude_indices->is_contiguous()),
+                    "exclude_indptr must be a contiguous [n_user_rows + 1] over h_user's rows");
+  if (meta(users)) return;
+  const c10::DeviceGuard g(users.device());
+  ck(gnnrec_rank_resolve_f32(p<int64_t>(users), p<int64_t>(items), p<float>(thr),
+                             p<int32_t>(ahead), p<int32_t>(band_counts), p<int32_t>(band_items),
+                             cap, P, p<float>(h_user), ldu, h_user.size(0), p<float>(h_item), ldi,
+                             h_item.size(0), d, p<int64_t>(exclude_indptr),
+                             p<int32_t>(exclude_indices), p<int64_t>(rank), stream_of(users)),
+     "gnnrec_rank_resolve_f32");
+}
+
 void exp_rowsum(const Tensor& scores, Tensor& Z) {
   const OneDevice one_device_;
   dev(scores, "scores", at::kFloat);
@@ -2263,6 +2369,7 @@ int64_t csr_build_workspace_bytes(int64_t E, int64_t n_dst) {
   return (int64_t)gnnrec_csr_build_workspace_bytes(E, n_dst);
 }
 int64_t cos_denominator_parts(int64_t n_items) { return gnnrec_cos_denominator_parts(n_items); }
+double rank_eps(int64_t d) { return gnnrec_rank_eps(d); }
 int64_t csr_remove_edges_workspace_bytes(int64_t E, int64_t n_dst) {
   return (int64_t)gnnrec_csr_remove_edges_workspace_bytes(E, n_dst);
 }
@@ -2371,6 +2478,12 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor(b!) cand_items, Tensor(c!) cand_scores) -> ()");
   m.def("normalize_rows_f32(Tensor x, Tensor? row_map, Tensor(a!) out) -> ()");
   m.def("cos_denominators_f32(Tensor users, Tensor items, Tensor(a!) parts, Tensor(b!) Z) -> ()");
+  m.def("cos_scores_f32(Tensor users, Tensor items, Tensor(a!) out) -> ()");
+  m.def("rank_count_f32(Tensor users, Tensor items, Tensor thr, Tensor(a!) parts, "
+        "Tensor(b!) ahead, Tensor(c!) band_counts, Tensor(d!) band_items) -> ()");
+  m.def("rank_resolve_f32(Tensor users, Tensor items, Tensor thr, Tensor ahead, "
+        "Tensor band_counts, Tensor band_items, Tensor h_user, Tensor h_item, "
+        "Tensor? exclude_indptr, Tensor? exclude_indices, Tensor(a!) rank) -> ()");
   m.def("exp_rowsum_f32(Tensor scores, Tensor(a!) Z) -> ()");
   m.def("rating_rows_f32(Tensor(a!) scores, Tensor Z, Tensor p) -> ()");
   m.def("rating_thresholds_f32(Tensor tau, Tensor Z, Tensor pmax, Tensor(a!) thr) -> ()");
@@ -2467,6 +2580,7 @@ TORCH_LIBRARY(gnnrec, m) {
         &csr_from_keys_workspace_bytes);
   m.def("csr_build_workspace_bytes(int n_edges, int n_dst) -> int", &csr_build_workspace_bytes);
   m.def("cos_denominator_parts(int n_items) -> int", &cos_denominator_parts);
+  m.def("rank_eps(int d) -> float", &rank_eps);
   m.def("csr_remove_edges_workspace_bytes(int n_edges, int n_dst) -> int",
         &csr_remove_edges_workspace_bytes);
   m.def("csr_add_edges_workspace_bytes(int n_new, int n_dst) -> int",
@@ -2513,6 +2627,9 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("edge_mlp_dense_filter_rating_f32", &edge_mlp_dense_filter_rating); \
   m.impl("normalize_rows_f32", &normalize_rows_f32);     \
   m.impl("cos_denominators_f32", &cos_denominators);         \
+  m.impl("cos_scores_f32", &cos_scores);                     \
+  m.impl("rank_count_f32", &rank_count);                     \
+  m.impl("rank_resolve_f32", &rank_resolve);                 \
   m.impl("exp_rowsum_f32", &exp_rowsum);                     \
   m.impl("rating_rows_f32", &rating_rows_);                 \
   m.impl("rating_thresholds_f32", &rating_thresholds);       \

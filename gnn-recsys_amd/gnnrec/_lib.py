@@ -183,6 +183,11 @@ SIGNATURES = {
     "gnnrec_normalize_rows_f32": (_INT, [_P, _I64, _I64, _I64, _P, _P, _I64, _P]),
     "gnnrec_cos_denominator_parts": (_I64, [_I64]),
     "gnnrec_cos_denominators_f32": (_INT, [_P, _I64, _P, _I64, _I64, _P, _P, _P]),
+    "gnnrec_rank_eps": (_F64, [_I64]),
+    "gnnrec_cos_scores_f32": (_INT, [_P, _I64, _P, _I64, _I64, _P, _I64, _P]),
+    "gnnrec_rank_count_f32": (_INT, [_P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P, _I64, _P]),
+    "gnnrec_rank_resolve_f32": (_INT, [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _I64, _I64, _P,
+                                       _I64, _I64, _I64, _P, _P, _P, _P]),
     "gnnrec_fold_partials_f32": (_INT, [_P, _I64, _I64, _P, _P]),
     "gnnrec_edge_mlp_dense_denominators_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "gnnrec_edge_mlp_dense_store_rating_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P,

@@ -2098,6 +2098,68 @@ def cos_denominators(users: torch.Tensor, items: torch.Tensor) -> torch.Tensor:
     return Z
 
 
+# ---- f1f: exact rank among all items (csrc/rank.hip) ----
+def rank_eps(d: int) -> float:
+    """The bound on |a - sddmm_cos| for the fp32 MFMA dot a of two normalize_rows_f32 rows of
+    width d: (4 dpad + 32) 2^-24, dpad = d rounded up to a multiple of 8 (the library's value;
+    the derivation is in csrc/rank.hip)."""
+    return float(_T().rank_eps(int(d)))
+
+
+def cos_scores_f32(users: torch.Tensor, items: torch.Tensor) -> torch.Tensor:
+    """The fp32 MFMA dots of two normalize_rows_f32 tables, stored -> fp32 [n_users, n_items]:
+    the values rank_count compares and cos_denominators sums (for tests of the bound)."""
+    _dev(users, "users", torch.float32)
+    _dev(items, "items", torch.float32)
+    out = torch.empty((users.shape[0], items.shape[0]), dtype=torch.float32, device=users.device)
+    _T().cos_scores_f32(users, items, out)
+    return out
+
+
+def rank_count(users: torch.Tensor, items: torch.Tensor, thr: torch.Tensor,
+               band_counts: torch.Tensor, band_items: torch.Tensor) -> torch.Tensor:
+    """One fp32 MFMA pass over all items for the pair rows of `users` (normalize_rows_f32 of
+    each pair's user; `items` the item table): -> ahead int32 [R], the items whose dot exceeds
+    thr[r] + rank_eps; items within rank_eps of thr[r] join the row's list in band_items
+    [R, cap] (int32), band_counts [R] (int32, zeroed by the caller) counting past cap too."""
+    _dev(users, "users", torch.float32)
+    _dev(items, "items", torch.float32)
+    _dev(thr, "thr", torch.float32)
+    _dev(band_counts, "band_counts", torch.int32)
+    _dev(band_items, "band_items", torch.int32)
+    R = users.shape[0]
+    parts = torch.empty((denominator_parts(items.shape[0]), R), dtype=torch.int32,
+                        device=users.device)
+    ahead = torch.empty(R, dtype=torch.int32, device=users.device)
+    _T().rank_count_f32(users, items, thr, parts, ahead, band_counts, band_items)
+    return ahead
+
+
+def rank_resolve(users: torch.Tensor, items: torch.Tensor, thr: torch.Tensor,
+                 ahead: torch.Tensor, band_counts: torch.Tensor, band_items: torch.Tensor,
+                 h_user: torch.Tensor, h_item: torch.Tensor,
+                 exclude_indptr: Optional[torch.Tensor] = None,
+                 exclude_indices: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per pair (users[r], items[r]): rank = 1 + ahead + (band items exactly ahead) - (the
+    user's excluded items exactly ahead), 0 where the item is excluded, -1 where
+    band_counts[r] > cap -> int64 [P].  Scores are bitwise sddmm_cos's; the exclusion CSR
+    (over h_user's rows, int32) holds each id at most once per row, entries < 0 are skipped."""
+    _dev(users, "users", torch.int64)
+    _dev(items, "items", torch.int64)
+    _dev(thr, "thr", torch.float32)
+    _dev(ahead, "ahead", torch.int32)
+    _dev(band_counts, "band_counts", torch.int32)
+    _dev(band_items, "band_items", torch.int32)
+    _dev(h_user, "h_user", torch.float32)
+    _dev(h_item, "h_item", torch.float32)
+    if out is None:
+        out = torch.empty(users.numel(), dtype=torch.int64, device=users.device)
+    _T().rank_resolve_f32(users, items, thr, ahead, band_counts, band_items, h_user, h_item,
+                          exclude_indptr, exclude_indices, out)
+    return out
+
+
 def exp_rowsum(scores: torch.Tensor) -> torch.Tensor:
     """Z[r] = sum over the columns of expf(scores[r][c]), in a fixed order -> fp32 [n_rows]."""
     _dev(scores, "scores", torch.float32)

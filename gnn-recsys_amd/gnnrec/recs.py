@@ -17,6 +17,10 @@ reference's `--user_ids all`) on device tensors: the same ranking for the cosine
 for bit, from a bf16 MFMA prefilter and an fp32 rescoring of the few items it cannot rule
 out, with no score matrix.  With `head=` (a PredictingLayer) they rank by
 the MLP head's score instead, exactly and again without a score matrix.
+
+`rank_items` / `rank_for_graph` / `ranks_to_metrics` evaluate: the exact position of every
+held-out item in the cosine head's exhaustive ranking, from one fp32 MFMA pass over the items
+whose epilogue counts instead of storing.
 """
 from __future__ import annotations
 
@@ -535,6 +539,247 @@ def recommend_for_graph(g, h, k, user_ids=None, etype='bought-by', use_popularit
     if user_ids is not None:
         user_ids = torch.as_tensor(user_ids, dtype=torch.int64, device=dev)
     return recommend(h['user'], h['item'], k, user_ids, exclude, **kw)
+
+
+# ---- exact rank of held-out items among all items (csrc/rank.hip) -----------
+def rank_eps(d):
+    """|a - score| <= rank_eps(d) for the fp32 MFMA dot a of the two fp32-normalised rows
+    (ops.normalize_rows_f32) and score = ops.sddmm_cos: (4 dpad + 32) 2^-24 with dpad = d rounded
+    up to a multiple of 8 — 3.2e-5 at d = 128, 4.9e-4 at d = 2048.  Derived in csrc/rank.hip
+    and DESIGN.md §23 for rows whose norm lies in fp32's normal range and away from the 1e-12
+    guard (or is exactly zero), as REC_EPS is.  The library holds the value it compares with
+    (ops.rank_eps); this one is for callers."""
+    return (4.0 * ((int(d) + 7) // 8 * 8) + 32.0) * 2.0 ** -24
+
+
+def _distinct_exclusions(exclude, served, n_served, total, n_items):
+    """The exclusion rows of the served users only (served: bool [n_users], n_served of them,
+    their rows `total` entries long — both read with the id check), each row's ids ascending
+    and an id's repeats replaced by -1 (a multigraph's rows hold duplicates; an excluded item is
+    subtracted once) -> (indptr over ALL users, the other rows empty; indices int32).  One sort
+    of the served rows' entries, once per call; no host read."""
+    ex_ptr, ex_idx = exclude
+    dev, n_users = ex_idx.device, served.numel()
+    su = torch.sort(served.to(torch.int8), descending=True, stable=True).indices[:n_served]
+    deg = (ex_ptr[1:] - ex_ptr[:-1])[su]                       # su ascends: rows stay in order
+    ptr = torch.zeros(n_users + 1, dtype=torch.int64, device=dev)
+    ptr[1:] = torch.cumsum(torch.zeros(n_users, dtype=torch.int64, device=dev)
+                           .index_put_((su,), deg), 0)
+    if total == 0:      # every served row is empty: one unread entry, so the list has an address
+        return ptr, torch.full((1,), -1, dtype=torch.int32, device=dev)
+    row = torch.repeat_interleave(torch.arange(n_served, device=dev), deg, output_size=total)
+    src = ex_ptr[su][row] + (torch.arange(total, device=dev) - ptr[su][row])
+    ids = ex_idx[src].to(torch.int64)
+    ids = torch.where((ids < 0) | (ids > n_items), torch.full_like(ids, n_items), ids)
+    key = torch.sort(row * (int(n_items) + 1) + ids).values
+    ids = (key % (int(n_items) + 1)).to(torch.int32)
+    ids[1:][key[1:] == key[:-1]] = -1
+    ids[ids >= n_items] = -1                                    # ids past the table: no item
+    return ptr, ids.contiguous()
+
+
+def _ranks_exact(scorer, users, items, vals, exclude, rank, out_pos):
+    """The definition on exhaustive score rows, for the pairs (users, items) with threshold
+    vals, in chunks of 2^26 / n_items rows: ranks into rank[out_pos]."""
+    n_items = scorer.h_item.shape[0]
+    if users.numel() == 0:
+        return
+    ids = torch.arange(n_items, device=users.device)
+    step = max(1, (1 << 26) // n_items)
+    for c0 in range(0, users.numel(), step):
+        u = users[c0:c0 + step].contiguous()
+        g = items[c0:c0 + step].unsqueeze(1)
+        t = vals[c0:c0 + step].unsqueeze(1)
+        sc = scorer.score_rows(u)
+        ahead = (sc > t) | ((sc == t) & (ids < g))       # v = g itself: equal score, not below
+        r = None
+        if exclude is not None:
+            mark = torch.zeros_like(sc)
+            ops.mask_excluded(mark, u, exclude[0], exclude[1])
+            bought = mark == float('-inf')
+            ahead &= ~bought
+            r = bought.gather(1, g).squeeze(1)
+        out = 1 + ahead.sum(1)
+        if r is not None:
+            out = torch.where(r, torch.zeros_like(out), out)
+        rank[out_pos[c0:c0 + step]] = out
+
+
+def rank_items(h_user, h_item, users, items, exclude=None, *, batch_size=8192, cand_cap=1024,
+               return_stats=False):
+    """The exact position of item items[p] in recommend()'s exhaustive ranking for user
+    users[p], for every pair p, without a score matrix.
+
+        rank(u, g) = 1 + #{v not in exclude(u), v != g : s(u,v) > s(u,g) or
+                                                          (s(u,v) == s(u,g) and v < g)}
+        rank(u, g) = 0 where g is in exclude(u)   (the reference drops bought items)
+
+    with s = ops.sddmm_cos's value, the score recommend ranks by.  h_user [n_users, d], h_item
+    [n_items, d]: fp32 device tables.  users / items: int64 device tensors [P], repeats allowed;
+    an id out of range raises before any kernel of the pass is launched (one read: the four
+    id extremes and the size of the served users' exclusion rows).  exclude: recommend's
+    (indptr int64 [n_users + 1], indices int32); rows may be unsorted and hold an id more than once (a multigraph's bought-by CSR) — an excluded item
+    counts once: the served users' rows are sorted and their repeats struck once per call.
+    -> (rank int64 [P], vals fp32 [P]) [, stats]; vals are sddmm_cos's values for the pairs.
+
+    Per batch of `batch_size` pairs: the pairs' user rows and (once per call) the item table
+    normalised in fp32, then one fp32 MFMA pass over all items (ops.rank_count) whose epilogue
+    compares each dot a with the row's threshold t = vals[p]: a > t + eps is provably ahead and
+    counted, a < t - eps provably behind, anything between joins the row's band list (at most
+    cand_cap ids); ops.rank_resolve rescores the band and the user's excluded items with the
+    exact cosine and forms 1 + ahead + band_ahead - excluded_ahead.  eps = rank_eps(d) bounds
+    |a - s|.  Rows whose band holds more than cand_cap items (many items tied with the held-out
+    one) and the whole call when d % 4 != 0 or d > REC_MAX_D are redone from exhaustive score
+    rows in chunks of 2^26 / n_items rows, so the result never depends on the pass.  Apart
+    from the id check the host reads the device once (the band counts, after the last batch).
+    Non-finite embeddings are outside the contract, as for recommend.
+
+    stats (return_stats=True): band_mean, band_max (band items per row, counted past the cap),
+    overflow_rows, fast_path, eps, cand_cap."""
+    ops._dev(h_user, 'h_user', torch.float32)
+    ops._dev(h_item, 'h_item', torch.float32)
+    if h_user.dim() != 2 or h_item.dim() != 2 or h_user.shape[1] != h_item.shape[1]:
+        raise ValueError(f'h_user / h_item must be 2-D with one feature size, got '
+                         f'{tuple(h_user.shape)} and {tuple(h_item.shape)}')
+    batch_size, cand_cap = int(batch_size), int(cand_cap)
+    if batch_size < 1 or not 1 <= cand_cap <= REC_MAX_CAP:
+        raise ValueError(f'rank_items: batch_size must be >= 1 and cand_cap in '
+                         f'[1, {REC_MAX_CAP}]')
+    ops._dev(users, 'users', torch.int64)
+    ops._dev(items, 'items', torch.int64)
+    users, items = users.reshape(-1).contiguous(), items.reshape(-1).contiguous()
+    if users.numel() != items.numel():
+        raise ValueError(f'rank_items: {users.numel()} users for {items.numel()} items')
+    (n_users, d), n_items = h_user.shape, h_item.shape[0]
+    if exclude is not None:
+        ex_ptr, ex_idx = exclude
+        ops._dev(ex_ptr, 'exclude indptr', torch.int64)
+        ops._dev(ex_idx, 'exclude indices', torch.int32)
+        if ex_ptr.numel() != n_users + 1:
+            raise ValueError(f'exclude indptr must have n_users + 1 = {n_users + 1} entries, '
+                             f'got {ex_ptr.numel()}')
+        exclude = (ex_ptr.contiguous(), ex_idx.contiguous())
+    dev = h_item.device
+    h_user, h_item = h_user.contiguous(), h_item.contiguous()
+    P = users.numel()
+    fast = d % 4 == 0 and 4 <= d <= REC_MAX_D
+    stats = {'band_mean': 0.0, 'band_max': 0, 'overflow_rows': 0, 'fast_path': False,
+             'eps': rank_eps(d), 'cand_cap': cand_cap}
+    rank = torch.empty(P, dtype=torch.int64, device=dev)
+    if P == 0:
+        vals = torch.empty(0, dtype=torch.float32, device=dev)
+        return (rank, vals, stats) if return_stats else (rank, vals)
+    if n_users == 0 or n_items == 0:
+        raise ValueError(f'rank_items: ids out of range ({P} pairs for {n_users} users and '
+                         f'{n_items} items)')
+    check = [users.min(), users.max(), items.min(), items.max()]
+    if exclude is not None:     # what the exclusion sort needs to size itself: the same read
+        served = torch.zeros(n_users, dtype=torch.bool, device=dev)
+        served[users.clamp(0, n_users - 1)] = True
+        deg = exclude[0][1:] - exclude[0][:-1]
+        check += [served.sum(), (deg * served).sum()]
+    lo_u, hi_u, lo_i, hi_i, *sizes = torch.stack(check).tolist()
+    if lo_u < 0 or hi_u >= n_users or lo_i < 0 or hi_i >= n_items:
+        raise ValueError(f'rank_items: ids out of range (users in [{lo_u}, {hi_u}] of '
+                         f'{n_users}, items in [{lo_i}, {hi_i}] of {n_items})')
+    vals = ops.sddmm_cos(users, items, h_user, h_item)
+    scorer = _CosHead(h_user, h_item)
+    if not fast:
+        _ranks_exact(scorer, users, items, vals, exclude, rank, torch.arange(P, device=dev))
+        return (rank, vals, stats) if return_stats else (rank, vals)
+    stats['fast_path'] = True
+    items_f32 = ops.normalize_rows_f32(h_item)               # converted once per call
+    ex0, ex1 = (None, None) if exclude is None else \
+        _distinct_exclusions(exclude, served, *sizes, n_items)
+    band_counts = torch.zeros(P, dtype=torch.int32, device=dev)
+    band = torch.empty((min(batch_size, P), cand_cap), dtype=torch.int32, device=dev)
+    for b0 in range(0, P, batch_size):
+        ub = users[b0:b0 + batch_size]
+        cut = slice(b0, b0 + ub.numel())
+        bnd, t = band[:ub.numel()], vals[cut]
+        ahead = ops.rank_count(ops.normalize_rows_f32(h_user, ub), items_f32, t,
+                               band_counts[cut], bnd)
+        ops.rank_resolve(ub, items[cut], t, ahead, band_counts[cut], bnd, h_user, h_item, ex0,
+                         ex1, rank[cut])
+    cnt = band_counts.cpu().numpy()                          # the call's one readback
+    over = np.nonzero(cnt > cand_cap)[0]
+    if over.size:
+        pos = torch.from_numpy(over).to(dev)
+        _ranks_exact(scorer, users[pos], items[pos], vals[pos], exclude, rank, pos)
+    stats.update(band_mean=float(cnt.mean()), band_max=int(cnt.max()),
+                 overflow_rows=int(over.size))
+    return (rank, vals, stats) if return_stats else (rank, vals)
+
+
+def rank_for_graph(g, h, ground_truth, etype='bought-by', **kw):
+    """rank_items() for the held-out pairs ground_truth = (users, items) (as get_metrics_at_k
+    takes them) of a graph, the items each user has an `etype` edge from excluded: the lists
+    are the graph's own dst-major CSR of ('item', etype, 'user'), as in recommend_for_graph.
+    h: {'user': ..., 'item': ...} embeddings."""
+    dev = h['item'].device
+    users, items = ground_truth
+    users = torch.as_tensor(users, dtype=torch.int64, device=dev)
+    items = torch.as_tensor(items, dtype=torch.int64, device=dev)
+    ex_ptr, ex_idx = g.in_csr(etype)[:2]
+    return rank_items(h['user'], h['item'], users, items, (ex_ptr.to(dev), ex_idx.to(dev)), **kw)
+
+
+def ranks_to_metrics(rank, users, ks=(10,)):
+    """Full-ranking metrics from rank_items' ranks (0 = the item is excluded for the user) and
+    the pairs' users, every sum on the device in float64 -> dict:
+      unranked      pairs with rank 0
+      mrr           mean of 1 / rank over the ranked pairs
+      mean_rank     mean rank over the ranked pairs
+      recall@k      pairs with 1 <= rank <= k / all pairs (unranked included): for the same
+                    users' recommend(k) lists, recs_to_metrics_device's recall as the same ratio
+      hit_rate@k    users with at least one pair of rank in [1, k] / users among the pairs
+      ndcg@k        binary relevance over each user's distinct ranked items (a repeated pair
+                    counts once): DCG = sum of 1 / log2(1 + rank) over ranks <= k, IDCG over the
+                    first min(k, distinct ranked items) positions; the mean over the users with
+                    at least one ranked item
+    Ratios with an empty denominator are nan."""
+    ops._dev(rank, 'rank', torch.int64)
+    ops._dev(users, 'users', torch.int64)
+    rank, users = rank.reshape(-1), users.reshape(-1)
+    if rank.numel() != users.numel():
+        raise ValueError(f'ranks_to_metrics: {rank.numel()} ranks for {users.numel()} users')
+    ks = tuple(int(k) for k in ks)
+    if any(k < 1 for k in ks):
+        raise ValueError('ranks_to_metrics: every k must be >= 1')
+    dev, P = rank.device, rank.numel()
+    nan = float('nan')
+
+    def ratio(a, b):
+        return float(a) / float(b) if float(b) else nan
+
+    ranked = rank > 0
+    n_ranked = int(ranked.sum())
+    rr = rank[ranked].to(torch.float64)
+    out = {'unranked': P - n_ranked, 'mrr': ratio((1.0 / rr).sum(), n_ranked),
+           'mean_rank': ratio(rr.sum(), n_ranked)}
+    uniq, inv = torch.unique(users, return_inverse=True)
+    U = uniq.numel()
+    # each user's distinct ranked items: a rank names one item of a user's ranking
+    span = int(rank.max()) + 1 if P else 1
+    pair = torch.unique(inv[ranked] * span + rank[ranked])
+    pu, pr = pair // span, pair % span
+    n_dist = torch.bincount(pu, minlength=U)
+    kmax = max(ks) if ks else 1
+    disc = 1.0 / torch.log2(torch.arange(2, kmax + 2, device=dev, dtype=torch.float64))
+    ideal = torch.cat([disc.new_zeros(1), torch.cumsum(disc, 0)])   # ideal[j]: j positions
+    for k in ks:
+        hit = ranked & (rank <= k)
+        out[f'recall@{k}'] = ratio(hit.sum(), P)
+        per_user = torch.zeros(U, dtype=torch.int64, device=dev)
+        per_user.index_add_(0, inv, hit.to(torch.int64))
+        out[f'hit_rate@{k}'] = ratio((per_user > 0).sum(), U)
+        top = pr <= k
+        dcg = torch.zeros(U, dtype=torch.float64, device=dev)
+        dcg.index_add_(0, pu[top], disc[pr[top] - 1])
+        has = n_dist > 0
+        idcg = ideal[n_dist.clamp(max=k)]
+        out[f'ndcg@{k}'] = ratio((dcg[has] / idcg[has]).sum(), int(has.sum()))
+    return out
 
 
 # ---- cached lists kept current after a refresh (DESIGN.md §22) ---------------

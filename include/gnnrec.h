@@ -750,6 +750,45 @@ int gnnrec_topk_update_f32(const int64_t* rows, int64_t n_rows, int64_t* idx, fl
                            int64_t d, const int64_t* exclude_indptr,
                            const int32_t* exclude_indices, int32_t* redo, void* stream);
 
+/* ---- f1f: exact rank of held-out items among all items (csrc/rank.hip) ----
+ * s(u, v) = gnnrec_sddmm_cos_f32's value.  rank(u, g) = 1 + #{v not excluded for u, v != g :
+ * s(u,v) > s(u,g) or (s(u,v) == s(u,g) and v < g)}, 0 where g is excluded for u.  Rows of the
+ * kernels are pairs (u_r, g_r).
+ *
+ * eps(d) = (4 dpad + 32) 2^-24 (dpad = d rounded up to a multiple of 8) bounds |a - s| for the
+ * fp32 MFMA dot a of two gnnrec_normalize_rows_f32 rows (k ascending); 0 for d < 1. */
+double gnnrec_rank_eps(int64_t d);
+/* out[u][v] = a(u, v), the scores the count pass compares, stored (ldo >= n_items): for tests
+ * of the bound.  Tables as for gnnrec_cos_denominators_f32. */
+int gnnrec_cos_scores_f32(const float* users, int64_t n_users, const float* items,
+                          int64_t n_items, int64_t dpad, float* out, int64_t ldo, void* stream);
+/* One pass over all items for n_rows pairs: users [n_rows, dpad] the normalised user row of
+ * each pair, thr[r] = s(u_r, g_r).  ahead[r] (int32) = the items with a > thr[r] + eps (rounded
+ * up); an item with a >= thr[r] - eps (rounded down) that is not counted joins row r's band
+ * list: band_counts[r] (int32, zero before the call) takes one increment per such item and
+ * keeps counting past cap, ids are stored only into the row's cap slots of
+ * band_items[n_rows, cap] (int32, no fixed order).  parts: workspace of
+ * gnnrec_cos_denominator_parts(n_items) x n_rows int32.  The counts are integers: the result
+ * depends on neither the grid nor any order.  n_items = 0 gives ahead = 0.  cap <= 4096. */
+int gnnrec_rank_count_f32(const float* users, int64_t n_rows, const float* items,
+                          int64_t n_items, int64_t dpad, const float* thr, int32_t* parts,
+                          int32_t* ahead, int32_t* band_counts, int32_t* band_items, int64_t cap,
+                          void* stream);
+/* Per pair r = (users[r], items[r]) with band_counts[r] <= cap: its band items and the items of
+ * exclude_indices[exclude_indptr[u] .. exclude_indptr[u+1]) (a CSR over h_user's rows, int32,
+ * each id at most once per row, entries < 0 skipped; both pointers may be NULL) rescored with
+ * the fp32 cosine (bitwise gnnrec_sddmm_cos_f32; d % 4 == 0, 16-byte aligned rows):
+ * rank[r] = 1 + ahead[r] + (band items exactly ahead of items[r]) - (excluded items exactly
+ * ahead), or 0 where items[r] is excluded.  Rows with band_counts[r] > cap get rank -1: the
+ * caller redoes them.  Pairs with an id out of range are left unwritten. */
+int gnnrec_rank_resolve_f32(const int64_t* users, const int64_t* items, const float* thr,
+                            const int32_t* ahead, const int32_t* band_counts,
+                            const int32_t* band_items, int64_t cap, int64_t n_pairs,
+                            const float* h_user, int64_t ldu, int64_t n_users,
+                            const float* h_item, int64_t ldi, int64_t n_items, int64_t d,
+                            const int64_t* exclude_indptr, const int32_t* exclude_indices,
+                            int64_t* rank, void* stream);
+
 /* ---- f1d: popularity-weighted ratings (cosine head) ------------------------
  * R(u, v) = expf(score(u, v)) / Z_u + p_v, p_v = popularity[v] * weight, Z_u the sum of
  * expf(g(u, v)) over ALL items in a fixed order (csrc/rating.hpp, csrc/recommend_pop.hip,
