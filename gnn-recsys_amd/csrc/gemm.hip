@@ -14,16 +14,35 @@
 // block, reduced across the 32 lanes that hold it) and the cross-relation
 // accumulate into `out`.
 //
-// Tiling: 4 waves, each owning 32 rows × BN columns (BN/32 accumulators of
-// 16 regs).  K is staged through LDS 32 deep; the A and W tiles are stored
-// [row][k] with a 36-float row stride so the per-lane ds_read_b128 of 4
-// consecutive k is bank-conflict free (r·36 mod 64 covers 16 distinct 4-bank
-// slots).  Lane half h of the MFMA consumes k ∈ [16h, 16h+16) of the tile — a
-// permutation of the summation order inside the tile that keeps both operand
-// reads vectorised (fp32 sums stay within the 1e-4 parity tolerance).
+// Tiling, both kernels: 4 waves, each owning 32 rows × BN columns (BN/32
+// accumulators of 16 regs), BN = 32, 64, 128 or 256 by the output width (256
+// only where the row norm or the attention score needs the whole row in one
+// block).  K is staged through LDS in tiles; lane half h of the MFMA consumes
+// the h-th half of a tile's k, ascending, 4 at a time — a permutation of the
+// summation order inside the tile that keeps both operand reads vectorised
+// (fp32 sums stay within the 1e-4 parity tolerance).
+//
+//   gemm_f32_kernel      the general form: any alignment, any K.  Bounds-checked
+//                        loads staged through registers into 32-deep tiles stored
+//                        [row][k] with a 36-float row stride, so the per-lane
+//                        ds_read_b128 of 4 consecutive k is bank-conflict free
+//                        (r·36 mod 64 covers 16 distinct 4-bank slots).
+//   gemm_f32_dma_kernel  16-B aligned operands, K1 and K2 multiples of the tile
+//                        depth: global -> LDS DMA into unpadded, XOR-swizzled
+//                        tiles, S stages, (A1,W1) and (A2,W2) as one stream of
+//                        tiles.  Template over BN, the depth, S and a
+//                        compile-time epilogue FE (-1: the run-time one).
+//
+// Dispatch (launch_gemm), first match:
+//   BN 64 | 128, K % 16 == 0, aligned   -> dma<BN, 16, 3, FE>: FE = bias | relu << 1
+//                                          | l2norm << 2 in {0, 1, 2, 3, 6, 7} for a
+//                                          store-only, full-width (N == BN), aligned
+//                                          output without sigmoid / bias_nonempty;
+//                                          FE = -1 otherwise
+//   BN 32 | 256, K % 32 == 0, aligned   -> dma<BN, 32, 2, -1>
+//   anything else                       -> gemm_f32_kernel<BN>
 #include "common.hpp"
 #include <cmath>
-#include <cstdlib>
 
 namespace gnnrec {
 namespace {
@@ -316,7 +335,7 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmArgs& g, f32x16 (&a
 }
 
 // the general form (any alignment, any K): bounds-checked loads staged through registers;
-// aligned operands with K a multiple of BK take gemm_f32_glds_kernel / gemm_f32_glds16_kernel
+// aligned operands with K a multiple of the tile depth take gemm_f32_dma_kernel
 template <int BN>
 __global__ __launch_bounds__(256, GEMM_WAVES_PER_SIMD) void gemm_f32_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) float smem[smem_floats<BN>()];
@@ -430,14 +449,47 @@ __global__ __launch_bounds__(256, GEMM_WAVES_PER_SIMD) void gemm_f32_kernel(Gemm
   gemm_epilogue<BN>(g, acc, smem, m0, n0, wave, lane);
 }
 
-// ---- LDS-DMA variant (aligned operands, K1/K2 multiples of 32) -------------------
-// Tiles move global -> LDS with global_load_lds_dwordx4 (no staging registers), double
-// buffered: tile k+1 is in flight while the MFMAs consume tile k; a counted
-// `s_waitcnt vmcnt` + raw s_barrier publishes it (a __syncthreads() would drain the DMA).
-// The LDS image is lane-linear per wave-instruction (1 KiB = 8 rows x 128 B, unpadded), so
-// bank conflicts are removed on the SOURCE side: 16-B chunk j of tile row R is stored at
-// chunk j ^ ((R >> 1) & 7) of that row, which makes every 16-lane ds_read_b128 group of the
-// fragment reads hit 16 distinct 4-bank slots.
+// ---- the LDS-DMA kernel (aligned operands, K1/K2 multiples of the tile depth) -----------
+// Tiles move global -> LDS with global_load_lds_dwordx4 (no staging registers) through S
+// buffers: S-1 tiles are in flight while the MFMAs consume one; a counted `s_waitcnt vmcnt`
+// + raw s_barrier publishes the oldest (a __syncthreads() would drain the DMA).  Two depths:
+//   32 deep, S = 2: 32- and 256-column outputs.
+//   16 deep, S = 3: 64- and 128-column outputs.  Half the LDS per stage, so three blocks
+//     share a CU and one block's DMA prologue and store epilogue overlap the others' MFMAs,
+//     which is where a K = 128..256 GEMM loses its time; and a 16-deep tile is only 2048
+//     MFMA cycles per wave, shorter than an HBM round trip, so two tiles fly, not one (two
+//     stages: MFMA busy ~56 % at M = 1M, K = 256, N = 128).
+// The LDS image is lane-linear per wave-instruction (1 KiB = dma_rows rows of `depth` floats,
+// unpadded), so bank conflicts are removed on the SOURCE side: 16-B chunk j of tile row R is
+// stored at chunk j ^ ((R >> swz_shift) & swz_mask) of that row, which makes every 16-lane
+// ds_read_b128 group of the fragment reads hit 16 distinct 4-bank slots.
+constexpr int BK16 = 16;
+
+constexpr int dma_rows(int depth) { return 256 / depth; }           // rows per 1-KiB DMA: 8 | 16
+constexpr int swz_shift(int depth) { return depth == 32 ? 1 : 2; }
+constexpr int swz_mask(int depth) { return depth / 4 - 1; }         // chunks per row - 1: 7 | 3
+constexpr int k_steps(int depth) { return depth / 8; }              // 4-wide k-steps per lane half
+constexpr int dma_instrs(int rows, int depth) { return rows * depth / 1024; }  // per wave, per tile
+constexpr int tile_floats(int bn, int depth) { return (BM + bn) * depth; }
+// k-steps whose fragments are requested from LDS before their MFMAs start.  16 deep: both, so
+// the second step's LDS latency hides under the first step's MFMAs; 32 deep: one (four steps
+// of a 256-column tile do not fit the register file).  Scheduling only: the k order is the same.
+constexpr int frag_ahead(int depth) { return depth == 16 ? 2 : 1; }
+// waves per SIMD the kernel is built for (blocks per CU): what the stages' LDS allows, and
+// the 256-column accumulators' registers
+constexpr int dma_waves(int bn, int depth) { return depth == 16 ? 3 : (bn > 128 ? 1 : 2); }
+// The only arithmetic difference between the depths, kept so neither changes a result: the
+// mean's 1/deg (GNNREC_A2_DIV_DEG) is one division per row and a multiply per operand at 16
+// deep (64 IEEE divisions per lane per launch otherwise: half the VALU of the owned-row
+// GEMM), and a division per operand at 32 deep.
+constexpr bool deg_by_reciprocal(int depth) { return depth == 16; }
+
+template <int BN, int DEPTH, int S>
+constexpr int dma_smem_floats() {
+  return S * tile_floats(BN, DEPTH) > smem_floats<BN>() ? S * tile_floats(BN, DEPTH)
+                                                        : smem_floats<BN>();
+}
+
 // one 16-B-per-lane LDS-DMA (global_load_lds_dwordx4): lane L's bytes land at lds + 16 L.
 // (Kept out of lambdas and host-invisible: a device builtin inside a kernel-template
 // lambda makes hipcc drop the kernel's host launch stub.)
@@ -449,31 +501,35 @@ __device__ __forceinline__ void dma16(const float* src, float* lds) {
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt_barrier() {
-  static_assert(N >= 0 && N <= 15, "vmcnt immediate");
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)\n\ts_barrier" ::: "memory");
-  else static_assert(N == 0, "add the vmcnt immediate");
+  static_assert(N >= 0 && N <= 63, "vmcnt immediate");
+  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
-template <int BN>
-constexpr int glds_smem_floats() {
-  return 2 * (BM + BN) * BK > smem_floats<BN>() ? 2 * (BM + BN) * BK : smem_floats<BN>();
+// this wave's oldest tile landed while `ahead` (0..J) younger tiles of PER DMA instructions
+// each may still fly; then all waves are past it
+template <int PER, int J>
+__device__ __forceinline__ void wait_oldest_tile(int ahead) {
+  if constexpr (J == 0) {
+    wait_vmcnt_barrier<0>();
+  } else {
+    if (ahead >= J) wait_vmcnt_barrier<J * PER>();
+    else wait_oldest_tile<PER, J - 1>(ahead);
+  }
 }
 
-template <int BN>
-__global__ __launch_bounds__(256, (BN > 128 ? 1 : GEMM_WAVES_PER_SIMD)) void gemm_f32_glds_kernel(GemmArgs g) {
+template <int BN, int DEPTH, int S, int FE = -1>
+__global__ __launch_bounds__(256, dma_waves(BN, DEPTH)) void gemm_f32_dma_kernel(GemmArgs g) {
   constexpr int NT = BN / 32;
-  constexpr int AI = BM * BK * 4 / 1024 / 4;   // A-tile DMA instructions per wave (4)
-  constexpr int WI = BN * BK * 4 / 1024 / 4;   // W-tile DMA instructions per wave (BN/32)
-  constexpr int TILE = (BM + BN) * BK;         // floats per buffer
-  __shared__ __attribute__((aligned(16))) float smem[glds_smem_floats<BN>()];
+  constexpr int AI = dma_instrs(BM, DEPTH);   // A-tile DMA instructions per wave
+  constexpr int WI = dma_instrs(BN, DEPTH);   // W-tile DMA instructions per wave
+  constexpr int TILE = tile_floats(BN, DEPTH);
+  constexpr int ROWS = dma_rows(DEPTH), CPR = DEPTH / 4;  // rows per DMA, 16-B chunks per row
+  constexpr int KS = k_steps(DEPTH), FA = frag_ahead(DEPTH);
+  static_assert(DEPTH == 32 || DEPTH == 16, "tile depth");
+  static_assert(WI >= 1 && S >= 2 && KS % FA == 0, "tile shape");
+  static_assert(dma_waves(BN, DEPTH) * dma_smem_floats<BN, DEPTH, S>() * 4 <= 160 * 1024,
+                "the blocks the launch bounds ask for do not fit the CU's LDS");
+  __shared__ __attribute__((aligned(16))) float smem[dma_smem_floats<BN, DEPTH, S>()];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
@@ -481,7 +537,7 @@ __global__ __launch_bounds__(256, (BN > 128 ? 1 : GEMM_WAVES_PER_SIMD)) void gem
   const int h = lane >> 5;
   const int64_t m0 = (int64_t)blockIdx.x * BM;
   const int64_t n0 = (int64_t)blockIdx.y * BN;
-  const int sw = (r >> 1) & 7;                 // read-side swizzle of this lane's rows
+  const int sw = (r >> swz_shift(DEPTH)) & swz_mask(DEPTH);  // read-side swizzle of this lane's rows
 
   f32x16 acc[NT];
 #pragma unroll
@@ -489,186 +545,51 @@ __global__ __launch_bounds__(256, (BN > 128 ? 1 : GEMM_WAVES_PER_SIMD)) void gem
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc[t][v] = 0.f;
 
-  // DMA source rows of this lane (tile row R = instr*8 + lane/8, physical chunk lane%8)
-  int64_t a_row[AI], w_row[WI];
-  int a_chk[AI], w_chk[WI];
-#pragma unroll
-  for (int q = 0; q < AI; ++q) {
-    const int R = (wave * AI + q) * 8 + (lane >> 3);
-    const int64_t gm = m0 + R;
-    a_row[q] = gm < g.M ? gm : g.M - 1;
-    a_chk[q] = ((lane & 7) ^ ((R >> 1) & 7)) * 4;
-  }
-#pragma unroll
-  for (int q = 0; q < WI; ++q) {
-    const int R = (wave * WI + q) * 8 + (lane >> 3);
-    const int64_t gn = n0 + R;
-    w_row[q] = gn < g.N ? gn : g.N - 1;
-    w_chk[q] = ((lane & 7) ^ ((R >> 1) & 7)) * 4;
-  }
-  const int64_t my_row = m0 + wave * 32 + r;  // the A row this lane's fragments come from
-
-  // both operand pairs (A1,W1) then (A2,W2) as ONE stream of K tiles, so the DMA of the
-  // first A2 tile overlaps the last A1 tile's MFMAs (no pipeline restart between segments)
-  const int nk1 = (int)(g.K1 / BK), nk = nk1 + (int)(g.K2 / BK);
-  float rowdiv2 = 1.f;
-  bool rowzero2 = false;
-  if (g.K2 > 0 && g.a2_mode != GNNREC_A2_NONE) {
-    const int32_t dg = a2_degree(g, my_row < g.M ? my_row : g.M - 1);
-    if (g.a2_mode == GNNREC_A2_DIV_DEG) rowdiv2 = (float)(dg > 0 ? dg : 1);
-    else rowzero2 = dg == 0;
-  }
-  auto issue = [&](int kt, int buf) {
-    const bool s2 = kt >= nk1;
-    const float* A = s2 ? g.A2 : g.A1;
-    const float* W = s2 ? g.W2 : g.W1;
-    const int64_t K = s2 ? g.K2 : g.K1;
-    const int64_t lda = s2 ? g.lda2 : g.lda1;
-    const int64_t k0 = (int64_t)(s2 ? kt - nk1 : kt) * BK;
-    float* base = smem + buf * TILE;
-#pragma unroll
-    for (int q = 0; q < AI; ++q)
-      dma16(A + a_row[q] * lda + k0 + a_chk[q], base + (wave * AI + q) * 256);
-#pragma unroll
-    for (int q = 0; q < WI; ++q)
-      dma16(W + w_row[q] * K + k0 + w_chk[q], base + BM * BK + (wave * WI + q) * 256);
-  };
-  if (nk > 0) issue(0, 0);
-#pragma unroll 1
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) {
-      issue(kt + 1, buf ^ 1);
-      wait_vmcnt_barrier<AI + WI>();  // this wave's tile-kt DMA landed; all waves past it
-    } else {
-      wait_vmcnt_barrier<0>();
-    }
-    const bool s2 = kt >= nk1;
-    const bool divide = s2 && g.a2_mode == GNNREC_A2_DIV_DEG;
-    const bool zero = s2 && rowzero2;
-    const float* As = smem + buf * TILE + (wave * 32 + r) * BK;
-    const float* Ws = smem + buf * TILE + BM * BK + r * BK;
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
-      const int pc = ((h * 4 + s4) ^ sw) * 4;
-      f32x4 a = *reinterpret_cast<const f32x4*>(As + pc);
-      if (divide) a = a / rowdiv2;
-      else if (zero) a = f32x4{0.f, 0.f, 0.f, 0.f};
-      f32x4 b[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-        b[t] = *reinterpret_cast<const f32x4*>(Ws + t * 32 * BK + pc);
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[t][s], acc[t], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // buffer free for reuse
-  }
-  gemm_epilogue<BN>(g, acc, smem, m0, n0, wave, lane);
-}
-
-// ---- the same with 16-deep K tiles (short-K shapes) --------------------------------
-// Half the LDS of the 32-deep kernel (2 x 16 KB at BN=128), so three blocks share a CU
-// (three waves per SIMD): one block's DMA prologue and store epilogue overlap the others'
-// MFMAs, which is where a K=128..256 GEMM loses its time.  LDS image per wave-instruction:
-// 16 rows x 64 B; 16-B chunk j of tile row R sits at chunk j ^ ((R >> 2) & 3), so the 16
-// rows a 16-lane ds_read_b128 group touches map to 16 distinct 4-bank slots.
-constexpr int BK16 = 16;
-
-//
-// S stages (S−1 tiles in flight while one is consumed): a 16-deep tile is only 2048 MFMA
-// cycles per wave, shorter than an HBM round trip, so with two stages each block waited
-// on its DMA about as long as it computed (MFMA busy ≈56 % at M=1M, K=256, N=128).
-template <int BN, int S>
-constexpr int glds16_smem_floats() {
-  return S * (BM + BN) * BK16 > smem_floats<BN>() ? S * (BM + BN) * BK16 : smem_floats<BN>();
-}
-
-// waves per SIMD the S-stage kernel is built for: LDS allows 3 blocks per CU up to 3 stages
-template <int S>
-constexpr int glds16_waves() {
-  return S <= 3 ? 3 : 2;
-}
-
-template <int BN, int S, int FE = -1>
-__global__ __launch_bounds__(256, glds16_waves<S>()) void gemm_f32_glds16_kernel(GemmArgs g) {
-  constexpr int NT = BN / 32;
-  constexpr int AI = BM * BK16 * 4 / 1024 / 4;   // A-tile DMA instructions per wave (2)
-  constexpr int WI = BN * BK16 * 4 / 1024 / 4;   // W-tile DMA instructions per wave (BN/64)
-  constexpr int TILE = (BM + BN) * BK16;
-  static_assert(WI >= 1, "BN >= 64");
-  static_assert(S >= 2 && S <= 4, "stages");
-  __shared__ __attribute__((aligned(16))) float smem[glds16_smem_floats<BN, S>()];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int r = lane & 31;
-  const int h = lane >> 5;
-  const int64_t m0 = (int64_t)blockIdx.x * BM;
-  const int64_t n0 = (int64_t)blockIdx.y * BN;
-  const int sw = (r >> 2) & 3;
-
-  f32x16 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[t][v] = 0.f;
-
-  // DMA source rows of this lane (tile row R = instr*16 + lane/4, physical chunk lane%4)
-  int64_t a_row[AI], w_row[WI];
-  int a_chk[AI], w_chk[WI];
-#pragma unroll
-  for (int q = 0; q < AI; ++q) {
-    const int R = (wave * AI + q) * 16 + (lane >> 2);
-    const int64_t gm = m0 + R;
-    a_row[q] = gm < g.M ? gm : g.M - 1;
-    a_chk[q] = ((lane & 3) ^ ((R >> 2) & 3)) * 4;
-  }
-#pragma unroll
-  for (int q = 0; q < WI; ++q) {
-    const int R = (wave * WI + q) * 16 + (lane >> 2);
-    const int64_t gn = n0 + R;
-    w_row[q] = gn < g.N ? gn : g.N - 1;
-    w_chk[q] = ((lane & 3) ^ ((R >> 2) & 3)) * 4;
-  }
-  const int64_t my_row = m0 + wave * 32 + r;
-  // this lane's DMA source pointers of both operand pairs, formed once (a tile adds k0):
-  // the 64-bit row-offset products are not redone per tile
+  // this lane's DMA source pointers of both operand pairs, formed once (a tile adds k0): tile
+  // row R = instr * ROWS + lane / CPR (clamped to the last row / column), physical chunk
+  // lane % CPR
   const float* pa[2][AI];
   const float* pw[2][WI];
 #pragma unroll
   for (int q = 0; q < AI; ++q) {
-    pa[0][q] = g.A1 + a_row[q] * g.lda1 + a_chk[q];
-    pa[1][q] = g.K2 > 0 ? g.A2 + a_row[q] * g.lda2 + a_chk[q] : pa[0][q];
+    const int R = (wave * AI + q) * ROWS + lane / CPR;
+    const int64_t row = m0 + R < g.M ? m0 + R : g.M - 1;
+    const int chk = ((lane % CPR) ^ ((R >> swz_shift(DEPTH)) & swz_mask(DEPTH))) * 4;
+    pa[0][q] = g.A1 + row * g.lda1 + chk;
+    pa[1][q] = g.K2 > 0 ? g.A2 + row * g.lda2 + chk : pa[0][q];
   }
 #pragma unroll
   for (int q = 0; q < WI; ++q) {
-    pw[0][q] = g.W1 + w_row[q] * g.K1 + w_chk[q];
-    pw[1][q] = g.K2 > 0 ? g.W2 + w_row[q] * g.K2 + w_chk[q] : pw[0][q];
+    const int R = (wave * WI + q) * ROWS + lane / CPR;
+    const int64_t row = n0 + R < g.N ? n0 + R : g.N - 1;
+    const int chk = ((lane % CPR) ^ ((R >> swz_shift(DEPTH)) & swz_mask(DEPTH))) * 4;
+    pw[0][q] = g.W1 + row * g.K1 + chk;
+    pw[1][q] = g.K2 > 0 ? g.W2 + row * g.K2 + chk : pw[0][q];
   }
 
   // both operand pairs (A1,W1) then (A2,W2) as ONE stream of K tiles, so the DMA of the
   // first A2 tile overlaps the last A1 tile's MFMAs (no pipeline restart between segments)
-  const int nk1 = (int)(g.K1 / BK16), nk = nk1 + (int)(g.K2 / BK16);
-  // the mean's 1/deg (GNNREC_A2_DIV_DEG): one division per row, then a multiply per operand
-  // (64 IEEE divisions per lane per launch otherwise: half the VALU of the owned-row GEMM)
-  float rowinv2 = 1.f;
+  const int nk1 = (int)(g.K1 / DEPTH), nk = nk1 + (int)(g.K2 / DEPTH);
+  const int64_t my_row = m0 + wave * 32 + r;  // the A row this lane's fragments come from
+  float rowdeg2 = 1.f;  // the degree, or its reciprocal (deg_by_reciprocal)
   bool rowzero2 = false;
   if (g.K2 > 0 && g.a2_mode != GNNREC_A2_NONE) {
     const int32_t dg = a2_degree(g, my_row < g.M ? my_row : g.M - 1);
-    if (g.a2_mode == GNNREC_A2_DIV_DEG) rowinv2 = 1.f / (float)(dg > 0 ? dg : 1);
-    else rowzero2 = dg == 0;
+    if (g.a2_mode == GNNREC_A2_DIV_DEG) {
+      rowdeg2 = (float)(dg > 0 ? dg : 1);
+      if constexpr (deg_by_reciprocal(DEPTH)) rowdeg2 = 1.f / rowdeg2;
+    } else {
+      rowzero2 = dg == 0;
+    }
   }
   auto issue = [&](int kt, int buf) {
     const int s2 = kt >= nk1;
-    const int k0 = (s2 ? kt - nk1 : kt) * BK16;
+    const int k0 = (s2 ? kt - nk1 : kt) * DEPTH;
     float* base = smem + buf * TILE;
 #pragma unroll
     for (int q = 0; q < AI; ++q) dma16(pa[s2][q] + k0, base + (wave * AI + q) * 256);
 #pragma unroll
-    for (int q = 0; q < WI; ++q) dma16(pw[s2][q] + k0, base + BM * BK16 + (wave * WI + q) * 256);
+    for (int q = 0; q < WI; ++q) dma16(pw[s2][q] + k0, base + BM * DEPTH + (wave * WI + q) * 256);
   };
 #pragma unroll
   for (int j = 0; j < S - 1; ++j)
@@ -677,38 +598,38 @@ __global__ __launch_bounds__(256, glds16_waves<S>()) void gemm_f32_glds16_kernel
   for (int kt = 0; kt < nk; ++kt) {
     const int buf = kt % S;
     if (kt + S - 1 < nk) issue(kt + S - 1, (kt + S - 1) % S);
-    // this wave's tile-kt DMA landed (the younger tiles may still fly); all waves past it
-    const int ahead = nk - 1 - kt < S - 1 ? nk - 1 - kt : S - 1;
-    if (ahead >= 3) wait_vmcnt_barrier<3 * (AI + WI)>();
-    else if (ahead == 2) wait_vmcnt_barrier<2 * (AI + WI)>();
-    else if (ahead == 1) wait_vmcnt_barrier<AI + WI>();
-    else wait_vmcnt_barrier<0>();
+    wait_oldest_tile<AI + WI, S - 1>(nk - 1 - kt);
     const bool s2 = kt >= nk1;
     const bool divide = s2 && g.a2_mode == GNNREC_A2_DIV_DEG;
     const bool zero = s2 && rowzero2;
-    const float* As = smem + buf * TILE + (wave * 32 + r) * BK16;
-    const float* Ws = smem + buf * TILE + BM * BK16 + r * BK16;
-    // both halves' fragments are requested before the first MFMA: the second half's LDS
-    // latency hides under the first half's 16 MFMAs (one lgkmcnt wait per half, not a
-    // full drain before each)
-    f32x4 a[2], b[2][NT];
+    const float* As = smem + buf * TILE + (wave * 32 + r) * DEPTH;
+    const float* Ws = smem + buf * TILE + BM * DEPTH + r * DEPTH;
+    // lane half h consumes k in [h DEPTH/2, (h+1) DEPTH/2) of the tile, ascending, 4 at a time
 #pragma unroll
-    for (int s4 = 0; s4 < 2; ++s4) {
-      const int pc = ((h * 2 + s4) ^ sw) * 4;
-      a[s4] = *reinterpret_cast<const f32x4*>(As + pc);
+    for (int s0 = 0; s0 < KS; s0 += FA) {
+      f32x4 a[FA], b[FA][NT];
 #pragma unroll
-      for (int t = 0; t < NT; ++t)
-        b[s4][t] = *reinterpret_cast<const f32x4*>(Ws + t * 32 * BK16 + pc);
-    }
-#pragma unroll
-    for (int s4 = 0; s4 < 2; ++s4) {
-      if (divide) a[s4] = a[s4] * rowinv2;
-      else if (zero) a[s4] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
+      for (int j = 0; j < FA; ++j) {
+        const int pc = ((h * KS + s0 + j) ^ sw) * 4;
+        a[j] = *reinterpret_cast<const f32x4*>(As + pc);
 #pragma unroll
         for (int t = 0; t < NT; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s4][s], b[s4][t][s], acc[t], 0, 0, 0);
+          b[j][t] = *reinterpret_cast<const f32x4*>(Ws + t * 32 * DEPTH + pc);
+      }
+#pragma unroll
+      for (int j = 0; j < FA; ++j) {
+        if (divide) {
+          if constexpr (deg_by_reciprocal(DEPTH)) a[j] = a[j] * rowdeg2;
+          else a[j] = a[j] / rowdeg2;
+        } else if (zero) {
+          a[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int t = 0; t < NT; ++t)
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j][s], b[j][t][s], acc[t], 0, 0, 0);
+      }
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // buffer free for reuse
   }
@@ -735,22 +656,28 @@ int launch_gemm(const GemmArgs& g, hipStream_t s) {
       if (!sig && g.accum == GNNREC_ACC_STORE && !g.bias_ne && g.N == BN && g.vecO &&
           (g.row_norm == nullptr || (fe & 4))) {
         switch (fe) {
-          case 0: hipLaunchKernelGGL((gemm_f32_glds16_kernel<BN, 3, 0>), grid, dim3(256), 0, s, g); break;
-          case 1: hipLaunchKernelGGL((gemm_f32_glds16_kernel<BN, 3, 1>), grid, dim3(256), 0, s, g); break;
-          case 2: hipLaunchKernelGGL((gemm_f32_glds16_kernel<BN, 3, 2>), grid, dim3(256), 0, s, g); break;
-          case 3: hipLaunchKernelGGL((gemm_f32_glds16_kernel<BN, 3, 3>), grid, dim3(256), 0, s, g); break;
-          case 6: hipLaunchKernelGGL((gemm_f32_glds16_kernel<BN, 3, 6>), grid, dim3(256), 0, s, g); break;
-          case 7: hipLaunchKernelGGL((gemm_f32_glds16_kernel<BN, 3, 7>), grid, dim3(256), 0, s, g); break;
-          default: hipLaunchKernelGGL((gemm_f32_glds16_kernel<BN, 3>), grid, dim3(256), 0, s, g);
+          case 0: hipLaunchKernelGGL((gemm_f32_dma_kernel<BN, BK16, 3, 0>), grid, dim3(256), 0, s, g); break;
+          case 1: hipLaunchKernelGGL((gemm_f32_dma_kernel<BN, BK16, 3, 1>), grid, dim3(256), 0, s, g); break;
+          case 2: hipLaunchKernelGGL((gemm_f32_dma_kernel<BN, BK16, 3, 2>), grid, dim3(256), 0, s, g); break;
+          case 3: hipLaunchKernelGGL((gemm_f32_dma_kernel<BN, BK16, 3, 3>), grid, dim3(256), 0, s, g); break;
+          case 6: hipLaunchKernelGGL((gemm_f32_dma_kernel<BN, BK16, 3, 6>), grid, dim3(256), 0, s, g); break;
+          case 7: hipLaunchKernelGGL((gemm_f32_dma_kernel<BN, BK16, 3, 7>), grid, dim3(256), 0, s, g); break;
+          default: hipLaunchKernelGGL((gemm_f32_dma_kernel<BN, BK16, 3>), grid, dim3(256), 0, s, g);
         }
         return check_launch("gnnrec_gemm_f32");
       }
-      hipLaunchKernelGGL((gemm_f32_glds16_kernel<BN, 3>), grid, dim3(256), 0, s, g);
+      hipLaunchKernelGGL((gemm_f32_dma_kernel<BN, BK16, 3>), grid, dim3(256), 0, s, g);
+      return check_launch("gnnrec_gemm_f32");
+    }
+  } else {
+    // (at 64 and 128 columns `fast` implies `fast16`, which has returned: no 32-deep
+    // instantiation exists for them)
+    if (fast) {
+      hipLaunchKernelGGL((gemm_f32_dma_kernel<BN, BK, 2>), grid, dim3(256), 0, s, g);
       return check_launch("gnnrec_gemm_f32");
     }
   }
-  if (fast) hipLaunchKernelGGL((gemm_f32_glds_kernel<BN>), grid, dim3(256), 0, s, g);
-  else hipLaunchKernelGGL((gemm_f32_kernel<BN>), grid, dim3(256), 0, s, g);
+  hipLaunchKernelGGL((gemm_f32_kernel<BN>), grid, dim3(256), 0, s, g);
   return check_launch("gnnrec_gemm_f32");
 }
 

@@ -41,7 +41,6 @@ def main():
             res[f"M={M} K=128+128 N=128 relu l2"] = {"ms": ms2,
                                                      "TFs": 2 * M * K * 128 / ms2 / 1e9}
         del A
-    res["GNNREC_GEMM_BK16"] = os.environ.get("GNNREC_GEMM_BK16", "0")
     print(json.dumps(res, indent=1))
 
 

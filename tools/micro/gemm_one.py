@@ -1,6 +1,7 @@
 """One GEMM shape, a few launches (for rocprofv3 passes): M K N [reps] [form].
 
-form 'one' (default): out = A·Wᵀ, K deep.  form 'sage': the sharded pass's owned-row
+form 'one' (default): out = A·Wᵀ, K deep.  form 'norm': the same with ReLU and the row L2
+norm (N <= 256: the whole row in one block).  form 'sage': the sharded pass's owned-row
 projection — [h_self | partial / deg]·[W_self | W_neigh]ᵀ, K/2 + K/2 deep, ReLU, row L2 norm,
 the partial divided by the global in-degree in the operand load (GNNREC_A2_DIV_DEG)."""
 import os
@@ -28,7 +29,7 @@ else:
     W = torch.randn(N, K, device="cuda")
 
     def run():
-        ops.gemm(A, W)
+        ops.gemm(A, W, relu=form == "norm", l2norm=form == "norm")
 for _ in range(reps):
     run()
 torch.cuda.synchronize()
