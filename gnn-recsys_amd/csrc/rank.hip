@@ -57,6 +57,7 @@
 #include "common.hpp"
 #include "cos_score.hpp"
 #include "cos_tile.hpp"
+#include "fold_i32.hpp"
 #include <cmath>
 
 namespace gnnrec {
@@ -126,16 +127,6 @@ __global__ __launch_bounds__(256, 2) void rank_count_kernel(
       }
   });
   fold_tile_rows(cnt, reinterpret_cast<int*>(sA), B, ut, pi, part);
-}
-
-__global__ __launch_bounds__(256) void fold_partials_i32_kernel(const int* __restrict__ part,
-                                                                int64_t n_part, int64_t B,
-                                                                int* __restrict__ out) {
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r >= B) return;
-  int z = 0;
-  for (int64_t p = 0; p < n_part; ++p) z += part[p * B + r];
-  out[r] = z;
 }
 
 // The loop's scores themselves, stored: what the count pass compares (for the bound's test;
@@ -266,9 +257,7 @@ extern "C" int gnnrec_rank_count_f32(const float* users, int64_t n_rows, const f
     const int rc2 = check_launch(fn);
     if (rc2 != GNNREC_OK) return rc2;
   }
-  hipLaunchKernelGGL(fold_partials_i32_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256),
-                     0, as_stream(stream), parts, n_part, n_rows, ahead);
-  return check_launch(fn);
+  return launch_fold_partials_i32(fn, parts, n_part, n_rows, ahead, as_stream(stream));
 }
 
 extern "C" int gnnrec_rank_resolve_f32(const int64_t* users, const int64_t* items,

@@ -194,6 +194,13 @@ SIGNATURES = {
                                                       _P, _I64, _P]),
     "gnnrec_edge_mlp_dense_filter_rating_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P,
                                                        _P, _P, _P, _P, _I64, _P]),
+    # full-ranking evaluation for the MLP head (csrc/heads.hip)
+    "gnnrec_edge_mlp_dense_count_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
+                                               _P]),
+    "gnnrec_edge_mlp_dense_count_rating_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P,
+                                                      _P, _P, _P, _P, _P]),
+    "gnnrec_rank_resolve_mlp_f32": (_INT, [_P, _P, _P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P,
+                                           _P, _P, _P, _P, _P, _P, _P, _P]),
     "gnnrec_exp_rowsum_f32": (_INT, [_P, _I64, _I64, _I64, _P, _P]),
     "gnnrec_rating_rows_f32": (_INT, [_P, _I64, _I64, _I64, _P, _P, _P]),
     "gnnrec_rating_thresholds_f32": (_INT, [_P, _P, _P, _I64, _P, _P]),

@@ -20,7 +20,9 @@ the MLP head's score instead, exactly and again without a score matrix (DESIGN.m
 
 `rank_items` / `rank_for_graph` / `ranks_to_metrics` evaluate: the exact position of every
 held-out item in the cosine head's exhaustive ranking, from one fp32 MFMA pass over the items
-whose epilogue counts instead of storing.
+whose epilogue counts instead of storing; with `head=` the position in the MLP
+head's ranking (and with `popularity=` in its popularity-weighted one), from a counting
+epilogue on the dense MLP kernel that compares the final fp32 value.
 """
 from __future__ import annotations
 
@@ -578,9 +580,11 @@ def _distinct_exclusions(exclude, served, n_served, total, n_items):
     return ptr, ids.contiguous()
 
 
-def _ranks_exact(scorer, users, items, vals, exclude, rank, out_pos):
+def _ranks_exact(scorer, users, items, vals, exclude, rank, out_pos, Z=None):
     """The definition on exhaustive score rows, for the pairs (users, items) with threshold
-    vals, in chunks of 2^26 / n_items rows: ranks into rank[out_pos]."""
+    vals, in chunks of 2^26 / n_items rows: ranks into rank[out_pos].  Where the scorer has a
+    popularity (scorer.p) the rows become ratings first, as in _rows_exact (Z [len(users)];
+    None: summed from the rows), and vals are the pairs' ratings."""
     n_items = scorer.h_item.shape[0]
     if users.numel() == 0:
         return
@@ -591,6 +595,8 @@ def _ranks_exact(scorer, users, items, vals, exclude, rank, out_pos):
         g = items[c0:c0 + step].unsqueeze(1)
         t = vals[c0:c0 + step].unsqueeze(1)
         sc = scorer.score_rows(u)
+        if scorer.p is not None:
+            _to_ratings(sc, c0, (Z, scorer.p))
         ahead = (sc > t) | ((sc == t) & (ids < g))       # v = g itself: equal score, not below
         r = None
         if exclude is not None:
@@ -605,8 +611,33 @@ def _ranks_exact(scorer, users, items, vals, exclude, rank, out_pos):
         rank[out_pos[c0:c0 + step]] = out
 
 
+def _rank_items_mlp(scorer, users, items, exclude, batch_size, rank, vals):
+    """rank_items' loop for the MLP head (scorer: a _MlpHead whose Q is formed; exclude: the
+    distinct exclusion CSR or (None, None)).  Per batch of pairs: P of the pairs' users, the
+    pairs' own edge_mlp scores, one count pass over all items, one resolve launch.  No host
+    read: there is nothing to overflow."""
+    ex0, ex1 = exclude
+    n_users = scorer.h_user.shape[0]
+    for b0 in range(0, users.numel(), batch_size):
+        ub, gb = users[b0:b0 + batch_size], items[b0:b0 + batch_size]
+        cut = slice(b0, b0 + ub.numel())
+        P = scorer.P(ub)
+        s = ops.edge_mlp(torch.arange(ub.numel(), device=ub.device), gb, P, scorer.Q,
+                         *scorer.tail)
+        gid = gb.to(torch.int32)
+        if scorer.p is None:
+            Z = None
+            ahead = ops.edge_mlp_dense_count(P, scorer.Q, *scorer.tail, s, gid)
+        else:
+            Z = scorer.denominators(P)          # recommend's Z_u: the same bits in any batch
+            ahead = ops.edge_mlp_dense_count_rating(P, scorer.Q, *scorer.tail, Z, scorer.p, s,
+                                                    gid)
+        ops.rank_resolve_mlp(ub, gb, s, ahead, n_users, P, scorer.Q, *scorer.tail, ex0, ex1, Z,
+                             scorer.p, rank[cut], vals[cut])
+
+
 def rank_items(h_user, h_item, users, items, exclude=None, *, batch_size=8192, cand_cap=1024,
-               return_stats=False):
+               return_stats=False, head=None, popularity=None, weight_popularity=1.0):
     """The exact position of item items[p] in recommend()'s exhaustive ranking for user
     users[p], for every pair p, without a score matrix.
 
@@ -635,7 +666,36 @@ def rank_items(h_user, h_item, users, items, exclude=None, *, batch_size=8192, c
     Non-finite embeddings are outside the contract, as for recommend.
 
     stats (return_stats=True): band_mean, band_max (band items per row, counted past the cap),
-    overflow_rows, fast_path, eps, cand_cap."""
+    overflow_rows, fast_path, eps, cand_cap.
+
+    head: None ranks by the cosine, as above (that code path is untouched).  A PredictingLayer
+    (model.pred_fn.layer_nn, validated as for recommend) ranks by the MLP head's score instead:
+    s = ops.edge_mlp's value, vals those values bit for bit, the definition, the exclusions
+    and the repeats as above.  Q = h_item W1b^T is formed once per call; per
+    batch of pairs P = h_user[users] W1a^T + b1, the pairs' own scores (ops.edge_mlp), one pass
+    of the dense MLP kernel over all items whose epilogue counts the items exactly ahead
+    (ops.edge_mlp_dense_count), and ops.rank_resolve_mlp, which rescores the user's excluded
+    items with the same bits and subtracts those exactly ahead.  The pass compares the final
+    fp32 score — the very value the ranking is defined on — so there is no error bound, no
+    band, no overflow and no exhaustive redo: cand_cap is accepted and unused, the stats are
+    fast_path True, band_mean 0.0, band_max 0, overflow_rows 0, eps 0.0, and the id check is
+    the call's only host read.
+
+    popularity (with head=): a fp32 device tensor [n_items] or [n_items, 1], as for recommend.
+    The ranking is by R(u, v) = expf(s(u, v)) / Z_u + popularity[v] * weight_popularity, Z_u
+    recommend's denominator (the MLP head's denominator pass: the same bits for a user in any
+    batch), so a user's R values are the bits recommend(head=, popularity=) returns; vals are
+    the pairs' R.  The count pass and the resolve form every R, the pair's own included, with
+    the one function of csrc/rating.hpp.
+    popularity without head= raises NotImplementedError before anything is launched: the
+    cosine count pass classifies by |a - s| <= eps, and in rating space that needs a proved
+    band for expf(a) / Z_u + p_v against the rating of the exact cosine — the analogue of
+    REC_RATING_BAND for the fp32 MFMA dot — which has not been derived.  It is not
+    approximated."""
+    if popularity is not None and head is None:
+        raise NotImplementedError(
+            'rank_items: popularity= needs head= (the cosine head has no proved band in rating '
+            'space for its count pass; DESIGN.md §24)')
     ops._dev(h_user, 'h_user', torch.float32)
     ops._dev(h_item, 'h_item', torch.float32)
     if h_user.dim() != 2 or h_item.dim() != 2 or h_user.shape[1] != h_item.shape[1]:
@@ -664,7 +724,7 @@ def rank_items(h_user, h_item, users, items, exclude=None, *, batch_size=8192, c
     P = users.numel()
     fast = d % 4 == 0 and 4 <= d <= REC_MAX_D
     stats = {'band_mean': 0.0, 'band_max': 0, 'overflow_rows': 0, 'fast_path': False,
-             'eps': rank_eps(d), 'cand_cap': cand_cap}
+             'eps': rank_eps(d) if head is None else 0.0, 'cand_cap': cand_cap}
     rank = torch.empty(P, dtype=torch.int64, device=dev)
     if P == 0:
         vals = torch.empty(0, dtype=torch.float32, device=dev)
@@ -682,6 +742,16 @@ def rank_items(h_user, h_item, users, items, exclude=None, *, batch_size=8192, c
     if lo_u < 0 or hi_u >= n_users or lo_i < 0 or hi_i >= n_items:
         raise ValueError(f'rank_items: ids out of range (users in [{lo_u}, {hi_u}] of '
                          f'{n_users}, items in [{lo_i}, {hi_i}] of {n_items})')
+    if head is not None:    # the MLP head: exact in one pass, nothing to read back
+        p = None if popularity is None else \
+            _popularity_vector(popularity, weight_popularity, n_items)
+        scorer = _MlpHead(head, h_user, h_item, p)           # Q formed once per call
+        ex = (None, None) if exclude is None else \
+            _distinct_exclusions(exclude, served, *sizes, n_items)
+        vals = torch.empty(P, dtype=torch.float32, device=dev)
+        _rank_items_mlp(scorer, users, items, ex, batch_size, rank, vals)
+        stats['fast_path'] = True
+        return (rank, vals, stats) if return_stats else (rank, vals)
     vals = ops.sddmm_cos(users, items, h_user, h_item)
     scorer = _CosHead(h_user, h_item)
     if not fast:
@@ -711,12 +781,27 @@ def rank_items(h_user, h_item, users, items, exclude=None, *, batch_size=8192, c
     return (rank, vals, stats) if return_stats else (rank, vals)
 
 
-def rank_for_graph(g, h, ground_truth, etype='bought-by', **kw):
+def rank_for_graph(g, h, ground_truth, etype='bought-by', use_popularity=False,
+                   weight_popularity=1, **kw):
     """rank_items() for the held-out pairs ground_truth = (users, items) (as get_metrics_at_k
     takes them) of a graph, the items each user has an `etype` edge from excluded: the lists
     are the graph's own dst-major CSR of ('item', etype, 'user'), as in recommend_for_graph.
-    h: {'user': ..., 'item': ...} embeddings."""
+    h: {'user': ..., 'item': ...} embeddings.  head= (in kw) ranks by the MLP head;
+    use_popularity ranks by softmax + weight_popularity * g.ndata['popularity']['item']
+    (rank_items' popularity=: the MLP head only)."""
     dev = h['item'].device
+    if use_popularity:
+        if kw.get('head') is None:      # rank_items' refusal, before the graph is touched
+            raise NotImplementedError(
+                'rank_for_graph: use_popularity=True needs head= (rank_items: popularity= needs '
+                'head=; DESIGN.md §24)')
+        try:
+            pop = g.ndata['popularity']['item']
+        except (KeyError, AttributeError, TypeError) as exc:
+            raise KeyError("rank_for_graph(use_popularity=True): the graph has no "
+                           "ndata['popularity']['item']") from exc
+        kw = dict(kw, popularity=torch.as_tensor(pop).to(dev).float(),
+                  weight_popularity=weight_popularity)
     users, items = ground_truth
     users = torch.as_tensor(users, dtype=torch.int64, device=dev)
     items = torch.as_tensor(items, dtype=torch.int64, device=dev)

@@ -834,6 +834,41 @@ int gnnrec_edge_mlp_dense_filter_rating_f32(const float* P, int64_t n_users, con
                                             const float* p_col, const float* tau, int32_t* counts,
                                             int32_t* cand_items, float* cand_scores, int64_t cap,
                                             void* stream);
+/* ---- f1f for the MLP head: exact rank among all items (csrc/heads.hip) ----
+ * Rows are pairs (u_r, g_r): P [n_rows, 128] holds the P row of u_r, gid[r] = g_r (int32),
+ * thr[r] = gnnrec_edge_mlp_f32's score of the pair.  One pass over all items with the dense
+ * kernel's arithmetic: ahead[r] (int32) = #{v != gid[r] : score(r, v) > thr[r] or (score(r, v)
+ * == thr[r] and v < gid[r])}.  The compared value is the final fp32 score: no band, no
+ * candidate list.  parts: workspace [gnnrec_cos_denominator_parts(n_items), n_rows] int32.
+ * n_rows = 0 does nothing; n_items = 0 launches nothing and writes ahead = 0. */
+int gnnrec_edge_mlp_dense_count_f32(const float* P, int64_t n_rows, const float* Q,
+                                    int64_t n_items, const float* W2, const float* b2,
+                                    const float* w3, const float* b3, const float* thr,
+                                    const int32_t* gid, int32_t* parts, int32_t* ahead,
+                                    void* stream);
+/* The same count on R(r, v) = expf(score) / Z[r] + p_col[v] against the row's own
+ * R = expf(s[r]) / Z[r] + p_col[gid[r]], both formed in the kernel by one inline function
+ * (s[r]: the pair's raw score, Z [n_rows], p_col [n_items]). */
+int gnnrec_edge_mlp_dense_count_rating_f32(const float* P, int64_t n_rows, const float* Q,
+                                           int64_t n_items, const float* W2, const float* b2,
+                                           const float* w3, const float* b3, const float* Z,
+                                           const float* p_col, const float* s, const int32_t* gid,
+                                           int32_t* parts, int32_t* ahead, void* stream);
+/* Per pair r = (users[r], items[r]), P [n_pairs, 128] the P row of users[r] and s[r] its raw
+ * score: the items of exclude_indices[exclude_indptr[u] .. exclude_indptr[u+1]) (a CSR over the
+ * n_users users, int32, each id at most once per row, entries < 0 or >= n_items skipped; both
+ * pointers may be NULL) are scored with gnnrec_edge_mlp_f32's bits (Z [n_pairs] and p_col given:
+ * turned into R) and those exactly ahead of items[r] counted:
+ * rank[r] = 1 + ahead[r] - (excluded items exactly ahead), or 0 where items[r] is excluded.
+ * vals[r] = s[r], or the pair's R.  Z and p_col come together or are both NULL.  Pairs with an
+ * id out of range are left unwritten. */
+int gnnrec_rank_resolve_mlp_f32(const int64_t* users, const int64_t* items, const float* s,
+                                const int32_t* ahead, int64_t n_pairs, int64_t n_users,
+                                const float* P, const float* Q, int64_t n_items, const float* W2,
+                                const float* b2, const float* w3, const float* b3, const float* Z,
+                                const float* p_col, const int64_t* exclude_indptr,
+                                const int32_t* exclude_indices, int64_t* rank, float* vals,
+                                void* stream);
 /* Z[r] = sum over the columns of expf(scores[r][c]), in a fixed order (one block per row). */
 int gnnrec_exp_rowsum_f32(const float* scores, int64_t ld, int64_t n_rows, int64_t n_cols,
                           float* Z, void* stream);
