@@ -652,6 +652,15 @@ static void fused_entries() {
                                    nullptr, nullptr, a.n_dst, a.d, a.reduce, a.epilogue, a.mode,
                                    0.f, a.attn_vec, a.attn_state, a.out, a.ld, nullptr);
   };
+  // the VALU entry that saves the rows' aggregates (a load launch takes no source table:
+  // its refusals are below)
+  const Call single_agg = [](const FusedArgs& a) {
+    return gnnrec_spmm_project_agg_f32(a.indptr, nullptr, nullptr, a.X, a.ld, a.H, a.ld, a.W, a.W,
+                                       nullptr, nullptr, a.n_dst, a.d, a.reduce, a.epilogue,
+                                       a.mode, 0.f, a.attn_vec, a.attn_state, a.out, a.ld,
+                                       reinterpret_cast<float*>(16), 128, GNNREC_AGG_SAVE,
+                                       nullptr);
+  };
   const Call single_mfma = [](const FusedArgs& a) {
     return gnnrec_spmm_project_mfma_f32(a.indptr, nullptr, nullptr, a.X, a.ld, a.H, a.ld, a.W,
                                         a.W, nullptr, nullptr, a.n_dst, a.d, a.reduce, a.epilogue,
@@ -676,6 +685,7 @@ static void fused_entries() {
     bool two;  // two relations: `mode` is a combine, attention takes attn_vec alone
   };
   const Entry entries[] = {{"gnnrec_spmm_project_f32", single_valu, false},
+                           {"gnnrec_spmm_project_agg_f32", single_agg, false},
                            {"gnnrec_spmm_project_mfma_f32", single_mfma, false},
                            {"gnnrec_spmm_project2_f32", project2, true},
                            {"gnnrec_spmm_pair_f32", pair, true}};
@@ -740,6 +750,34 @@ static void fused_entries() {
             err_has("gnnrec_spmm_project_f32: W_neighT = NULL (pre-projected source rows) is "
                     "gnnrec_spmm_project_mfma_f32's form"),
         "valu entry without W_neighT");
+  // the aggregate modes: agg present, 16-B aligned, rows of at least d floats; a load
+  // launch takes no source table (X = NULL passes its pointer check, and the launch is
+  // refused for the next wrong argument instead)
+  auto agg_call = [&](const float* X, float* agg, int64_t lda, int mode) {
+    return gnnrec_spmm_project_agg_f32(l16, nullptr, nullptr, X, 128, f16, 128, f16, f16, nullptr,
+                                       nullptr, 10, 128, GNNREC_REDUCE_MEAN, 0, GNNREC_ACC_STORE,
+                                       0.f, nullptr, nullptr, f16, 128, agg, lda, mode, nullptr);
+  };
+  CHECK(agg_call(f16, f16, 128, 3) == GNNREC_EINVAL &&
+            err_has("gnnrec_spmm_project_agg_f32: unknown aggregate mode 3"),
+        "agg unknown mode");
+  CHECK(agg_call(f16, nullptr, 128, GNNREC_AGG_SAVE) == GNNREC_EINVAL &&
+            err_has("gnnrec_spmm_project_agg_f32: the aggregate mode needs agg"),
+        "agg save without agg");
+  CHECK(agg_call(nullptr, nullptr, 128, GNNREC_AGG_LOAD) == GNNREC_EINVAL &&
+            err_has("gnnrec_spmm_project_agg_f32: the aggregate mode needs agg"),
+        "agg load without agg (and without X: not a null-pointer refusal)");
+  CHECK(agg_call(nullptr, f16, 128, GNNREC_AGG_SAVE) == GNNREC_EINVAL && err_has("null pointer"),
+        "agg save without X");
+  CHECK(agg_call(f16, f24, 128, GNNREC_AGG_SAVE) == GNNREC_EINVAL &&
+            err_has("agg needs 16-B aligned rows of lda >= 128 floats"),
+        "agg misaligned");
+  CHECK(agg_call(nullptr, f16, 64, GNNREC_AGG_LOAD) == GNNREC_EINVAL &&
+            err_has("agg needs 16-B aligned rows of lda >= 128 floats"),
+        "agg lda below the row width");
+  CHECK(agg_call(f16, f16, 130, GNNREC_AGG_SAVE) == GNNREC_EINVAL &&
+            err_has("agg needs 16-B aligned rows of lda >= 128 floats"),
+        "agg lda not a multiple of 4");
   CHECK(gnnrec_spmm_project_mfma_f32(l16, nullptr, nullptr, f16, 128, f16, 128, f16, nullptr,
                                      nullptr, nullptr, 10, 128, GNNREC_REDUCE_MAX, 0,
                                      GNNREC_ACC_STORE, 0.f, nullptr, nullptr, f16, 128, nullptr) ==

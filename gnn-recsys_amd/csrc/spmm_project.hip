@@ -105,7 +105,19 @@ __device__ __forceinline__ void epilogue_row(const EpiArgs& e, int64_t row, bool
   st_stream2(reinterpret_cast<float*>(p), y0, y1);
 }
 
-template <int REDUCE, bool WEIGHTED, int UNROLL>
+// AGG: what the launch does with a row's finalized aggregate besides projecting it.
+//   kAggNone  nothing more (gnnrec_spmm_project_f32)
+//   kAggSave  lane group 0 also streams the fragment it parks in its slot to agg[row]
+//   kAggLoad  the fragment is read from agg[row] instead of gathered: indices, X and ew are
+//             not touched (they may be null), indptr only for the row's bias_nonempty term
+// The aggregate depends on the CSR and the source table alone, never on a weight, so a caller
+// whose source table stays fixed from launch to launch (a first layer over raw features) saves
+// it once and loads it afterwards.  The slots hold the same bits either way and the matvec,
+// bias and epilogue below are one body: a load launch's output is bit-identical to the
+// gathering launch's on the same aggregate.
+constexpr int kAggNone = GNNREC_AGG_NONE, kAggSave = GNNREC_AGG_SAVE, kAggLoad = GNNREC_AGG_LOAD;
+
+template <int REDUCE, bool WEIGHTED, int UNROLL, int AGG = kAggNone>
 __global__ __launch_bounds__(kPWaves * 64) void spmm_project_kernel(
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
     const float* __restrict__ ew, const float* __restrict__ X, int64_t ldx,
@@ -113,7 +125,8 @@ __global__ __launch_bounds__(kPWaves * 64) void spmm_project_kernel(
     const float* __restrict__ WnT, const float* __restrict__ bias,
     const float* __restrict__ bias_ne, int64_t n_dst, int epilogue, int accum, float out_div,
     const float* __restrict__ attn_vec, float* __restrict__ attn_state,
-    float* __restrict__ out, int64_t ldo, unsigned* rq, int rq_ch) {
+    float* __restrict__ out, int64_t ldo, unsigned* rq, int rq_ch, float* __restrict__ agg,
+    int64_t lda) {
   __shared__ float Ws[kPD * kPD];
   __shared__ float Wn[kPD * kPD];
   __shared__ float slots[kPWaves][kPRows][2][kPD];
@@ -154,14 +167,25 @@ __global__ __launch_bounds__(kPWaves * 64) void spmm_project_kernel(
 #pragma unroll
     for (int r = 0; r < kPRows; ++r) {
       const bool valid = r < nv;  // uniform per wave
-      pidx[r] = valid && lane < rb[r + 1] - rb[r] ? ld_stream(indices + rb[r] + lane) : 0;
       hsr[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (valid && grp == 1) hsr[r] = ld_stream4(H + (row0 + r) * ldh + col);
+      if constexpr (AGG == kAggLoad) {  // the saved aggregate rides with the self row
+        pidx[r] = 0;
+        if (valid) hsr[r] = ld_stream4((grp == 0 ? agg + (row0 + r) * lda
+                                                 : H + (row0 + r) * ldh) + col);
+      } else {
+        pidx[r] = valid && lane < rb[r + 1] - rb[r] ? ld_stream(indices + rb[r] + lane) : 0;
+        if (valid && grp == 1) hsr[r] = ld_stream4(H + (row0 + r) * ldh + col);
+      }
     }
 #pragma unroll
     for (int r = 0; r < kPRows; ++r) {
       const bool valid = r < nv;  // uniform per wave
       const float4 hs = hsr[r];
+      if constexpr (AGG == kAggLoad) {  // group 0: the aggregate, group 1: the self row
+        nonempty[r] = rb[r + 1] - rb[r] > 0;
+        *reinterpret_cast<float4*>(&slots[wave][r][grp][col]) = hs;
+        continue;
+      }
       Frag<VEC> acc;
 #pragma unroll
       for (int v = 0; v < VEC; ++v) acc.v[v] = init;
@@ -175,11 +199,14 @@ __global__ __launch_bounds__(kPWaves * 64) void spmm_project_kernel(
       combine_groups<LPR, VEC, REDUCE>(acc);
       finalize<VEC, REDUCE>(acc, deg, 0);
       nonempty[r] = deg > 0;
-      if (grp == 0)
+      if (grp == 0) {
         *reinterpret_cast<float4*>(&slots[wave][r][0][col]) =
             make_float4(acc.v[0], acc.v[1], acc.v[2], acc.v[3]);
-      else
+        if constexpr (AGG == kAggSave)
+          if (valid) store_frag<VEC>(agg + (row0 + r) * lda + col, acc);
+      } else {
         *reinterpret_cast<float4*>(&slots[wave][r][1][col]) = hs;
+      }
     }
     // the slots are written and read by this wave only: LDS is in order per wave, the
     // clobber keeps the compiler from hoisting the reads above the writes
@@ -395,24 +422,36 @@ __global__ __launch_bounds__(kMWaves * 64, 4) void spmm_project_mfma_kernel(
 
 using namespace gnnrec;
 
-extern "C" int gnnrec_spmm_project_f32(const int64_t* indptr, const int32_t* indices,
-                                       const float* ew, const float* X, int64_t ldx,
-                                       const float* H, int64_t ldh, const float* W_selfT,
-                                       const float* W_neighT, const float* bias,
-                                       const float* bias_nonempty, int64_t n_dst, int64_t d,
-                                       int reduce, int epilogue, int accum, float out_div,
-                                       const float* attn_vec, float* attn_state, float* out,
-                                       int64_t ldo, void* stream) {
-  const char* const name = "gnnrec_spmm_project_f32";
+// The VALU kernel's launch, shared by its two entries (`name` keeps each one's messages).
+static int launch_spmm_project(const char* name, const int64_t* indptr, const int32_t* indices,
+                               const float* ew, const float* X, int64_t ldx, const float* H,
+                               int64_t ldh, const float* W_selfT, const float* W_neighT,
+                               const float* bias, const float* bias_nonempty, int64_t n_dst,
+                               int64_t d, int reduce, int epilogue, int accum, float out_div,
+                               const float* attn_vec, float* attn_state, float* out, int64_t ldo,
+                               float* agg, int64_t lda, int agg_mode, void* stream) {
   GNNREC_REQUIRE(reduce == GNNREC_REDUCE_SUM || reduce == GNNREC_REDUCE_MEAN ||
                      reduce == GNNREC_REDUCE_MAX,
-                 "gnnrec_spmm_project_f32: unknown reduce %d", reduce);
-  const int st = fused_check(name, d, epilogue, false, accum, attn_vec, attn_state, n_dst, 'X',
-                             {indptr, X, H, W_selfT}, {X, H, W_selfT, W_neighT}, {ldx, ldh}, out,
-                             ldo);
+                 "%s: unknown reduce %d", name, reduce);
+  GNNREC_REQUIRE(agg_mode == GNNREC_AGG_NONE || agg_mode == GNNREC_AGG_SAVE ||
+                     agg_mode == GNNREC_AGG_LOAD,
+                 "%s: unknown aggregate mode %d", name, agg_mode);
+  // a load launch reads neither the source table nor the edges
+  const bool load = agg_mode == GNNREC_AGG_LOAD;
+  const int st = load ? fused_check(name, d, epilogue, false, accum, attn_vec, attn_state, n_dst,
+                                    'X', {indptr, H, W_selfT}, {H, W_selfT, W_neighT}, {ldh}, out,
+                                    ldo)
+                      : fused_check(name, d, epilogue, false, accum, attn_vec, attn_state, n_dst,
+                                    'X', {indptr, X, H, W_selfT}, {X, H, W_selfT, W_neighT},
+                                    {ldx, ldh}, out, ldo);
   if (st != GNNREC_OK || n_dst == 0) return st;
-  GNNREC_REQUIRE(W_neighT, "gnnrec_spmm_project_f32: W_neighT = NULL (pre-projected source "
-                           "rows) is gnnrec_spmm_project_mfma_f32's form");
+  GNNREC_REQUIRE(W_neighT, "%s: W_neighT = NULL (pre-projected source "
+                           "rows) is gnnrec_spmm_project_mfma_f32's form", name);
+  if (agg_mode != GNNREC_AGG_NONE) {
+    GNNREC_REQUIRE(agg, "%s: the aggregate mode needs agg", name);
+    GNNREC_REQUIRE(aligned16(agg) && lda >= kPD && lda % 4 == 0,
+                   "%s: agg needs 16-B aligned rows of lda >= %d floats", name, kPD);
+  }
   // one persistent block per CU; queued rows when every wave has several tickets of work
   const int64_t per_block = (int64_t)kPWaves * kPRows;
   const int64_t blocks = persistent_blocks((n_dst + per_block - 1) / per_block, 1);
@@ -421,16 +460,57 @@ extern "C" int gnnrec_spmm_project_f32(const int64_t* indptr, const int32_t* ind
   int ticket = -1;
   unsigned* rq = rowq_slot_for(n_dst, blocks * kPWaves, rq_ch, s, &ticket);
   const dim3 grid((unsigned)blocks), block(kPWaves * 64);
-  dispatch_bool(ew != nullptr, [&](auto w) {
-    dispatch_reduce(reduce, [&](auto r) {
-      hipLaunchKernelGGL((spmm_project_kernel<decltype(r)::value, decltype(w)::value, kSppU>),
-                         grid, block, 0, s, indptr, indices, ew, X, ldx, H, ldh, W_selfT, W_neighT,
-                         bias, bias_nonempty, n_dst, epilogue, accum, out_div, attn_vec,
-                         attn_state, out, ldo, rq, rq_ch);
+  auto launch = [&](auto r, auto w, auto m) {
+    hipLaunchKernelGGL(
+        (spmm_project_kernel<decltype(r)::value, decltype(w)::value, kSppU, decltype(m)::value>),
+        grid, block, 0, s, indptr, indices, ew, X, ldx, H, ldh, W_selfT, W_neighT, bias,
+        bias_nonempty, n_dst, epilogue, accum, out_div, attn_vec, attn_state, out, ldo, rq, rq_ch,
+        agg, lda);
+  };
+  using Sum = std::integral_constant<int, GNNREC_REDUCE_SUM>;
+  if (load) {  // nothing is reduced: one instantiation
+    launch(Sum{}, std::false_type{}, std::integral_constant<int, kAggLoad>{});
+  } else {
+    dispatch_bool(ew != nullptr, [&](auto w) {
+      dispatch_reduce(reduce, [&](auto r) {
+        if (agg_mode == GNNREC_AGG_SAVE)
+          launch(r, w, std::integral_constant<int, kAggSave>{});
+        else
+          launch(r, w, std::integral_constant<int, kAggNone>{});
+      });
     });
-  });
+  }
   rowq_launched(ticket, s);
   return check_launch(name);
+}
+
+extern "C" int gnnrec_spmm_project_f32(const int64_t* indptr, const int32_t* indices,
+                                       const float* ew, const float* X, int64_t ldx,
+                                       const float* H, int64_t ldh, const float* W_selfT,
+                                       const float* W_neighT, const float* bias,
+                                       const float* bias_nonempty, int64_t n_dst, int64_t d,
+                                       int reduce, int epilogue, int accum, float out_div,
+                                       const float* attn_vec, float* attn_state, float* out,
+                                       int64_t ldo, void* stream) {
+  return launch_spmm_project("gnnrec_spmm_project_f32", indptr, indices, ew, X, ldx, H, ldh,
+                             W_selfT, W_neighT, bias, bias_nonempty, n_dst, d, reduce, epilogue,
+                             accum, out_div, attn_vec, attn_state, out, ldo, nullptr, 0,
+                             GNNREC_AGG_NONE, stream);
+}
+
+extern "C" int gnnrec_spmm_project_agg_f32(const int64_t* indptr, const int32_t* indices,
+                                           const float* ew, const float* X, int64_t ldx,
+                                           const float* H, int64_t ldh, const float* W_selfT,
+                                           const float* W_neighT, const float* bias,
+                                           const float* bias_nonempty, int64_t n_dst, int64_t d,
+                                           int reduce, int epilogue, int accum, float out_div,
+                                           const float* attn_vec, float* attn_state, float* out,
+                                           int64_t ldo, float* agg, int64_t lda, int agg_mode,
+                                           void* stream) {
+  return launch_spmm_project("gnnrec_spmm_project_agg_f32", indptr, indices, ew, X, ldx, H, ldh,
+                             W_selfT, W_neighT, bias, bias_nonempty, n_dst, d, reduce, epilogue,
+                             accum, out_div, attn_vec, attn_state, out, ldo, agg, lda, agg_mode,
+                             stream);
 }
 
 extern "C" int gnnrec_spmm_project_mfma_f32(const int64_t* indptr, const int32_t* indices,

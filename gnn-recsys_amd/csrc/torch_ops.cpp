@@ -271,6 +271,55 @@ void spmm_project(const Tensor& indptr, const Tensor& indices, const optional<Te
      mfma ? "gnnrec_spmm_project_mfma_f32" : "gnnrec_spmm_project_f32");
 }
 
+// the VALU launch that saves (agg_mode 1) or takes (2) the rows' aggregates: agg [n_dst, d];
+// a load launch reads neither indices, edge weights nor X (all three optional there)
+void spmm_project_agg_f32(const Tensor& indptr, const optional<Tensor>& indices,
+                          const optional<Tensor>& ew, const optional<Tensor>& X, const Tensor& H,
+                          const Tensor& W_selfT, const Tensor& W_neighT,
+                          const optional<Tensor>& bias, const optional<Tensor>& bias_nonempty,
+                          int64_t reduce, int64_t epilogue, int64_t accum, double out_div,
+                          const optional<Tensor>& attn_vec, const optional<Tensor>& attn_state,
+                          Tensor& agg, int64_t agg_mode, Tensor& out) {
+  const OneDevice one_device_;
+  dev(indptr, "indptr", at::kLong);
+  dev(indices, "indices", at::kInt);
+  dev(ew, "edge_weight", at::kFloat);
+  dev(X, "X", at::kFloat);
+  dev(H, "H", at::kFloat);
+  dev(W_selfT, "W_selfT", at::kFloat);
+  dev(W_neighT, "W_neighT", at::kFloat);
+  dev(bias, "bias", at::kFloat);
+  dev(bias_nonempty, "bias_nonempty", at::kFloat);
+  dev(attn_vec, "attn_vec", at::kFloat);
+  dev(attn_state, "attn_state", at::kFloat);
+  dev(agg, "agg", at::kFloat);
+  dev(out, "out", at::kFloat);
+  const int64_t n_dst = indptr.numel() - 1, d = H.size(1);
+  TORCH_CHECK_VALUE(agg_mode == GNNREC_AGG_SAVE || agg_mode == GNNREC_AGG_LOAD,
+                    "agg_mode must be GNNREC_AGG_SAVE or GNNREC_AGG_LOAD");
+  TORCH_CHECK_VALUE(agg_mode == GNNREC_AGG_LOAD || (has(indices) && has(X)),
+                    "a saving launch gathers: it needs indices and X");
+  TORCH_CHECK_VALUE(!has(X) || X->size(1) == d, "X and H widths differ");
+  TORCH_CHECK_VALUE(H.size(0) >= n_dst, "H has ", H.size(0), " rows, the CSR ", n_dst,
+                    " destinations");
+  TORCH_CHECK_VALUE(out.size(0) == n_dst && out.size(1) == d, "out must be [", n_dst, ", ", d, "]");
+  TORCH_CHECK_VALUE(agg.dim() == 2 && agg.size(0) == n_dst && agg.size(1) == d, "agg must be [",
+                    n_dst, ", ", d, "]");
+  TORCH_CHECK_VALUE(W_selfT.is_contiguous() && W_neighT.is_contiguous(),
+                    "transposed weights must be contiguous");
+  const int64_t ldx = has(X) ? ld(*X, "X") : 0, ldh = ld(H, "H"), ldo = ld(out, "out");
+  const int64_t lda = ld(agg, "agg");
+  if (meta(H)) return;
+  const c10::DeviceGuard g(H.device());
+  ck(gnnrec_spmm_project_agg_f32(p<int64_t>(indptr), p<int32_t>(indices), p<float>(ew),
+                                 p<float>(X), ldx, p<float>(H), ldh, p<float>(W_selfT),
+                                 p<float>(W_neighT), p<float>(bias), p<float>(bias_nonempty),
+                                 n_dst, d, (int)reduce, (int)epilogue, (int)accum, (float)out_div,
+                                 p<float>(attn_vec), p<float>(attn_state), p<float>(out), ldo,
+                                 p<float>(agg), lda, (int)agg_mode, stream_of(H)),
+     "gnnrec_spmm_project_agg_f32");
+}
+
 // ---------------------------------------------------------------- packed rows
 // packed: int32 [n, 96] (csrc/pack_rows.hpp), status: int32 [4]
 void packed_pair(const Tensor& packed, const Tensor& status, const Tensor& X) {
@@ -2516,6 +2565,10 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor W_selfT, Tensor? W_neighT, Tensor? bias, Tensor? bias_nonempty, int reduce, "
         "int epilogue, int accum, float out_div, Tensor? attn_vec, Tensor(b!)? attn_state, "
         "bool mfma, Tensor(a!) out) -> ()");
+  m.def("spmm_project_agg_f32(Tensor indptr, Tensor? indices, Tensor? edge_weight, Tensor? X, "
+        "Tensor H, Tensor W_selfT, Tensor W_neighT, Tensor? bias, Tensor? bias_nonempty, "
+        "int reduce, int epilogue, int accum, float out_div, Tensor? attn_vec, "
+        "Tensor(b!)? attn_state, Tensor(c!) agg, int agg_mode, Tensor(a!) out) -> ()");
   m.def("pack_rows_f32(Tensor X, float max_dense_frac, Tensor(a!) packed, Tensor(b!) status) "
         "-> ()");
   m.def("spmm_csr_packed_f32(Tensor indptr, Tensor indices, Tensor packed, Tensor status, "
@@ -2709,6 +2762,7 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("gemm", &gemm);                                 \
   m.impl("row_epilogue", &row_epilogue);                 \
   m.impl("spmm_project", &spmm_project);                 \
+  m.impl("spmm_project_agg_f32", &spmm_project_agg_f32); \
   m.impl("spmm_project2", &spmm_project2);               \
   m.impl("pack_rows_f32", &pack_rows_f32);               \
   m.impl("spmm_csr_packed_f32", &spmm_csr_packed_f32);   \

@@ -28,6 +28,7 @@ EPI_RELU, EPI_L2NORM, EPI_SIGMOID = 1, 2, 4
 ACC_STORE, ACC_ADD, ACC_MAX = 0, 1, 2
 ACC_ATTN_FIRST, ACC_ATTN, ACC_ATTN_LAST = 3, 4, 5
 A2_NONE, A2_DIV_DEG, A2_ZERO_DEG = 0, 1, 2
+AGG_NONE, AGG_SAVE, AGG_LOAD = 0, 1, 2  # spmm_project_agg: the rows' aggregates kept / reused
 DROPOUT_SRC, DROPOUT_OUT = 0, 1
 
 
@@ -116,6 +117,9 @@ SIGNATURES = {
     "gnnrec_lstm_slots": (_INT, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "gnnrec_spmm_project_f32": (_INT, [_P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I64,
                                        _INT, _INT, _INT, _F32, _P, _P, _P, _I64, _P]),
+    "gnnrec_spmm_project_agg_f32": (_INT, [_P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64,
+                                           _I64, _INT, _INT, _INT, _F32, _P, _P, _P, _I64, _P,
+                                           _I64, _INT, _P]),
     "gnnrec_spmm_project_mfma_f32": (_INT, [_P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I64,
                                        _INT, _INT, _INT, _F32, _P, _P, _P, _I64, _P]),
     "gnnrec_spmm_project2_f32": (_INT, [_P, _P, _P, _P, _I64, _INT, _P, _P, _P, _P, _P, _I64, _INT,

@@ -794,12 +794,49 @@ class ShardedFullGraphPass:
     user-dst aggregation and the all-gather the next layer's partial aggregation.
 
     `ops_backend` defaults to the HIP ops (gnnrec.ops); tests on CPU ranks
-    inject a checker backend with the same signatures."""
+    inject a checker backend with the same signatures.
+
+    The first layer's aggregates of the caller's raw feature tensors are kept across run()
+    calls (cache_aggregates): a pass over the same tensors projects them with
+    the current weights instead of gathering again; agg_hits / agg_saved record which
+    relations did.  A feature write that does not move the tensor's version counter needs
+    invalidate_aggregates().  With several ranks, run() and invalidate_aggregates() are
+    collective: every rank passes the same tensors, rewritten on all ranks or on none;
+    relations whose hit skips a collective are kept only with cache_exchanged=True."""
 
     def __init__(self, model, shard: GraphShard, exchange: Optional[Exchange] = None,
                  ops_backend=None, overlap: bool = True, fold_embedding: bool = True,
-                 deterministic: bool = False, concurrency=None):
+                 deterministic: bool = False, concurrency=None, cache_aggregates: bool = True,
+                 cache_exchanged: bool = False):
         self.model = model
+        # The first layer's aggregates of RAW feature tables (mean / sum / max over a
+        # relation's in-edges of feats[src]) depend on the shard and the features alone, never
+        # on a weight: a folded NodeEmbedding moves W_e into the layer's weights and leaves
+        # the gather on the caller's tensor.  They are kept across passes (one buffer per
+        # relation, allocated once per runner) and a later pass over the same tensors
+        # projects them instead of gathering again (_agg_lookup; DESIGN §25).
+        #   key: (id, _version, data_ptr, shape, stride) of the source table and of the edge
+        #   weights, and the reducer; the entry holds the tensors, so an id is not recycled.
+        #   SPMD: at P > 1 a hit skips the relation's partial exchange, so every rank must
+        #   take the same decision — it depends on the caller's tensors alone, which every
+        #   rank passes in step (the same tensors, rewritten on every rank or on none);
+        #   invalidate_aggregates() is collective in the same sense.  No host read agrees it,
+        #   so a rank that decides alone leaves the others waiting in the collective: with
+        #   several ranks the relations whose hit skips one (those into a replicated type)
+        #   are kept only on request, cache_exchanged=True or GNNREC_AGG_CACHE_EXCHANGE=1,
+        #   by a caller who keeps that contract; the partitioned side, which exchanges
+        #   nothing, is kept at any world size.
+        #   Staleness: a write that does not move _version (a raw pointer handed to the C
+        #   ABI, .data tricks) is not seen: call invalidate_aggregates() after one.
+        # GNNREC_AGG_CACHE=0 or cache_aggregates=False: every pass gathers.
+        self.cache_aggregates = bool(cache_aggregates)
+        self.cache_exchanged = bool(cache_exchanged)
+        self._agg_cache = {}  # ce -> {'key', 'refs', 'buf', 'valid'}
+        self._agg_miss = {}   # ce -> buffer the current pass fills
+        self._agg_on = self._agg_exchange_on = False
+        self.agg_hits = set()   # relations whose kept aggregate the last run reused
+        self.agg_saved = set()  # relations whose aggregate the last run kept
+        self._feats_in = {}
         # deterministic: outputs bitwise independent of the world size (needs a shard built
         # with `segments`): replicated-type sums are per-segment partials folded in a fixed
         # pairwise tree (locally, then across ranks after an all-to-all) and every kernel
@@ -857,6 +894,7 @@ class ShardedFullGraphPass:
         self.packed = set()  # relations whose gather read packed rows
         self._scratch_ev = {}  # scratch key -> event of the side-stream work reading it
         self._last, self._replicate_last = False, True
+        self._side_hold = None  # (event, tensors) of the last layer's side-stream work (_layer)
 
     def _scratch(self, key, shape, device):
         """A per-runner scratch table reused by every pass (tile partials, unfused
@@ -873,6 +911,62 @@ class ShardedFullGraphPass:
             t = torch.empty(shape, dtype=torch.float32, device=device)
             self._pool[key] = t
         return t
+
+    def invalidate_aggregates(self) -> None:
+        """Drop the kept first-layer aggregates: the next pass gathers them again.  For
+        feature (or edge weight) writes that do not move the tensor's version counter.  With
+        several ranks every rank calls it before the same pass (a hit skips a collective)."""
+        self._agg_cache.clear()
+
+    @staticmethod
+    def _tkey(t):
+        return (id(t), t._version, t.data_ptr(), tuple(t.shape), tuple(t.stride()))
+
+    def _agg_lookup(self, ce, msg, preagg, weights, reduce, rows, exchanged=False):
+        """The kept aggregate of first-layer relation ce: (buffer [rows, d], hit), or None
+        when the relation is not cacheable — its source table must BE the caller's feature
+        tensor (a folded embedding, or no embedding layer), with no fc_preagg and a reducer
+        that splits (not lstm).  hit: the buffer holds the aggregate of exactly these
+        tensors; else the caller fills it in this pass and reports that with _agg_filled.
+        exchanged: with several ranks a hit skips a collective (cache_exchanged)."""
+        if exchanged and multi_rank(self.ex) and not self._agg_exchange_on:
+            return None
+        if not self._agg_on or self._layer_idx != 0 or preagg or reduce == 'lstm' or \
+                msg is not self._feats_in.get(ce[0]) or msg.dim() != 2:
+            return None
+        key = (self._tkey(msg), None if weights is None else self._tkey(weights), reduce)
+        shape = (rows, msg.shape[1])
+        ent = self._agg_cache.get(ce)
+        buf = None
+        if ent is not None and tuple(ent['buf'].shape) == shape and ent['buf'].device == msg.device:
+            buf = ent['buf']
+            if ent['valid'] and ent['key'] == key:
+                self.agg_hits.add(ce)
+                return buf, True
+        if buf is None:
+            buf = torch.empty(shape, dtype=torch.float32, device=msg.device)
+        self._agg_cache[ce] = {'key': key, 'refs': (msg, weights), 'buf': buf, 'valid': False}
+        self._agg_miss[ce] = buf
+        return buf, False
+
+    def _agg_unhit(self, ce):
+        """Take back a hit (its partner in a two-relation tile launch missed): ce is
+        gathered in this pass after all."""
+        ent = self._agg_cache[ce]
+        ent['valid'] = False
+        self.agg_hits.discard(ce)
+        self._agg_miss[ce] = ent['buf']
+
+    def _agg_filled(self, ce, own=None):
+        """The launches that produce relation ce's aggregate are queued; `own`: the tensor
+        that holds it, copied when it is not the buffer itself (several ranks: the
+        exchange's output).  -> the buffer."""
+        buf = self._agg_miss.pop(ce)
+        if own is not None and own.data_ptr() != buf.data_ptr():
+            buf.copy_(own)
+        self._agg_cache[ce]['valid'] = True
+        self.agg_saved.add(ce)
+        return buf
 
     def _pack(self, msg, nt, reduce, weighted):
         """The packed copy of hidden table `msg` = h[nt] (384-B rows: a ReLU output is about
@@ -989,6 +1083,14 @@ class ShardedFullGraphPass:
         self._packed_on = self.ops is ops and sh.device.type == 'cuda' and \
             os.environ.get("GNNREC_PACKED_ROWS", "1") != "0"
         self.packed.clear()
+        self._agg_on = self.cache_aggregates and os.environ.get("GNNREC_AGG_CACHE", "1") != "0"
+        self._agg_exchange_on = self.cache_exchanged or \
+            os.environ.get("GNNREC_AGG_CACHE_EXCHANGE", "0") != "0"
+        self._feats_in = feats
+        self._agg_miss.clear()
+        self._side_hold = None
+        self.agg_hits.clear()
+        self.agg_saved.clear()
         if embedding_layer is None:
             embedding_layer = m.embedding_layer
         h = dict(feats)
@@ -1027,6 +1129,9 @@ class ShardedFullGraphPass:
                 self.capture.append(dict(h))
         for nt in list(h):
             self._get(h, nt)
+        if self._side_hold is not None:  # main is ordered after everything the side stream ran
+            torch.cuda.current_stream(self.shard.device).wait_event(self._side_hold[0])
+            self._side_hold = None
         return h
 
     def _foldable(self, hconv, h, nt, W_emb) -> bool:
@@ -1125,8 +1230,16 @@ class ShardedFullGraphPass:
                     # source-range tiles: each tile gathers from a slice of the source table
                     # small enough to stay in the Infinity Cache; accumulated in place
                     op = 'max' if reduce == 'max' else 'sum'
-                    part = self._scratch(('part', ce, self._par()), (rs.n_rows, msg.shape[1]),
-                                         msg.device)
+                    kept = self._agg_lookup(ce, msg, preagg, rs.weights if weighted else None,
+                                            reduce, sh.shard_rows[T], exchanged=True)
+                    if kept is not None and kept[1]:  # no tiles, no exchange
+                        partials[ce] = (kept[0], None, reduce, 'kept')
+                        continue
+                    # one rank: the partial IS the owner's aggregate, accumulated in the kept
+                    # buffer itself
+                    part = kept[0] if kept is not None and not multi_rank(self.ex) else \
+                        self._scratch(('part', ce, self._par()), (rs.n_rows, msg.shape[1]),
+                                      msg.device)
                     pk = None if preagg else self._pack(msg, ce[0], reduce, weighted)
                     if pk is not None:
                         self.packed.add(ce)
@@ -1144,7 +1257,7 @@ class ShardedFullGraphPass:
                     if can_fuse(rs.indptr, msg, self_rows, mod.fc_self.weight,
                                 mod.fc_neigh.weight):
                         # one rank: no partials to exchange, aggregate + project in _owned
-                        partials[ce] = ('fused', msg, reduce, weighted)
+                        partials[ce] = ('fused', msg, reduce, weighted, preagg)
                         continue
                 if reduce == 'lstm':
                     # the recurrence runs over each destination's whole in-edge sequence and
@@ -1160,10 +1273,16 @@ class ShardedFullGraphPass:
                         own = self._lstm(mod, rs.indptr, rs.indices, msg)
                     partials[ce] = (own, None, reduce)
                     continue
+                kept = self._agg_lookup(ce, msg, preagg, rs.weights if weighted else None,
+                                        reduce, sh.shard_rows[T], exchanged=True)
+                if kept is not None and kept[1]:
+                    partials[ce] = (kept[0], None, reduce, 'kept')
+                    continue
+                okw = {'out': kept[0]} if kept is not None and not multi_rank(self.ex) else {}
                 with self._time('spmm'):
                     part = O.spmm(rs.indptr, rs.indices, msg, 'max' if reduce == 'max' else 'sum',
                                   edge_weight=rs.weights if weighted else None,
-                                  empty_neginf=reduce == 'max')
+                                  empty_neginf=reduce == 'max', **okw)
                 own, work = self.ex.reduce_scatter_rows(part, 'max' if reduce == 'max' else 'sum',
                                                         async_op=self.overlap)
                 partials[ce] = (own, work, reduce)
@@ -1205,8 +1324,31 @@ class ShardedFullGraphPass:
         parts = {ce: [] for ce, *_ in rels}
         n_seg = max((len(rs.segs) for _, rs, *_ in rels), default=0)
         pairs = self._tile_pairs(rels)
+        # first-layer aggregates kept from an earlier pass: a relation that hits runs no
+        # tile, no tree and no exchange (both relations of a two-relation launch, or
+        # neither); one that misses builds its tree in the kept buffer — at one rank tile 0's
+        # output, which the tree's last level is folded into
+        kept = {ce: self._agg_lookup(ce, msg, preagg, rs.weights if weighted else None, reduce,
+                                     self.shard.shard_rows[ce[2]], exchanged=True)
+                for ce, rs, msg, weighted, reduce, preagg in rels}
+        hits = {ce for ce, k in kept.items() if k is not None and k[1]}
+        for item in pairs:
+            both = {r[0] for r in item}
+            if len(item) == 2 and len(both & hits) == 1:
+                ce = (both & hits).pop()  # its partner gathers: the launch runs for both
+                self._agg_unhit(ce)
+                hits.discard(ce)
+        one = not multi_rank(self.ex)
+
+        def tile0(ce, j, shp, dev):
+            if j == 0 and one and kept[ce] is not None:
+                return kept[ce][0]
+            return self._scratch(('tile', ce, j, self._par()), shp, dev)
+
         for j in range(n_seg):
             for item in pairs:
+                if item[0][0] in hits:
+                    continue
                 if len(item) == 2:  # two relations, one launch per tile (gnnrec_spmm_csr2_f32)
                     (ca, ra, msg, weighted, *_), (cb, rb, *_r) = item
                     self.tile_pairs.add((ca, cb))
@@ -1218,10 +1360,8 @@ class ShardedFullGraphPass:
                             shp = (ra.n_rows, msg.shape[1])
                             pa, pb = self.ops.spmm2(
                                 csr_a, csr_b, msg, 'sum',
-                                out_a=self._scratch(('tile', ca, j, self._par()), shp,
-                                                    msg.device),
-                                out_b=self._scratch(('tile', cb, j, self._par()), shp,
-                                                    msg.device))
+                                out_a=tile0(ca, j, shp, msg.device),
+                                out_b=tile0(cb, j, shp, msg.device))
                             parts[ca].append(pa)
                             parts[cb].append(pb)
                         else:
@@ -1240,13 +1380,15 @@ class ShardedFullGraphPass:
                     if j % 2 == 0:
                         parts[ce].append(self._spmm(
                             ip, ix, msg, 'sum', pk, edge_weight=ew, split=TILE_SPLIT,
-                            out=self._scratch(('tile', ce, j, self._par()),
-                                              (rs.n_rows, msg.shape[1]), msg.device)))
+                            out=tile0(ce, j, (rs.n_rows, msg.shape[1]), msg.device)))
                     else:
                         self._spmm(ip, ix, msg, 'sum', pk, edge_weight=ew, out=parts[ce][-1],
                                    accumulate=True, split=TILE_SPLIT)
         out = {}
         for ce, rs, msg, weighted, reduce, _ in rels:
+            if ce in hits:
+                out[ce] = (kept[ce][0], None, reduce, 'kept')
+                continue
             if not multi_rank(self.ex) and self._owned_side:
                 # one rank, owner work on the side stream: the whole tree is folded there
                 # (_owned), off the main stream that runs the pair launch's inputs next
@@ -1336,22 +1478,34 @@ class ShardedFullGraphPass:
                         msg = O.preproject(msg, Wn, out=self._scratch(
                             ('pre', ce), (msg.shape[0], Wn.shape[0]), msg.device))
                     Wn = None
-                with self._time(self._fused_tag(rs, avg)):
+                tag, kkw = (self._fused_tag(rs, avg), {}) if Wn is None else \
+                    self._fused_kept(ce, rs, msg, preagg, weighted, reduce, avg)
+                with self._time(tag):
                     O.spmm_project(rs.indptr, rs.indices, msg, self_rows, Ws, Wn, reduce,
                                    rs.weights if weighted else None, relu=True,
                                    l2norm=bool(mod.norm), accum=acc, out_div=div, out=o,
-                                   bias=bias, bias_nonempty=bias_ne, **akw, **vkw)
+                                   bias=bias, bias_nonempty=bias_ne, **akw, **vkw, **kkw)
+                if ce in self._agg_miss:
+                    self._agg_filled(ce)
                 self.fused.add(ce)
                 continue
-            with self._time('spmm'):
-                ev_prev = self._scratch_ev.pop(('agg', ce), None)
-                if ev_prev is not None:  # the last side-stream GEMM that read this scratch
-                    torch.cuda.current_stream(self.shard.device).wait_event(ev_prev)
-                a = (self._lstm(mod, rs.indptr, rs.indices, msg) if reduce == 'lstm' else
-                     O.spmm(rs.indptr, rs.indices, msg, reduce,
-                            edge_weight=rs.weights if weighted else None,
-                            out=self._scratch(('agg', ce), (rs.n_rows, msg.shape[1]),
-                                              msg.device)))
+            # unfused: the aggregate in a scratch table, or in the kept buffer (a hit: no spmm)
+            kept = self._agg_lookup(ce, msg, preagg, rs.weights if weighted else None, reduce,
+                                    rs.n_rows)
+            if kept is not None and kept[1]:
+                a = kept[0]
+            else:
+                with self._time('spmm'):
+                    ev_prev = self._scratch_ev.pop(('agg', ce), None)
+                    if ev_prev is not None:  # the last side-stream GEMM that read this scratch
+                        torch.cuda.current_stream(self.shard.device).wait_event(ev_prev)
+                    a = (self._lstm(mod, rs.indptr, rs.indices, msg) if reduce == 'lstm' else
+                         O.spmm(rs.indptr, rs.indices, msg, reduce,
+                                edge_weight=rs.weights if weighted else None,
+                                out=kept[0] if kept is not None else self._scratch(
+                                    ('agg', ce), (rs.n_rows, msg.shape[1]), msg.device)))
+                if kept is not None:
+                    self._agg_filled(ce)
             if o is None:
                 o = torch.empty((sh.n_own, mod._out_feats), dtype=torch.float32, device=a.device)
                 akw = self._attn(hconv, T, sh.n_own, o.device)
@@ -1482,6 +1636,21 @@ class ShardedFullGraphPass:
                 return None
         return plan
 
+    def _fused_kept(self, ce, rs, msg, preagg, weighted, reduce, avg):
+        """(timer tag, spmm_project kwargs) of a fused launch of the VALU kernel that keeps
+        the rows' aggregate (a miss: the usual tag, the launch gathers) or takes the kept one
+        (a hit: 'project_cached', no aggregation launch — the tools that price the gathers do
+        not count it).  The MFMA variant and other backends run as ever."""
+        tag = self._fused_tag(rs, avg)
+        if tag != 'spmm_project' or self.ops is not ops:
+            return tag, {}
+        kept = self._agg_lookup(ce, msg, preagg, rs.weights if weighted else None, reduce,
+                                rs.indptr.numel() - 1)
+        if kept is None:
+            return tag, {}
+        return ('project_cached', {'agg': kept[0], 'agg_mode': 'load'}) if kept[1] else \
+            (tag, {'agg': kept[0], 'agg_mode': 'save'})
+
     def _fused_tag(self, rs, avg):
         """timer tag of a fused launch: 'spmm_project' (VALU kernel) or 'spmm_project_mfma'."""
         fv = getattr(self.ops, 'fused_variant', None)
@@ -1508,27 +1677,33 @@ class ShardedFullGraphPass:
             for j, ce in enumerate(ces):
                 mod = hconv.mods[ce[1]]
                 acc, div = hconv.accum_mode(j, R)
-                if isinstance(partials[ce][0], str):  # ('fused', msg, reduce, weighted)
-                    _, msg, reduce, weighted = partials[ce]
+                if isinstance(partials[ce][0], str):  # ('fused', msg, reduce, weighted, preagg)
+                    _, msg, reduce, weighted, preagg = partials[ce]
                     rs = sh.rels[ce]
                     if o is None:
                         o = torch.empty((self_rows.shape[0], mod._out_feats),
                                         dtype=torch.float32, device=msg.device)
                     Ws, Wn, bias, bias_ne = self._folded(mod, ce)
-                    with self._time(self._fused_tag(rs, None)):
+                    tag, kkw = self._fused_kept(ce, rs, msg, preagg, weighted, reduce, None)
+                    with self._time(tag):
                         O.spmm_project(rs.indptr, rs.indices, msg, self_rows, Ws, Wn, reduce,
                                        rs.weights if weighted else None, relu=True,
                                        l2norm=bool(mod.norm), accum=acc, out_div=div, out=o,
-                                       bias=bias, bias_nonempty=bias_ne, **akw)
+                                       bias=bias, bias_nonempty=bias_ne, **akw, **kkw)
+                    if ce in self._agg_miss:
+                        self._agg_filled(ce)
                     self.fused.add(ce)
                     continue
                 own, work, reduce = partials[ce][:3]
+                kind = partials[ce][3] if len(partials[ce]) == 4 else None
                 if work is not None:
                     work.wait()
-                if len(partials[ce]) == 4 and partials[ce][3] == 'tree_local':
+                if kind == 'tree_local':
                     own = _tree_sum(own, self.ops)  # one rank: the segments' whole tree
-                elif len(partials[ce]) == 4:  # deterministic: fold the P subtree roots
+                elif kind == 'tree':  # deterministic: fold the P subtree roots
                     own = _tree_sum(list(own.unbind(0)), self.ops)
+                if ce in self._agg_miss:  # the owner's aggregate of raw features: kept
+                    own = self._agg_filled(ce, own)
                 if o is None:
                     o = torch.empty((own.shape[0], mod._out_feats), dtype=torch.float32,
                                     device=own.device)
@@ -1565,6 +1740,7 @@ class ShardedFullGraphPass:
             t.record_stream(main)  # read on main later: not recycled under it
             self._ready[id(t)] = ev
             out[T] = t
+        return ev
 
     def _layer(self, hconv, h):
         self._packs = {}
@@ -1576,9 +1752,21 @@ class ShardedFullGraphPass:
             # (the tiles' tree is folded on the side stream too: the partitioned type's
             # launch follows the tiles at once — C4 143.2 -> 142.9 ms, C5 152.3 -> 151.5)
             partials = self._partials(hconv, h, active)
-            self._owned_on_side(hconv, h, active, partials, out)
+            ev = self._owned_on_side(hconv, h, active, partials, out)
             self._local(hconv, h, active, out)
             self._fold.clear()
+            # The side stream reads tensors that main allocated: this layer's input tables
+            # and what _partials made (a fused launch's fc_preagg message, an untiled
+            # partial).  The caller drops them when this layer returns, and the allocator
+            # would hand their memory to main's next allocation (the next layer's fc_preagg
+            # output is written before main waits for anything of the side stream) while a
+            # late side stream still reads it.  They stay referenced for one more layer and
+            # are let go once main is ordered after the side work that read them (no
+            # record_stream: it would park every such block until the side stream catches
+            # up, _scratch).
+            held, self._side_hold = self._side_hold, (ev, partials, h)
+            if held is not None:
+                torch.cuda.current_stream(self.shard.device).wait_event(held[0])
             return out
         if multi_rank(self.ex):
             partials = self._partials(hconv, h, active)

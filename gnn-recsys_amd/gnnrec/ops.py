@@ -961,7 +961,9 @@ def spmm_project(indptr, indices, X, H, W_self, W_neigh, reduce: str = "mean",
                  bias_nonempty: Optional[torch.Tensor] = None,
                  attn_vec: Optional[torch.Tensor] = None,
                  attn_state: Optional[torch.Tensor] = None,
-                 avg_deg: Optional[float] = None, variant: Optional[str] = None) -> torch.Tensor:
+                 avg_deg: Optional[float] = None, variant: Optional[str] = None,
+                 agg: Optional[torch.Tensor] = None,
+                 agg_mode: Optional[str] = None) -> torch.Tensor:
     """a1+a3 fused: out (accum)= epi(H W_selfᵀ + reduce_e X[src_e] W_neighᵀ + bias
     + [deg > 0]·bias_nonempty), d = 128.  variant 'valu' | 'mfma' (default: fused_variant
     of avg_deg) picks the kernel; both give the same aggregate bits, the projection's
@@ -970,10 +972,23 @@ def spmm_project(indptr, indices, X, H, W_self, W_neigh, reduce: str = "mean",
     W_neigh None: X holds pre-projected source rows (preproject(X, W_neigh)) and the
     neighbour term is reduce_e X[src_e] itself (sum / mean only; the mfma kernel, which
     then runs only the self half on the MFMA).  The same value up to fp32 rounding: the
-    projection is applied before the (linear) reduction instead of after it."""
+    projection is applied before the (linear) reduction instead of after it.
+
+    agg_mode 'save' | 'load' with agg [n_dst, 128] (the valu kernel only): the rows'
+    aggregates reduce_e X[src_e] — which no weight enters — are also written to agg ('save':
+    spmm's bits for the same CSR and reduce), or read from it instead of gathered ('load':
+    indices, X and edge_weight are not read and may be None).  `out` has the same bits as the
+    plain launch's on the same aggregate."""
+    if agg_mode not in (None, "save", "load"):
+        raise ValueError(f"spmm_project agg_mode must be 'save' or 'load', not {agg_mode!r}")
+    if (agg is None) != (agg_mode is None):
+        raise ValueError("spmm_project: agg and agg_mode go together")
+    load = agg_mode == "load"
     _dev(indptr, "indptr", torch.int64)
-    _dev(indices, "indices", torch.int32)
-    _dev(X, "X", torch.float32)
+    if not load or indices is not None:
+        _dev(indices, "indices", torch.int32)
+    if not load or X is not None:
+        _dev(X, "X", torch.float32)
     _dev(H, "H", torch.float32)
     n_dst = indptr.numel() - 1
     if H.shape[0] < n_dst:
@@ -985,7 +1000,7 @@ def spmm_project(indptr, indices, X, H, W_self, W_neigh, reduce: str = "mean",
     if out is None:
         if accum not in ("store", "attn_first"):
             raise ValueError("accumulating spmm_project needs an out tensor")
-        out = torch.empty((n_dst, D), dtype=torch.float32, device=X.device)
+        out = torch.empty((n_dst, D), dtype=torch.float32, device=H.device)
     else:
         _dev(out, "out", torch.float32)
         if tuple(out.shape) != (n_dst, D):
@@ -1010,12 +1025,27 @@ def spmm_project(indptr, indices, X, H, W_self, W_neigh, reduce: str = "mean",
     bias_nonempty = None if bias_nonempty is None else bias_nonempty.detach().contiguous()
     av, ast = _attn_args(accum, attn_vec, attn_state, n_dst, D)
     epi = (_lib.EPI_RELU if relu else 0) | (_lib.EPI_L2NORM if l2norm else 0)
-    variant = variant or fused_variant(indptr, avg_deg)
+    variant = variant or ("valu" if agg_mode is not None else fused_variant(indptr, avg_deg))
     if variant not in ("valu", "mfma"):
         raise ValueError(f"spmm_project variant must be 'valu' or 'mfma', not {variant!r}")
-    _rowmajor(X, "X")
+    if X is not None:
+        _rowmajor(X, "X")
     _rowmajor(H, "H")
     _rowmajor(out, "out")
+    if agg_mode is not None:
+        if variant != "valu" or W_neigh is None:
+            raise ValueError("spmm_project: agg_mode runs on the valu kernel")
+        _dev(agg, "agg", torch.float32)
+        if agg.dim() != 2 or tuple(agg.shape) != (n_dst, D):
+            raise ValueError(f"agg must be [{n_dst}, {D}], got {tuple(agg.shape)}")
+        _rowmajor(agg, "agg")
+        if n_dst == 0:  # nothing to launch
+            return out
+        _T().spmm_project_agg_f32(indptr, indices, edge_weight, X, H, WsT, WnT, bias,
+                                  bias_nonempty, REDUCE[reduce], epi, ACCUM[accum],
+                                  float(out_div), av, ast, agg,
+                                  _lib.AGG_LOAD if load else _lib.AGG_SAVE, out)
+        return out
     _T().spmm_project(indptr, indices, edge_weight, X, H, WsT, WnT, bias, bias_nonempty,
                       REDUCE[reduce], epi, ACCUM[accum], float(out_div), av, ast,
                       variant == "mfma", out)

@@ -343,6 +343,28 @@ int gnnrec_spmm_project_f32(const int64_t* indptr, const int32_t* indices, const
                             int epilogue, int accum, float out_div, const float* attn_vec,
                             float* attn_state, float* out, int64_t ldo, void* stream);
 
+/* gnnrec_spmm_project_f32 that also saves, or takes, the rows' aggregates agg(v): a table
+ * agg [n_dst, d] with row stride lda >= d (lda % 4 == 0, 16-B aligned).  agg(v) depends on
+ * the CSR, ew and X alone — not on a weight, a bias or the epilogue — so a caller whose X
+ * stays fixed from launch to launch saves it once and loads it afterwards.
+ *   GNNREC_AGG_NONE  gnnrec_spmm_project_f32 itself (agg ignored)
+ *   GNNREC_AGG_SAVE  the same launch, and agg[v] receives agg(v): the bits
+ *                    gnnrec_spmm_csr_f32 gives for the same CSR and reduce
+ *   GNNREC_AGG_LOAD  agg(v) is read from agg[v] instead of gathered: indices, ew and X are
+ *                    not read (they may be NULL); indptr still is, for bias_nonempty
+ * The projection and epilogue are the same instructions in every mode: on the same
+ * aggregate the three modes write bit-identical `out`. */
+#define GNNREC_AGG_NONE 0
+#define GNNREC_AGG_SAVE 1
+#define GNNREC_AGG_LOAD 2
+int gnnrec_spmm_project_agg_f32(const int64_t* indptr, const int32_t* indices, const float* ew,
+                                const float* X, int64_t ldx, const float* H, int64_t ldh,
+                                const float* W_selfT, const float* W_neighT, const float* bias,
+                                const float* bias_nonempty, int64_t n_dst, int64_t d, int reduce,
+                                int epilogue, int accum, float out_div, const float* attn_vec,
+                                float* attn_state, float* out, int64_t ldo, float* agg,
+                                int64_t lda, int agg_mode, void* stream);
+
 /* The same operation with the projection on the MFMA, for low-degree CSRs (callers
  * pick it below ~24 edges per row): 32-row tiles, [h_self | agg] staged in LDS and
  * multiplied by the register-resident weights with v_mfma_f32_32x32x2_f32, so the
