@@ -19,8 +19,9 @@
 // LDS: W_selfᵀ, W_neighᵀ (2 × 64 KiB, k-major so a lane's two output columns are one
 // ds_read_b64) + per wave ROWS × (agg, self) row slots read back as broadcasts.
 //
-// Three kernels live here (spmm_project_kernel above, spmm_project_mfma_kernel and
-// spmm_project2_pipe_kernel below) beside spmm_pair_mfma.hip's fourth; what they have in
+// Four kernels live here (spmm_project_kernel above, spmm_project_mfma_kernel,
+// spmm_project_load_mfma_kernel and spmm_project2_pipe_kernel below) beside
+// spmm_pair_mfma.hip's fifth; what they have in
 // common is written once: gather.hpp has the lockstep 4-row gather (gather_lockstep4), the
 // row epilogue (activate, combine2_store) and the streamed-weight MFMA projection
 // (weight_rsrc, mfma_project32, store_c32); rowq.hpp the block-level tile walk (TileCursor)
@@ -108,14 +109,13 @@ __device__ __forceinline__ void epilogue_row(const EpiArgs& e, int64_t row, bool
 // AGG: what the launch does with a row's finalized aggregate besides projecting it.
 //   kAggNone  nothing more (gnnrec_spmm_project_f32)
 //   kAggSave  lane group 0 also streams the fragment it parks in its slot to agg[row]
-//   kAggLoad  the fragment is read from agg[row] instead of gathered: indices, X and ew are
-//             not touched (they may be null), indptr only for the row's bias_nonempty term
 // The aggregate depends on the CSR and the source table alone, never on a weight, so a caller
 // whose source table stays fixed from launch to launch (a first layer over raw features) saves
-// it once and loads it afterwards.  The slots hold the same bits either way and the matvec,
-// bias and epilogue below are one body: a load launch's output is bit-identical to the
-// gathering launch's on the same aggregate.
-constexpr int kAggNone = GNNREC_AGG_NONE, kAggSave = GNNREC_AGG_SAVE, kAggLoad = GNNREC_AGG_LOAD;
+// it once and loads it afterwards (GNNREC_AGG_LOAD): that launch gathers nothing and is
+// spmm_project_load_mfma_kernel below, which runs this kernel's bias term, fmaf chain and
+// epilogue per output element — its output is bit-identical to the gathering launch's on the
+// same aggregate.
+constexpr int kAggNone = GNNREC_AGG_NONE, kAggSave = GNNREC_AGG_SAVE;
 
 template <int REDUCE, bool WEIGHTED, int UNROLL, int AGG = kAggNone>
 __global__ __launch_bounds__(kPWaves * 64) void spmm_project_kernel(
@@ -168,24 +168,13 @@ __global__ __launch_bounds__(kPWaves * 64) void spmm_project_kernel(
     for (int r = 0; r < kPRows; ++r) {
       const bool valid = r < nv;  // uniform per wave
       hsr[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if constexpr (AGG == kAggLoad) {  // the saved aggregate rides with the self row
-        pidx[r] = 0;
-        if (valid) hsr[r] = ld_stream4((grp == 0 ? agg + (row0 + r) * lda
-                                                 : H + (row0 + r) * ldh) + col);
-      } else {
-        pidx[r] = valid && lane < rb[r + 1] - rb[r] ? ld_stream(indices + rb[r] + lane) : 0;
-        if (valid && grp == 1) hsr[r] = ld_stream4(H + (row0 + r) * ldh + col);
-      }
+      pidx[r] = valid && lane < rb[r + 1] - rb[r] ? ld_stream(indices + rb[r] + lane) : 0;
+      if (valid && grp == 1) hsr[r] = ld_stream4(H + (row0 + r) * ldh + col);
     }
 #pragma unroll
     for (int r = 0; r < kPRows; ++r) {
       const bool valid = r < nv;  // uniform per wave
       const float4 hs = hsr[r];
-      if constexpr (AGG == kAggLoad) {  // group 0: the aggregate, group 1: the self row
-        nonempty[r] = rb[r + 1] - rb[r] > 0;
-        *reinterpret_cast<float4*>(&slots[wave][r][grp][col]) = hs;
-        continue;
-      }
       Frag<VEC> acc;
 #pragma unroll
       for (int v = 0; v < VEC; ++v) acc.v[v] = init;
@@ -417,12 +406,202 @@ __global__ __launch_bounds__(kMWaves * 64, 4) void spmm_project_mfma_kernel(
   if (rq != nullptr) rq_finish(rq);
 }
 
+
+// ---------------------------------------------------------------------------------------
+// The load launch (GNNREC_AGG_LOAD) on the fp32 MFMA, bit for bit the VALU kernel's output.
+//
+// Why: with the aggregate read back instead of gathered, the launch is a plain
+// [n_dst × 256] · [256 × 128] product with the row epilogue, and the VALU kernel runs it at
+// neither limit: per two rows a wave re-reads both weight matrices from LDS (16 ds_read_b64
+// per 8 k) and as many cycles again of slot broadcasts (8 ds_read_b128), ≈8 ms of LDS time at
+// C4's 10M rows beside 4.2 ms of v_pk_fma_f32, and it took 14.7 ms.
+//
+// v_mfma_f32_32x32x2_f32 is a k-ordered fmaf chain, D = fma(a_k1, b_k1, fma(a_k0, b_k0, C)),
+// and the VALU kernel's chain per output element is
+//   z = bias + (nonempty ? bias_ne : 0);  for k: z = fma(self[k], Ws[k][j], z);
+//                                                z = fma(agg[k], Wn[k][j], z)
+// so with k-slot 0 (lanes 0–31) carrying self[row][k], Ws[k][col] and k-slot 1 (lanes 32–63)
+// carrying agg[row][k], Wn[k][col], C initialised to the bias term and the 128 MFMAs of a
+// 32×32 tile issued in ascending k into one accumulator, every element runs that very chain.
+// (spmm_project_mfma_kernel above splits K over lane halves and waves instead: other bits.)
+//
+// Shape: a block of 4 waves walks 32-row tiles (TileCursor); wave w owns output columns
+// 32w … 32w+31 and keeps its 128 weight operands per lane in registers for the whole launch —
+// no weight is re-read, nothing is broadcast.  The tile A = [self | agg] (32 × 256, row stride
+// kALd) is double-buffered: the next tile's rows are DMA'd into the other buffer (one row per
+// wave-instruction, the self half on lanes 0–31, the aggregate on 32–63; no registers live
+// across the MFMAs, which with 128 weights held would spill) before this tile's MFMAs and
+// have landed after them.  The pre-activation tile goes through LDS (store_c32, in
+// the A buffer the MFMAs have just consumed) to the shared epilogue_row, 8 rows per wave at
+// its lane = columns 2l, 2l+1 mapping.  Two blocks per CU (2 × 65 KiB LDS, 2 waves per SIMD, 256
+// registers each): one block's staging and epilogue run under the other's MFMAs.
+//
+// Measured (one MI355X, profiles/project_load_mfma_ab.md): 10M rows 6.22 ms alone and 8.43 ms
+// in the C4 pass beside the first layer's item GEMM (the VALU form: 13.65 and 14.56 ms), 100k
+// rows 0.100 against 0.191 ms, 4099 rows 30 against 31 µs: the VALU load form is retired.
+constexpr int kLWaves = 4;            // waves per block: one 32-column block of the output each
+constexpr int kLRows = kMT / kLWaves;  // rows staged and finished per wave per tile
+static_assert(kMT * kCLd <= kALds, "the C tile lives in the A buffer the MFMAs have consumed");
+
+// 16 B per lane from src (per lane) to lds + 16·lane (lds wave-uniform), non-temporal
+__device__ __forceinline__ void dma16(const float* src, float* lds) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds, 16, 0, 2);
+#endif
+}
+
+__global__ __launch_bounds__(kLWaves * 64, 2) void spmm_project_load_mfma_kernel(
+    const int64_t* __restrict__ indptr, const float* __restrict__ H, int64_t ldh,
+    const float* __restrict__ agg, int64_t lda, const float* __restrict__ WsT,
+    const float* __restrict__ WnT, const float* __restrict__ bias,
+    const float* __restrict__ bias_ne, int64_t n_dst, int epilogue, int accum, float out_div,
+    const float* __restrict__ attn_vec, float* __restrict__ attn_state,
+    float* __restrict__ out, int64_t ldo, unsigned* rq, int rq_ch) {
+  __shared__ __attribute__((aligned(16))) float As[2][kALds];
+  __shared__ int nes[2][kMT];
+  __shared__ int64_t blk_r[2];
+
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int li = lane & 31, bh = lane >> 5;
+  const int col = li * 4;
+  const int j0 = 2 * lane;
+  const int cj = 32 * wave + li;  // this lane's column of the MFMA tile
+  const bool attn = accum >= GNNREC_ACC_ATTN_FIRST;
+  const float a0 = attn ? attn_vec[j0] : 0.f, a1 = attn ? attn_vec[j0 + 1] : 0.f;
+  const EpiArgs ep{(epilogue & GNNREC_EPI_RELU) != 0, (epilogue & GNNREC_EPI_L2NORM) != 0,
+                   attn, accum, out_div, a0, a1, attn_state, out, ldo, j0};
+  const float bj = bias ? bias[cj] : 0.f, cjn = bias_ne ? bias_ne[cj] : 0.f;
+
+  // B operands, resident: MFMA k takes Wsᵀ[k][cj] on lanes 0–31, Wnᵀ[k][cj] on lanes 32–63
+  float bw[kPD];
+  {
+    const float* wp = (bh ? WnT : WsT) + cj;
+#pragma unroll
+    for (int k = 0; k < kPD; ++k) bw[k] = wp[k * kPD];
+  }
+
+  // rows [t0, lim) of a tile (at most kMT: a chunk of the cursor is one tile) into A[b]: a
+  // wave-instruction DMAs one row's 1 KiB, self half from lanes 0–31, aggregate from 32–63.
+  // Rows at or past `lim` keep what the buffer held: a row of A enters its own row of C
+  // only, and that row is not stored.  nonempty per row from indptr (threads 0..31), loaded
+  // first: nothing waits on a load behind the DMAs.
+  int64_t ip0 = 0, ip1 = 0;  // the bounds of row t0 + thread: compared once they have landed
+  auto request = [&](int b, int64_t t0, int64_t lim) __attribute__((always_inline)) {
+    ip0 = ip1 = 0;
+    if (threadIdx.x < kMT) {
+      const int64_t row = t0 + threadIdx.x;
+      if (row < lim) {
+        ip0 = ld_stream(indptr + row);
+        ip1 = ld_stream(indptr + row + 1);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kLRows; ++r) {
+      const int rl = wave * kLRows + r;
+      const int64_t row = t0 + rl;
+      if (row < lim) dma16((bh ? agg + row * lda : H + row * ldh) + col, &As[b][rl * kALd]);
+    }
+  };
+
+  // the cursor's chunk bounds are block-uniform: keep them in scalar registers
+  auto uniform = [](int64_t v) __attribute__((always_inline)) {
+    return (int64_t)(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+                     (unsigned)__builtin_amdgcn_readfirstlane((int)v));
+  };
+  TileCursor<kMT> cur;
+  cur.begin(rq, n_dst, rq_ch, blk_r);
+  int64_t t0, lim;
+  bool have = cur.next(t0, lim);
+  t0 = uniform(t0);
+  lim = uniform(lim);
+  if (have) request(0, t0, lim);
+  int buf = 0;
+  while (have) {
+    // this tile's rows have landed (each wave waits for its own; the cursor's barrier
+    // publishes them and the nonempty flags)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (threadIdx.x < kMT) nes[buf][threadIdx.x] = ip1 - ip0 > 0;
+    int64_t nt0 = 0, nlim = 0;
+    const bool more = cur.next(nt0, nlim);
+    nt0 = uniform(nt0);
+    nlim = uniform(nlim);
+
+    // C = the bias term as the VALU kernel computes it
+    f32x16 c;
+#pragma unroll
+    for (int v = 0; v < 16; ++v)
+      c[v] = bj + (nes[buf][(v & 3) + 8 * (v >> 2) + 4 * bh] ? cjn : 0.f);
+    __builtin_amdgcn_sched_barrier(0);
+    // the next tile's rows into the other buffer, whose C tile every wave has finished
+    // reading before the cursor's barrier: in flight under this tile's MFMAs.  From here to
+    // the barrier after the MFMAs the LDS reads are written as instructions: the compiler
+    // would drain the DMA (vmcnt(0)) before any LDS read of its own that follows one.
+    if (more) request(buf ^ 1, nt0, nlim);
+    __builtin_amdgcn_sched_barrier(0);
+
+    // the chain in ascending k: A operands in chunks of 16 k, the next chunk's reads under
+    // this chunk's MFMAs (all 32 reads up front would spill the weights)
+    const unsigned ap = (unsigned)(uintptr_t)(
+        __attribute__((address_space(3))) const float*)&As[buf][li * kALd + bh * kPD];
+    constexpr int kAC = 16;
+    f32x4s a[2][kAC / 4];
+    auto read_a = [&](int ch) __attribute__((always_inline)) {
+      asm volatile("ds_read_b128 %0, %4\n\t"
+                   "ds_read_b128 %1, %4 offset:16\n\t"
+                   "ds_read_b128 %2, %4 offset:32\n\t"
+                   "ds_read_b128 %3, %4 offset:48"
+                   : "=&v"(a[ch & 1][0]), "=&v"(a[ch & 1][1]), "=&v"(a[ch & 1][2]),
+                     "=&v"(a[ch & 1][3])
+                   : "v"(ap + ch * kAC * 4)
+                   : "memory");
+    };
+    // the reads issued so far have returned; the MFMAs that follow depend on this
+    auto landed_a = [&](int ch) __attribute__((always_inline)) {
+      asm volatile("s_waitcnt lgkmcnt(0)"
+                   : "+v"(a[ch & 1][0]), "+v"(a[ch & 1][1]), "+v"(a[ch & 1][2]),
+                     "+v"(a[ch & 1][3])
+                   :
+                   : "memory");
+    };
+    read_a(0);
+#pragma unroll
+    for (int ch = 0; ch < kPD / kAC; ++ch) {
+      landed_a(ch);
+      if (ch + 1 < kPD / kAC) read_a(ch + 1);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < kAC; ++i)
+        c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ch & 1][i / 4][i % 4], bw[ch * kAC + i], c, 0,
+                                                 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();  // every wave has read A[buf]: it takes the C tile
+
+    float* const Cs = As[buf];
+    store_c32(Cs + cj, kCLd, bh, c);
+    __syncthreads();
+
+#pragma unroll kSpmEU
+    for (int r = 0; r < kLRows; ++r) {
+      const int rl = wave * kLRows + r;
+      const float2 z = *reinterpret_cast<const float2*>(&Cs[rl * kCLd + j0]);
+      epilogue_row(ep, t0 + rl, t0 + rl < lim, z.x, z.y);
+    }
+    t0 = nt0;
+    lim = nlim;
+    have = more;
+    buf ^= 1;
+  }
+  if (rq != nullptr) rq_finish(rq);
+}
+
 }  // namespace
 }  // namespace gnnrec
 
 using namespace gnnrec;
 
-// The VALU kernel's launch, shared by its two entries (`name` keeps each one's messages).
+// The VALU kernel's launch, shared by its two entries (`name` keeps each one's messages); a
+// load launch goes to spmm_project_load_mfma_kernel.
 static int launch_spmm_project(const char* name, const int64_t* indptr, const int32_t* indices,
                                const float* ew, const float* X, int64_t ldx, const float* H,
                                int64_t ldh, const float* W_selfT, const float* W_neighT,
@@ -452,12 +631,24 @@ static int launch_spmm_project(const char* name, const int64_t* indptr, const in
     GNNREC_REQUIRE(aligned16(agg) && lda >= kPD && lda % 4 == 0,
                    "%s: agg needs 16-B aligned rows of lda >= %d floats", name, kPD);
   }
+  hipStream_t s = as_stream(stream);
+  int ticket = -1;
+  if (load) {  // nothing is gathered or reduced: the MFMA load kernel, whatever the reducer
+    // two persistent 4-wave blocks per CU, a queue ticket of one tile per block draw
+    const int64_t blocks = persistent_blocks((n_dst + kMT - 1) / kMT, 2);
+    constexpr int rq_ch = kMT;
+    unsigned* rq = rowq_slot_for(n_dst, blocks, rq_ch, s, &ticket);
+    hipLaunchKernelGGL(spmm_project_load_mfma_kernel, dim3((unsigned)blocks),
+                       dim3(kLWaves * 64), 0, s, indptr, H, ldh, agg, lda, W_selfT, W_neighT,
+                       bias, bias_nonempty, n_dst, epilogue, accum, out_div, attn_vec,
+                       attn_state, out, ldo, rq, rq_ch);
+    rowq_launched(ticket, s);
+    return check_launch(name);
+  }
   // one persistent block per CU; queued rows when every wave has several tickets of work
   const int64_t per_block = (int64_t)kPWaves * kPRows;
   const int64_t blocks = persistent_blocks((n_dst + per_block - 1) / per_block, 1);
   const int rq_ch = kFusedChunk;
-  hipStream_t s = as_stream(stream);
-  int ticket = -1;
   unsigned* rq = rowq_slot_for(n_dst, blocks * kPWaves, rq_ch, s, &ticket);
   const dim3 grid((unsigned)blocks), block(kPWaves * 64);
   auto launch = [&](auto r, auto w, auto m) {
@@ -467,19 +658,14 @@ static int launch_spmm_project(const char* name, const int64_t* indptr, const in
         bias_nonempty, n_dst, epilogue, accum, out_div, attn_vec, attn_state, out, ldo, rq, rq_ch,
         agg, lda);
   };
-  using Sum = std::integral_constant<int, GNNREC_REDUCE_SUM>;
-  if (load) {  // nothing is reduced: one instantiation
-    launch(Sum{}, std::false_type{}, std::integral_constant<int, kAggLoad>{});
-  } else {
-    dispatch_bool(ew != nullptr, [&](auto w) {
-      dispatch_reduce(reduce, [&](auto r) {
-        if (agg_mode == GNNREC_AGG_SAVE)
-          launch(r, w, std::integral_constant<int, kAggSave>{});
-        else
-          launch(r, w, std::integral_constant<int, kAggNone>{});
-      });
+  dispatch_bool(ew != nullptr, [&](auto w) {
+    dispatch_reduce(reduce, [&](auto r) {
+      if (agg_mode == GNNREC_AGG_SAVE)
+        launch(r, w, std::integral_constant<int, kAggSave>{});
+      else
+        launch(r, w, std::integral_constant<int, kAggNone>{});
     });
-  }
+  });
   rowq_launched(ticket, s);
   return check_launch(name);
 }
