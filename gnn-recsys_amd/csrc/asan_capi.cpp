@@ -473,6 +473,59 @@ static void validation() {
                                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                     nullptr, nullptr, nullptr, nullptr) == GNNREC_OK,
         "resolve mlp no pairs");
+  // its list forms: one scored row per user
+  CHECK(gnnrec_rank_list_slots() == 16, "list slots");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_f32(f16, 4, f16, 9, f16, f16, f16, f16, l16, 65, f16,
+                                              i16, i16, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("n_slots must be in"),
+        "list count more slots than the rows hold");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_f32(f16, 4, f16, 9, f16, f16, f16, f16, nullptr, 5, f16,
+                                              i16, i16, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("null lptr"),
+        "list count null lptr");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_f32(f16, 4, f16, 9, f16, f16, f16, f16, l16, 5, f16,
+                                              i16, i16, nullptr, nullptr) == GNNREC_EINVAL &&
+            err_has("null ahead"),
+        "list count null ahead");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_f32(f16, 4, f16, 9, f16, f16, f16, f16, l16, -1, f16,
+                                              i16, i16, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("n_slots must be in"),
+        "list count negative slots");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_f32(f16, 4, f16, 9, f16, f16, f16, f16, nullptr, 0,
+                                              nullptr, nullptr, nullptr, nullptr, nullptr) ==
+            GNNREC_OK,
+        "list count no slots");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_rating_f32(f16, 4, f16, 9, f16, f16, f16, f16, nullptr,
+                                                     f16, l16, 5, f16, i16, i16, i16, nullptr) ==
+            GNNREC_EINVAL && err_has("null Z"),
+        "list count rating null Z");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_rating_f32(f16, 4, reinterpret_cast<float*>(8), 9, f16,
+                                                     f16, f16, f16, f16, f16, l16, 5, f16, i16,
+                                                     i16, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("16-byte aligned"),
+        "list count rating unaligned Q");
+  CHECK(gnnrec_rank_resolve_mlp_lists_f32(l16, l16, 3, f16, i16, i16, 5, 4, f16, f16, 9, f16, f16,
+                                          f16, f16, nullptr, nullptr, l16, nullptr, l16, f16,
+                                          nullptr) == GNNREC_EINVAL && err_has("come together"),
+        "list resolve indptr without indices");
+  CHECK(gnnrec_rank_resolve_mlp_lists_f32(l16, l16, 3, f16, i16, i16, 5, 4, f16, f16, 9, f16, f16,
+                                          f16, f16, nullptr, f16, nullptr, nullptr, l16, f16,
+                                          nullptr) == GNNREC_EINVAL && err_has("Z and p_col"),
+        "list resolve p_col without Z");
+  CHECK(gnnrec_rank_resolve_mlp_lists_f32(l16, l16, 3, f16, i16, i16, 49, 4, f16, f16, 9, f16,
+                                          f16, f16, f16, nullptr, nullptr, nullptr, nullptr, l16,
+                                          f16, nullptr) == GNNREC_EINVAL && err_has("bad size"),
+        "list resolve more slots than the rows hold");
+  CHECK(gnnrec_rank_resolve_mlp_lists_f32(l16, nullptr, 3, f16, i16, i16, 5, 4, f16, f16, 9, f16,
+                                          f16, f16, f16, nullptr, nullptr, nullptr, nullptr, l16,
+                                          f16, nullptr) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "list resolve null lptr");
+  CHECK(gnnrec_rank_resolve_mlp_lists_f32(nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 4,
+                                          nullptr, nullptr, 9, nullptr, nullptr, nullptr, nullptr,
+                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                          nullptr) == GNNREC_OK,
+        "list resolve no slots");
   // edge removal (csr_filter.hip): every refusal comes before the first memset or launch;
   // an empty problem still writes the status and indptr', so its host side is the
   // workspace query, which must give room for them

@@ -427,9 +427,25 @@ int launch_edge_mlp_lds(bool grouped, EdgeMlpArgs& a, hipStream_t s) {
 // count of a (row, tile) is the popcount of a ballot — wave-uniform — which lane 0 adds to
 // the row's int slot in the wave's LDS; after the chunk the slots go to part[chunk, row]
 // (int32) and fold_partials_i32_kernel sums them.  Integers: no order to fix, no atomics.
+//
+// The list forms of that evaluation, COUNT_L and COUNT_LR, share one scored row
+// among a user's held-out items.  A row r is a USER (or kDenseListSlots entries of a longer
+// list: the caller splits it over rows that repeat the user's P row); its entries are the
+// slots [lptr[r], lptr[r + 1]) of thr (the entry's own edge_mlp score) and gid (its item).
+// After a (row, tile) is scored, lane j loads slot j's threshold and item — for COUNT_LR the
+// threshold becomes rating(thr_j, Z[r], pcol[gid_j]) by the function that rates the items
+// (loading them before the row's 64 MFMAs spilled 360 B a lane around the MFMA chain) — and
+// a wave-uniform loop over the row's slots reads them back by v_readlane and counts, per
+// slot, COUNT's compare by ballot and popcount; lane j keeps slot j's count and
+// adds it to the slot's 16-bit counter in the wave's LDS (a chunk holds 1024 items: no
+// overflow), 64 rows x 16 slots x 2 B = the 2 KB a wave has left beside the image and the P
+// stage with two blocks on a CU.  After the chunk the counters go to part[chunk, slot].
 constexpr int kDenseZTiles = 32;  // item tiles (1024 items) per partial of the denominators
 enum DenseMode { kDenseStore = 0, kDenseFilter = 1, kDenseDenom = 2, kDenseStoreR = 3,
-                 kDenseFilterR = 4, kDenseCount = 5, kDenseCountR = 6 };
+                 kDenseFilterR = 4, kDenseCount = 5, kDenseCountR = 6, kDenseCountL = 7,
+                 kDenseCountLR = 8 };
+constexpr int kDenseListSlots = 16;  // COUNT_L / COUNT_LR: list entries per row, at most
+static_assert(kDenseZTiles * kMlpTile <= 65535, "a chunk's count fits a 16-bit counter");
 constexpr int kDenseUsers = 64;  // users scored per staged item tile, at most
 constexpr int kDenseStage = 4;   // users whose P rows are staged in LDS at a time
 constexpr int kDenseCandMax = 4096;  // candidate slots per row, at most (recommend.hip's)
@@ -453,8 +469,22 @@ struct DenseMlpArgs {
   float* part;          // DENOM: [chunks, n_users]
   int64_t n_tiles;      // DENOM / COUNT: item tiles
   const int* gid;       // COUNT / COUNT_R: the row's held-out item
-  int* ipart;           // COUNT / COUNT_R: [chunks, n_users]
+  int* ipart;           // COUNT / COUNT_R: [chunks, n_users]; COUNT_L / COUNT_LR: [chunks, n_slots]
+  const int64_t* lptr;  // COUNT_L / COUNT_LR: [n_users + 1], row r's slots of tau / gid
+  int64_t n_slots;
 };
+
+// The slots of list row u: its first slot in b0 and their number (wave-uniform where u is),
+// zero where the row's bounds do not lie inside [0, n_slots] or span more than
+// kDenseListSlots slots (out of contract: a row is never counted in part) — nothing is read or
+// written then.
+__device__ __forceinline__ int dense_list_slots(const int64_t* __restrict__ lptr, int64_t n_slots,
+                                                int64_t u, int64_t& b0) {
+  b0 = lptr[u];
+  const int64_t b1 = lptr[u + 1];
+  if (b0 < 0 || b1 > n_slots || b1 <= b0 || b1 - b0 > kDenseListSlots) return 0;
+  return (int)(b1 - b0);
+}
 
 // The P rows of users [u0, u0 + kDenseStage) as the stage holds them (row-major, 32 chunks a
 // row: contiguous in the table), lane l the chunks l and 64 + l; zero past u1.
@@ -470,16 +500,20 @@ __device__ __forceinline__ void dense_fetch_p(const float4* __restrict__ P4, int
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) {
   constexpr bool FILTER = MODE == kDenseFilter || MODE == kDenseFilterR;
-  constexpr bool RATING = MODE == kDenseStoreR || MODE == kDenseFilterR || MODE == kDenseCountR;
+  constexpr bool RATING = MODE == kDenseStoreR || MODE == kDenseFilterR ||
+                          MODE == kDenseCountR || MODE == kDenseCountLR;
   constexpr bool DENOM = MODE == kDenseDenom;
   constexpr bool COUNT = MODE == kDenseCount || MODE == kDenseCountR;
-  constexpr bool CHUNKED = DENOM || COUNT;  // a work item walks a chunk of tiles
+  constexpr bool LISTS = MODE == kDenseCountL || MODE == kDenseCountLR;
+  constexpr bool CHUNKED = DENOM || COUNT || LISTS;  // a work item walks a chunk of tiles
   __shared__ float4 image[kMlpWaves][kMlpTile * 32];     // 16 KB per wave
   __shared__ float4 pstage[kMlpWaves][kDenseStage * 32];  // 2 KB per wave
   __shared__ float zsum[kMlpWaves][DENOM ? kDenseUsers : 1];  // DENOM: the group's sums
   __shared__ int csum[kMlpWaves][COUNT ? kDenseUsers : 1];    // COUNT: the group's counts,
   __shared__ float cthr[kMlpWaves][COUNT ? kDenseUsers : 1];  //   thresholds
   __shared__ int cgid[kMlpWaves][COUNT ? kDenseUsers : 1];    //   and held-out items
+  // LISTS: the group's slot counters, [row][slot], two to a word
+  __shared__ unsigned short lsum[kMlpWaves][LISTS ? kDenseUsers * kDenseListSlots : 2];
   static_assert(kDenseStage * 32 == 2 * kWave, "a stage is two chunks per lane");
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
@@ -515,6 +549,11 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) 
       csum[wv][lane] = 0;
       cthr[wv][lane] = tl;
       cgid[wv][lane] = gl;
+    }
+    if constexpr (LISTS) {
+      unsigned* z = reinterpret_cast<unsigned*>(lsum[wv]);
+#pragma unroll
+      for (int k = 0; k < kDenseUsers * kDenseListSlots / 2 / kWave; ++k) z[k * kWave + lane] = 0u;
     }
     // one item tile for the group's users (the body stays at the loop's indentation); a
     // lambda, called once outside DENOM: as a loop with one trip the store and filter forms
@@ -564,10 +603,35 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) 
         }
         float sc = mlp_tile_score<true>(a.m, S, w, pc, r, h, b3v);
         if constexpr (RATING) sc = rating(sc, zu, pv);
+        int ns = 0;  // LISTS: the row's slots, lane j holding slot j's threshold and item
+        if constexpr (LISTS) {
+          int64_t b0;
+          ns = __builtin_amdgcn_readfirstlane(dense_list_slots(a.lptr, a.n_slots, u, b0));
+          if (lane < ns) {
+            thr = a.tau[b0 + lane];
+            gu = a.gid[b0 + lane];
+            if constexpr (RATING)
+              thr = rating(thr, zu, gu >= 0 && gu < a.n_cols ? a.pcol[gu] : 0.f);
+          }
+        }
         if constexpr (COUNT) {
           const bool ahead = h == 0 && v >= 0 && v != gu && (sc > thr || (sc == thr && v < gu));
           const int n_ahead = __popcll(__ballot(ahead));  // wave-uniform
           if (lane == 0) csum[wv][u - u_beg] += n_ahead;
+        } else if constexpr (LISTS) {
+          int mine = 0;
+          const bool live = h == 0 && v >= 0;
+          for (int sl = 0; sl < ns; ++sl) {  // wave-uniform
+            const float tj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(thr), sl));
+            const int gj = __builtin_amdgcn_readlane(gu, sl);
+            // COUNT's compare, its terms combined without branches (| and & on bools: every
+            // term is a lane mask, and a short-circuit form compiled to two branches a slot)
+            const bool ahead = live & (v != gj) & ((sc > tj) | ((sc == tj) & (v < gj)));
+            const int n_ahead = __popcll(__ballot(ahead));
+            mine = lane == sl ? n_ahead : mine;
+          }
+          // lane j alone touches (row, slot j)'s counter, in every tile of the chunk
+          if (lane < ns) lsum[wv][(u - u_beg) * kDenseListSlots + lane] += (unsigned short)mine;
         } else if constexpr (DENOM) {
           float x = (h == 0 && v >= 0) ? expf(sc) : 0.f;
 #pragma unroll
@@ -596,7 +660,24 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) 
     } else {
       score_tile(t0);
     }
-    if constexpr (CHUNKED) {
+    if constexpr (LISTS) {
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the slot lanes' counts are visible
+      static_assert(kWave % kDenseListSlots == 0, "a wave writes whole rows of counters");
+      constexpr int kRows = kWave / kDenseListSlots;  // rows written at a time
+      const int64_t u_beg = g * a.per_group;
+      const int64_t u1 = min<int64_t>(a.n_users, u_beg + a.per_group);
+      const int j = lane % kDenseListSlots;
+      for (int64_t ub = u_beg; ub < u1; ub += kRows) {  // wave-uniform
+        const int64_t u = ub + lane / kDenseListSlots;
+        if (u < u1) {
+          int64_t b0;
+          const int ns = dense_list_slots(a.lptr, a.n_slots, u, b0);
+          if (j < ns)
+            a.ipart[t0 * a.n_slots + b0 + j] = lsum[wv][(u - u_beg) * kDenseListSlots + j];
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    } else if constexpr (CHUNKED) {
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // lane 0's sums are visible
       const int64_t u = g * a.per_group + lane;
       if (lane < a.per_group && u < a.n_users) {
@@ -625,7 +706,8 @@ int launch_edge_mlp_dense(int mode, const char* fn, DenseMlpArgs& a, hipStream_t
   a.groups = (a.n_users + kDenseUsers - 1) / kDenseUsers;
   a.per_group = (a.n_users + a.groups - 1) / a.groups;
   a.n_tiles = (a.n_cols + kMlpTile - 1) / kMlpTile;
-  const bool chunked = mode == kDenseDenom || mode == kDenseCount || mode == kDenseCountR;
+  const bool chunked = mode == kDenseDenom || mode == kDenseCount || mode == kDenseCountR ||
+                       mode == kDenseCountL || mode == kDenseCountLR;
   a.work = (chunked ? (a.n_tiles + kDenseZTiles - 1) / kDenseZTiles : a.n_tiles) * a.groups;
   int64_t blocks = (a.work + kMlpWaves - 1) / kMlpWaves;
   if (blocks > kMlpResidentWaves / kMlpWaves) blocks = kMlpResidentWaves / kMlpWaves;
@@ -637,6 +719,8 @@ int launch_edge_mlp_dense(int mode, const char* fn, DenseMlpArgs& a, hipStream_t
   else if (mode == kDenseStoreR) GNNREC_LAUNCH_DENSE(kDenseStoreR);
   else if (mode == kDenseCount) GNNREC_LAUNCH_DENSE(kDenseCount);
   else if (mode == kDenseCountR) GNNREC_LAUNCH_DENSE(kDenseCountR);
+  else if (mode == kDenseCountL) GNNREC_LAUNCH_DENSE(kDenseCountL);
+  else if (mode == kDenseCountLR) GNNREC_LAUNCH_DENSE(kDenseCountLR);
   else GNNREC_LAUNCH_DENSE(kDenseFilterR);
 #undef GNNREC_LAUNCH_DENSE
   return check_launch(fn);
@@ -648,6 +732,15 @@ int launch_dense_count(int mode, const char* fn, DenseMlpArgs& a, int32_t* ahead
   if (rc != GNNREC_OK) return rc;
   return launch_fold_partials_i32(fn, a.ipart, (a.n_tiles + kDenseZTiles - 1) / kDenseZTiles,
                                   a.n_users, ahead, s);
+}
+
+// The list forms' launch, then the fold of the slots' partials into ahead.
+int launch_dense_count_lists(int mode, const char* fn, DenseMlpArgs& a, int32_t* ahead,
+                             hipStream_t s) {
+  const int rc = launch_edge_mlp_dense(mode, fn, a, s);
+  if (rc != GNNREC_OK) return rc;
+  return launch_fold_partials_i32(fn, a.ipart, (a.n_tiles + kDenseZTiles - 1) / kDenseZTiles,
+                                  a.n_slots, ahead, s);
 }
 
 // ------------------------------------------------- rank resolve, MLP head ----
@@ -724,6 +817,96 @@ __global__ __launch_bounds__(256) void rank_resolve_mlp_kernel(
   }
   const bool any_excluded = __ballot(excluded) != 0;
   if (lane == 0) rank[b] = any_excluded ? 0 : 1 + (int64_t)ahead[b] - behind;
+}
+
+// The list form: one wave per list row — a user, or kDenseListSlots entries of
+// a longer list — of the count pass's row plan: P row b, slots [lptr[b], lptr[b + 1]) of sraw /
+// gid / ahead, row_user[b] the user whose exclusion row is walked.  That row is walked ONCE: a
+// tile of 32 entries is staged and scored once, as above, and a wave-uniform loop over the
+// row's slots (lane j holds slot j's threshold and item, read back by v_readlane) counts the
+// entries exactly ahead of each slot and notes a slot whose item is among them; lane j keeps
+// slot j's two results and writes rank and vals of its slot.  A slot whose item is out of
+// range, and a row whose user is, are left unwritten.
+template <bool RATING>
+__global__ __launch_bounds__(256) void rank_resolve_mlp_lists_kernel(
+    EdgeMlpArgs m, const int64_t* __restrict__ row_user, const int64_t* __restrict__ lptr,
+    int64_t n_rows, const float* __restrict__ sraw, const int* __restrict__ gid,
+    const int* __restrict__ ahead, int64_t n_slots, int64_t n_users, int64_t n_cols,
+    const float* __restrict__ Z, const float* __restrict__ pcol,
+    const int64_t* __restrict__ ex_ptr, const int32_t* __restrict__ ex_idx,
+    int64_t* __restrict__ rank, float* __restrict__ vals) {
+  __shared__ float4 image[kMlpWaves][kMlpTile * 32];  // 16 KB per wave
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int r = lane & 31;
+  const int h = lane >> 5;
+  const int64_t b = (int64_t)blockIdx.x * kMlpWaves + wv;
+  if (b >= n_rows) return;  // wave-uniform, as every exit below; no block-wide barrier follows
+  const int64_t u = row_user[b];
+  int64_t b0;
+  const int ns = __builtin_amdgcn_readfirstlane(dense_list_slots(lptr, n_slots, b, b0));
+  if (u < 0 || u >= n_users || ns == 0) return;
+  float4* S = image[wv];
+  const float4* P4 = reinterpret_cast<const float4*>(m.P);
+  const float4* Q4 = reinterpret_cast<const float4*>(m.Q);
+  float zb = 1.f;
+  if constexpr (RATING) zb = Z[b];
+  float t = 0.f;  // lane j: slot j's threshold and item
+  int g = -1;
+  if (lane < ns) {
+    t = sraw[b0 + lane];
+    g = gid[b0 + lane];
+    if (g < 0 || g >= n_cols) g = -1;
+    if constexpr (RATING) t = rating(t, zb, g >= 0 ? pcol[g] : 0.f);
+  }
+  int behind = 0;  // lane j: the excluded items exactly ahead of slot j
+  bool excluded = false;
+  if (ex_ptr) {
+    const int64_t e0 = ex_ptr[u], e1 = ex_ptr[u + 1];
+    if (e0 < e1) {
+      float4 w[16], pc[16];
+      mlp_load_w2(m, r, h, w);
+      const float b3v = m.b3[0];
+#pragma unroll
+      for (int c = 0; c < 16; ++c) pc[c] = P4[b * 32 + 16 * h + c];  // the row's P row
+      for (int64_t base = e0; base < e1; base += kMlpTile) {  // wave-uniform bound
+        const int64_t e = base + r;
+        const int64_t c = e < e1 ? ex_idx[e] : -1;  // -1: a repeat or an id past the table
+        const int v = c >= 0 && c < n_cols ? (int)c : -1;
+        float pv = 0.f;
+        if constexpr (RATING) pv = v >= 0 ? pcol[v] : 0.f;
+        // the previous tile's reads of the image are done before it is overwritten
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+          float4 q[8], p[8];
+          mlp_load<true, 8>(Q4, P4, v, 0, r, h, 8 * half, q, p);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) S[(2 * (8 * half + i) + h) * 32 + r] = q[i];
+        }
+        // the staging stores are visible to the MFMA-layout reads (lane r reads row r)
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        float sc = mlp_tile_score<true>(m, S, w, pc, r, h, b3v);
+        if constexpr (RATING) sc = rating(sc, zb, pv);
+        for (int j = 0; j < ns; ++j) {  // wave-uniform
+          const float tj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), j));
+          const int gj = __builtin_amdgcn_readlane(g, j);
+          const bool hit = __ballot((v >= 0) & (v == gj)) != 0;
+          const bool is_ahead =
+              (h == 0) & (v >= 0) & (v != gj) & ((sc > tj) | ((sc == tj) & (v < gj)));
+          const int n_ahead = __popcll(__ballot(is_ahead));
+          if (lane == j) {
+            behind += n_ahead;
+            excluded |= hit;
+          }
+        }
+      }
+    }
+  }
+  if (lane < ns && g >= 0) {
+    vals[b0 + lane] = t;
+    rank[b0 + lane] = excluded ? 0 : 1 + (int64_t)ahead[b0 + lane] - behind;
+  }
 }
 
 }  // namespace
@@ -1001,5 +1184,106 @@ extern "C" int gnnrec_rank_resolve_mlp_f32(const int64_t* users, const int64_t* 
     hipLaunchKernelGGL(rank_resolve_mlp_kernel<false>, grid, block, 0, st, m, users, items, s,
                        ahead, n_pairs, n_users, n_items, Z, p_col, exclude_indptr,
                        exclude_indices, rank, vals);
+  return check_launch(fn);
+}
+
+// ---- the list forms of the full-ranking evaluation ----
+extern "C" int64_t gnnrec_rank_list_slots(void) { return gnnrec::kDenseListSlots; }
+
+// the slot operands of a list count pass, after check_dense; as dense_count_operands
+static int dense_count_lists_operands(const char* fn, int64_t n_rows, int64_t n_items,
+                                      const void* lptr, int64_t n_slots, const void* thr,
+                                      const void* gid, const void* parts, int32_t* ahead,
+                                      void* stream, bool* empty) {
+  using namespace gnnrec;
+  GNNREC_REQUIRE(n_slots >= 0 && (n_slots + 255) / 256 < (int64_t(1) << 31) &&
+                     n_slots <= n_rows * kDenseListSlots,
+                 "%s: n_slots must be in [0, %d n_rows] (got %lld for %lld rows)", fn,
+                 kDenseListSlots, (long long)n_slots, (long long)n_rows);
+  *empty = n_slots == 0 || n_items == 0;
+  if (n_slots == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(ahead, "%s: null ahead", fn);
+  if (n_items == 0) {
+    const hipError_t e = hipMemsetAsync(ahead, 0, (size_t)n_slots * sizeof(int32_t),
+                                        as_stream(stream));
+    GNNREC_REQUIRE(e == hipSuccess, "%s: %s", fn, hipGetErrorString(e));
+    return GNNREC_OK;
+  }
+  GNNREC_REQUIRE(lptr && thr && gid && parts, "%s: null lptr / thr / gid / parts", fn);
+  return GNNREC_OK;
+}
+
+extern "C" int gnnrec_edge_mlp_dense_count_lists_f32(
+    const float* P, int64_t n_rows, const float* Q, int64_t n_items, const float* W2,
+    const float* b2, const float* w3, const float* b3, const int64_t* lptr, int64_t n_slots,
+    const float* thr, const int32_t* gid, int32_t* parts, int32_t* ahead, void* stream) {
+  using namespace gnnrec;
+  const char* fn = "gnnrec_edge_mlp_dense_count_lists_f32";
+  int rc = check_dense(fn, P, n_rows, Q, n_items, W2, b2, w3, b3);
+  if (rc != GNNREC_OK) return rc;
+  bool empty;
+  rc = dense_count_lists_operands(fn, n_rows, n_items, lptr, n_slots, thr, gid, parts, ahead,
+                                  stream, &empty);
+  if (rc != GNNREC_OK || empty) return rc;
+  DenseMlpArgs a{};
+  a.m.P = P; a.m.Q = Q; a.m.W2 = W2; a.m.b2 = b2; a.m.w3 = w3; a.m.b3 = b3;
+  a.n_users = n_rows; a.n_cols = n_items;
+  a.tau = thr; a.gid = gid; a.ipart = parts; a.lptr = lptr; a.n_slots = n_slots;
+  return launch_dense_count_lists(kDenseCountL, fn, a, ahead, as_stream(stream));
+}
+
+extern "C" int gnnrec_edge_mlp_dense_count_lists_rating_f32(
+    const float* P, int64_t n_rows, const float* Q, int64_t n_items, const float* W2,
+    const float* b2, const float* w3, const float* b3, const float* Z, const float* p_col,
+    const int64_t* lptr, int64_t n_slots, const float* s, const int32_t* gid, int32_t* parts,
+    int32_t* ahead, void* stream) {
+  using namespace gnnrec;
+  const char* fn = "gnnrec_edge_mlp_dense_count_lists_rating_f32";
+  int rc = check_dense(fn, P, n_rows, Q, n_items, W2, b2, w3, b3);
+  if (rc != GNNREC_OK) return rc;
+  bool empty;
+  rc = dense_count_lists_operands(fn, n_rows, n_items, lptr, n_slots, s, gid, parts, ahead,
+                                  stream, &empty);
+  if (rc != GNNREC_OK || empty) return rc;
+  GNNREC_REQUIRE(Z && p_col, "%s: null Z / p_col", fn);
+  DenseMlpArgs a{};
+  a.m.P = P; a.m.Q = Q; a.m.W2 = W2; a.m.b2 = b2; a.m.w3 = w3; a.m.b3 = b3;
+  a.n_users = n_rows; a.n_cols = n_items;
+  a.tau = s; a.gid = gid; a.ipart = parts; a.Z = Z; a.pcol = p_col;
+  a.lptr = lptr; a.n_slots = n_slots;
+  return launch_dense_count_lists(kDenseCountLR, fn, a, ahead, as_stream(stream));
+}
+
+extern "C" int gnnrec_rank_resolve_mlp_lists_f32(
+    const int64_t* row_user, const int64_t* lptr, int64_t n_rows, const float* s,
+    const int32_t* gid, const int32_t* ahead, int64_t n_slots, int64_t n_users, const float* P,
+    const float* Q, int64_t n_items, const float* W2, const float* b2, const float* w3,
+    const float* b3, const float* Z, const float* p_col, const int64_t* exclude_indptr,
+    const int32_t* exclude_indices, int64_t* rank, float* vals, void* stream) {
+  using namespace gnnrec;
+  const char* fn = "gnnrec_rank_resolve_mlp_lists_f32";
+  GNNREC_REQUIRE(n_rows >= 0 && (n_rows + kMlpWaves - 1) / kMlpWaves < (int64_t(1) << 31) &&
+                     n_users >= 0 && n_slots >= 0 && n_slots <= n_rows * kDenseListSlots,
+                 "%s: bad size", fn);
+  const int rc = check_dense(fn, P, n_rows, Q, n_items, W2, b2, w3, b3);
+  if (rc != GNNREC_OK) return rc;
+  GNNREC_REQUIRE(!exclude_indptr == !exclude_indices,
+                 "%s: exclusion indptr and indices come together", fn);
+  GNNREC_REQUIRE(!Z == !p_col, "%s: Z and p_col come together", fn);
+  if (n_slots == 0) return GNNREC_OK;
+  GNNREC_REQUIRE(n_items > 0 && n_users > 0, "%s: entries without users or items", fn);
+  GNNREC_REQUIRE(row_user && lptr && s && gid && ahead && rank && vals, "%s: null pointer", fn);
+  EdgeMlpArgs m{};
+  m.P = P; m.Q = Q; m.W2 = W2; m.b2 = b2; m.w3 = w3; m.b3 = b3;
+  const dim3 grid((unsigned)((n_rows + kMlpWaves - 1) / kMlpWaves)), block(256);
+  hipStream_t st = as_stream(stream);
+  if (Z)
+    hipLaunchKernelGGL(rank_resolve_mlp_lists_kernel<true>, grid, block, 0, st, m, row_user, lptr,
+                       n_rows, s, gid, ahead, n_slots, n_users, n_items, Z, p_col,
+                       exclude_indptr, exclude_indices, rank, vals);
+  else
+    hipLaunchKernelGGL(rank_resolve_mlp_lists_kernel<false>, grid, block, 0, st, m, row_user, lptr,
+                       n_rows, s, gid, ahead, n_slots, n_users, n_items, Z, p_col,
+                       exclude_indptr, exclude_indices, rank, vals);
   return check_launch(fn);
 }

@@ -1457,6 +1457,117 @@ void rank_resolve_mlp(const Tensor& users, const Tensor& items, const Tensor& s,
      "gnnrec_rank_resolve_mlp_f32");
 }
 
+// ------------------------------------------------ f1f for the MLP head, the list forms
+// the slot operands of a list count pass over B rows and n items -> nothing; all checked
+void dense_count_slots(const Tensor& lptr, const Tensor& thr, const Tensor& gid,
+                       const Tensor& parts, const Tensor& ahead, int64_t B, int64_t n) {
+  dev(lptr, "lptr", at::kLong);
+  TORCH_CHECK_VALUE(lptr.numel() == B + 1 && lptr.is_contiguous(), "lptr must be contiguous [",
+                    B + 1, "], got ", lptr.sizes());
+  const int64_t E = thr.numel();
+  TORCH_CHECK_VALUE(E <= B * gnnrec_rank_list_slots(), "at most ", gnnrec_rank_list_slots(),
+                    " slots a row: ", E, " slots for ", B, " rows");
+  rating_vec(thr, "thr", E);
+  dev(gid, "gid", at::kInt);
+  dev(parts, "parts", at::kInt);
+  dev(ahead, "ahead", at::kInt);
+  TORCH_CHECK_VALUE(gid.numel() == E && ahead.numel() == E && gid.is_contiguous() &&
+                        ahead.is_contiguous(),
+                    "gid / ahead must be contiguous [", E, "]");
+  const int64_t n_part = gnnrec_cos_denominator_parts(n);
+  TORCH_CHECK_VALUE(parts.dim() == 2 && parts.size(0) == n_part && parts.size(1) == E &&
+                        parts.is_contiguous(),
+                    "parts must be a contiguous [", n_part, ", ", E, "], got ", parts.sizes());
+}
+
+void edge_mlp_dense_count_lists(const Tensor& P, const Tensor& Q, const Tensor& W2,
+                                const Tensor& b2, const Tensor& w3, const Tensor& b3,
+                                const Tensor& lptr, const Tensor& thr, const Tensor& gid,
+                                Tensor& parts, Tensor& ahead) {
+  const OneDevice one_device_;
+  dense_mlp_tables(P, Q, W2, b2, w3, b3);
+  const int64_t B = P.size(0), n = Q.size(0);
+  dense_count_slots(lptr, thr, gid, parts, ahead, B, n);
+  if (meta(P)) return;
+  const c10::DeviceGuard g(P.device());
+  ck(gnnrec_edge_mlp_dense_count_lists_f32(p<float>(P), B, p<float>(Q), n, p<float>(W2),
+                                           p<float>(b2), p<float>(w3), p<float>(b3),
+                                           p<int64_t>(lptr), thr.numel(), p<float>(thr),
+                                           p<int32_t>(gid), p<int32_t>(parts), p<int32_t>(ahead),
+                                           stream_of(P)),
+     "gnnrec_edge_mlp_dense_count_lists_f32");
+}
+
+void edge_mlp_dense_count_lists_rating(const Tensor& P, const Tensor& Q, const Tensor& W2,
+                                       const Tensor& b2, const Tensor& w3, const Tensor& b3,
+                                       const Tensor& Z, const Tensor& p_col, const Tensor& lptr,
+                                       const Tensor& s, const Tensor& gid, Tensor& parts,
+                                       Tensor& ahead) {
+  const OneDevice one_device_;
+  dense_mlp_tables(P, Q, W2, b2, w3, b3);
+  const int64_t B = P.size(0), n = Q.size(0);
+  rating_vec(Z, "Z", B);
+  rating_vec(p_col, "p_col", n);
+  dense_count_slots(lptr, s, gid, parts, ahead, B, n);
+  if (meta(P)) return;
+  const c10::DeviceGuard g(P.device());
+  ck(gnnrec_edge_mlp_dense_count_lists_rating_f32(
+         p<float>(P), B, p<float>(Q), n, p<float>(W2), p<float>(b2), p<float>(w3), p<float>(b3),
+         p<float>(Z), p<float>(p_col), p<int64_t>(lptr), s.numel(), p<float>(s), p<int32_t>(gid),
+         p<int32_t>(parts), p<int32_t>(ahead), stream_of(P)),
+     "gnnrec_edge_mlp_dense_count_lists_rating_f32");
+}
+
+void rank_resolve_mlp_lists(const Tensor& row_user, const Tensor& lptr, const Tensor& s,
+                            const Tensor& gid, const Tensor& ahead, int64_t n_users,
+                            const Tensor& P, const Tensor& Q, const Tensor& W2, const Tensor& b2,
+                            const Tensor& w3, const Tensor& b3, const optional<Tensor>& Z,
+                            const optional<Tensor>& p_col, const optional<Tensor>& exclude_indptr,
+                            const optional<Tensor>& exclude_indices, Tensor& rank, Tensor& vals) {
+  const OneDevice one_device_;
+  dev(row_user, "row_user", at::kLong);
+  dev(lptr, "lptr", at::kLong);
+  dense_mlp_tables(P, Q, W2, b2, w3, b3);
+  dev(gid, "gid", at::kInt);
+  dev(ahead, "ahead", at::kInt);
+  dev(exclude_indptr, "exclude_indptr", at::kLong);
+  dev(exclude_indices, "exclude_indices", at::kInt);
+  dev(rank, "rank", at::kLong);
+  const int64_t B = row_user.numel(), E = s.numel(), n = Q.size(0);
+  rating_vec(s, "s", E);
+  rating_vec(vals, "vals", E);
+  TORCH_CHECK_VALUE(P.size(0) == B, "P must hold one row per list row: [", B, ", 128], got ",
+                    P.sizes());
+  TORCH_CHECK_VALUE(lptr.numel() == B + 1 && lptr.is_contiguous() && row_user.is_contiguous(),
+                    "row_user / lptr must be contiguous [", B, "] / [", B + 1, "]");
+  TORCH_CHECK_VALUE(E <= B * gnnrec_rank_list_slots(), "at most ", gnnrec_rank_list_slots(),
+                    " slots a row: ", E, " slots for ", B, " rows");
+  TORCH_CHECK_VALUE(gid.numel() == E && ahead.numel() == E && rank.numel() == E &&
+                        gid.is_contiguous() && ahead.is_contiguous() && rank.is_contiguous(),
+                    "gid / ahead / rank must be contiguous [", E, "]");
+  TORCH_CHECK_VALUE(n_users >= 0 && (E == 0 || (n_users > 0 && n > 0)),
+                    "entries need users and items (n_users = ", n_users, ", n_items = ", n, ")");
+  TORCH_CHECK_VALUE(has(Z) == has(p_col), "Z and p_col come together");
+  if (has(Z)) {
+    rating_vec(*Z, "Z", B);
+    rating_vec(*p_col, "p_col", n);
+  }
+  TORCH_CHECK_VALUE(has(exclude_indptr) == has(exclude_indices),
+                    "exclude_indptr and exclude_indices come together");
+  TORCH_CHECK_VALUE(!has(exclude_indptr) ||
+                        (exclude_indptr->numel() == n_users + 1 &&
+                         exclude_indptr->is_contiguous() && exclude_indices->is_contiguous()),
+                    "exclude_indptr must be a contiguous [n_users + 1]");
+  if (meta(row_user)) return;
+  const c10::DeviceGuard g(row_user.device());
+  ck(gnnrec_rank_resolve_mlp_lists_f32(
+         p<int64_t>(row_user), p<int64_t>(lptr), B, p<float>(s), p<int32_t>(gid),
+         p<int32_t>(ahead), E, n_users, p<float>(P), p<float>(Q), n, p<float>(W2), p<float>(b2),
+         p<float>(w3), p<float>(b3), p<float>(Z), p<float>(p_col), p<int64_t>(exclude_indptr),
+         p<int32_t>(exclude_indices), p<int64_t>(rank), p<float>(vals), stream_of(row_user)),
+     "gnnrec_rank_resolve_mlp_lists_f32");
+}
+
 void topk_scored_candidates_f32(const Tensor& counts, const Tensor& cand_items,
                                 const Tensor& cand_scores, const optional<Tensor>& user_rows,
                                 const optional<Tensor>& exclude_indptr,
@@ -2518,6 +2629,7 @@ int64_t csr_build_workspace_bytes(int64_t E, int64_t n_dst) {
 }
 int64_t cos_denominator_parts(int64_t n_items) { return gnnrec_cos_denominator_parts(n_items); }
 double rank_eps(int64_t d) { return gnnrec_rank_eps(d); }
+int64_t rank_list_slots() { return gnnrec_rank_list_slots(); }
 int64_t csr_remove_edges_workspace_bytes(int64_t E, int64_t n_dst) {
   return (int64_t)gnnrec_csr_remove_edges_workspace_bytes(E, n_dst);
 }
@@ -2637,6 +2749,16 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor? Z, "
         "Tensor? p_col, Tensor? exclude_indptr, Tensor? exclude_indices, Tensor(a!) rank, "
         "Tensor(b!) vals) -> ()");
+  m.def("edge_mlp_dense_count_lists_f32(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, "
+        "Tensor b3, Tensor lptr, Tensor thr, Tensor gid, Tensor(a!) parts, Tensor(b!) ahead) "
+        "-> ()");
+  m.def("edge_mlp_dense_count_lists_rating_f32(Tensor P, Tensor Q, Tensor W2, Tensor b2, "
+        "Tensor w3, Tensor b3, Tensor Z, Tensor p_col, Tensor lptr, Tensor s, Tensor gid, "
+        "Tensor(a!) parts, Tensor(b!) ahead) -> ()");
+  m.def("rank_resolve_mlp_lists_f32(Tensor row_user, Tensor lptr, Tensor s, Tensor gid, "
+        "Tensor ahead, int n_users, Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, "
+        "Tensor b3, Tensor? Z, Tensor? p_col, Tensor? exclude_indptr, Tensor? exclude_indices, "
+        "Tensor(a!) rank, Tensor(b!) vals) -> ()");
   m.def("normalize_rows_f32(Tensor x, Tensor? row_map, Tensor(a!) out) -> ()");
   m.def("cos_denominators_f32(Tensor users, Tensor items, Tensor(a!) parts, Tensor(b!) Z) -> ()");
   m.def("cos_scores_f32(Tensor users, Tensor items, Tensor(a!) out) -> ()");
@@ -2742,6 +2864,7 @@ TORCH_LIBRARY(gnnrec, m) {
   m.def("csr_build_workspace_bytes(int n_edges, int n_dst) -> int", &csr_build_workspace_bytes);
   m.def("cos_denominator_parts(int n_items) -> int", &cos_denominator_parts);
   m.def("rank_eps(int d) -> float", &rank_eps);
+  m.def("rank_list_slots() -> int", &rank_list_slots);
   m.def("csr_remove_edges_workspace_bytes(int n_edges, int n_dst) -> int",
         &csr_remove_edges_workspace_bytes);
   m.def("csr_add_edges_workspace_bytes(int n_new, int n_dst) -> int",
@@ -2790,6 +2913,9 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("edge_mlp_dense_count_f32", &edge_mlp_dense_count); \
   m.impl("edge_mlp_dense_count_rating_f32", &edge_mlp_dense_count_rating); \
   m.impl("rank_resolve_mlp_f32", &rank_resolve_mlp);     \
+  m.impl("edge_mlp_dense_count_lists_f32", &edge_mlp_dense_count_lists); \
+  m.impl("edge_mlp_dense_count_lists_rating_f32", &edge_mlp_dense_count_lists_rating); \
+  m.impl("rank_resolve_mlp_lists_f32", &rank_resolve_mlp_lists); \
   m.impl("normalize_rows_f32", &normalize_rows_f32);     \
   m.impl("cos_denominators_f32", &cos_denominators);         \
   m.impl("cos_scores_f32", &cos_scores);                     \

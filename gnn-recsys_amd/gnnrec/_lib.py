@@ -205,6 +205,15 @@ SIGNATURES = {
                                                       _P, _P, _P, _P, _P]),
     "gnnrec_rank_resolve_mlp_f32": (_INT, [_P, _P, _P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P,
                                            _P, _P, _P, _P, _P, _P, _P, _P]),
+    # its list forms: one scored row per user (csrc/heads.hip)
+    "gnnrec_rank_list_slots": (_I64, []),
+    "gnnrec_edge_mlp_dense_count_lists_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64,
+                                                     _P, _P, _P, _P, _P]),
+    "gnnrec_edge_mlp_dense_count_lists_rating_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P,
+                                                            _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "gnnrec_rank_resolve_mlp_lists_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _I64, _I64, _P, _P,
+                                                 _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                 _P]),
     "gnnrec_exp_rowsum_f32": (_INT, [_P, _I64, _I64, _I64, _P, _P]),
     "gnnrec_rating_rows_f32": (_INT, [_P, _I64, _I64, _I64, _P, _P, _P]),
     "gnnrec_rating_thresholds_f32": (_INT, [_P, _P, _P, _I64, _P, _P]),

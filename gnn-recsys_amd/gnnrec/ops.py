@@ -2260,6 +2260,84 @@ def rank_resolve_mlp(users: torch.Tensor, items: torch.Tensor, s: torch.Tensor,
     return out, vals
 
 
+# ---- the list forms: one scored row per user (csrc/heads.hip) ----
+def rank_list_slots() -> int:
+    """List entries a row of the list count pass holds at most (kDenseListSlots); a longer
+    list is split over rows that repeat the user's P row."""
+    return int(_T().rank_list_slots())
+
+
+def _count_slots(Q, lptr, s, gid):
+    _dev(lptr, "lptr", torch.int64)
+    _dev(s, "thr", torch.float32)
+    _dev(gid, "gid", torch.int32)
+    E = s.numel()
+    parts = torch.empty((denominator_parts(Q.shape[0]), E), dtype=torch.int32, device=Q.device)
+    ahead = torch.empty(E, dtype=torch.int32, device=Q.device)
+    return parts, ahead
+
+
+def edge_mlp_dense_count_lists(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor,
+                               b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor,
+                               lptr: torch.Tensor, thr: torch.Tensor,
+                               gid: torch.Tensor) -> torch.Tensor:
+    """edge_mlp_dense_count with one scored row for several entries: row r of P [R, 128] (a
+    user, or rank_list_slots() entries of a longer list) owns the slots [lptr[r], lptr[r + 1])
+    (int64 [R + 1], at most rank_list_slots() a row) of thr (the entry's own edge_mlp score)
+    and gid (its item, int32) -> ahead int32 [E], per slot the count edge_mlp_dense_count gives
+    the pair (row, gid)."""
+    ops = _dense_mlp_operands(P, Q, W2, b2, w3, b3)
+    parts, ahead = _count_slots(Q, lptr, thr, gid)
+    _T().edge_mlp_dense_count_lists_f32(*ops, lptr, thr, gid, parts, ahead)
+    return ahead
+
+
+def edge_mlp_dense_count_lists_rating(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor,
+                                      b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor,
+                                      Z: torch.Tensor, p_col: torch.Tensor, lptr: torch.Tensor,
+                                      s: torch.Tensor, gid: torch.Tensor) -> torch.Tensor:
+    """edge_mlp_dense_count_lists on R = expf(score) / Z[r] + p_col[v] (Z per ROW); slot j's
+    threshold is its own R, formed in the kernel from its raw score s[j] by the same function."""
+    ops = _dense_mlp_operands(P, Q, W2, b2, w3, b3)
+    _dev(Z, "Z", torch.float32)
+    _dev(p_col, "p_col", torch.float32)
+    parts, ahead = _count_slots(Q, lptr, s, gid)
+    _T().edge_mlp_dense_count_lists_rating_f32(*ops, Z, p_col, lptr, s, gid, parts, ahead)
+    return ahead
+
+
+def rank_resolve_mlp_lists(row_user: torch.Tensor, lptr: torch.Tensor, s: torch.Tensor,
+                           gid: torch.Tensor, ahead: torch.Tensor, n_users: int,
+                           P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor,
+                           w3: torch.Tensor, b3: torch.Tensor,
+                           exclude_indptr: Optional[torch.Tensor] = None,
+                           exclude_indices: Optional[torch.Tensor] = None,
+                           Z: Optional[torch.Tensor] = None,
+                           p_col: Optional[torch.Tensor] = None,
+                           out: Optional[torch.Tensor] = None,
+                           vals: Optional[torch.Tensor] = None):
+    """rank_resolve_mlp for the rows of a list count pass: row r (P row r, user row_user[r],
+    slots [lptr[r], lptr[r + 1]) of s / gid / ahead) walks its user's exclusion row once and
+    resolves every slot from the same scores -> (rank int64 [E], vals fp32 [E]); Z is per row."""
+    _dev(row_user, "row_user", torch.int64)
+    _dev(lptr, "lptr", torch.int64)
+    _dev(s, "s", torch.float32)
+    _dev(gid, "gid", torch.int32)
+    _dev(ahead, "ahead", torch.int32)
+    ops = _dense_mlp_operands(P, Q, W2, b2, w3, b3)
+    if Z is not None:
+        _dev(Z, "Z", torch.float32)
+    if p_col is not None:
+        _dev(p_col, "p_col", torch.float32)
+    if out is None:
+        out = torch.empty(s.numel(), dtype=torch.int64, device=s.device)
+    if vals is None:
+        vals = torch.empty(s.numel(), dtype=torch.float32, device=s.device)
+    _T().rank_resolve_mlp_lists_f32(row_user, lptr, s, gid, ahead, int(n_users), *ops, Z, p_col,
+                                    exclude_indptr, exclude_indices, out, vals)
+    return out, vals
+
+
 def exp_rowsum(scores: torch.Tensor) -> torch.Tensor:
     """Z[r] = sum over the columns of expf(scores[r][c]), in a fixed order -> fp32 [n_rows]."""
     _dev(scores, "scores", torch.float32)

@@ -23,6 +23,8 @@ held-out item in the cosine head's exhaustive ranking, from one fp32 MFMA pass o
 whose epilogue counts instead of storing; with `head=` the position in the MLP
 head's ranking (and with `popularity=` in its popularity-weighted one), from a counting
 epilogue on the dense MLP kernel that compares the final fp32 value.
+`rank_lists` / `rank_lists_for_graph` / `list_pairs` take held-out LISTS, one per user, and give
+the same ranks with each user scored once for the MLP head.
 """
 from __future__ import annotations
 
@@ -807,6 +809,326 @@ def rank_for_graph(g, h, ground_truth, etype='bought-by', use_popularity=False,
     items = torch.as_tensor(items, dtype=torch.int64, device=dev)
     ex_ptr, ex_idx = g.in_csr(etype)[:2]
     return rank_items(h['user'], h['item'], users, items, (ex_ptr.to(dev), ex_idx.to(dev)), **kw)
+
+
+# ---- the list-shaped entry: one scored row per user (csrc/heads.hip, DESIGN.md §26) --------
+def _ptr(lens):
+    """[0, lens[0], lens[0] + lens[1], ...]: int64 [len + 1]."""
+    ptr = torch.zeros(lens.numel() + 1, dtype=torch.int64, device=lens.device)
+    ptr[1:] = torch.cumsum(lens, 0)
+    return ptr
+
+
+def _expand_lists(user_rows, gt_indptr, gt_indices, lens, n_pairs=None):
+    """The served lists as pairs (lens: their lengths; n_pairs: their sum where the caller has
+    read it, else read here) -> (users, items, owner: the entry's position in user_rows)."""
+    dev = user_rows.device
+    eptr = _ptr(lens)
+    if n_pairs is None:
+        n_pairs = int(eptr[-1])
+    owner = torch.repeat_interleave(torch.arange(user_rows.numel(), device=dev), lens,
+                                    output_size=n_pairs)
+    pos = gt_indptr[user_rows][owner] + (torch.arange(n_pairs, device=dev) - eptr[owner])
+    return user_rows[owner], gt_indices[pos].to(torch.int64), owner
+
+
+def list_pairs(user_rows, gt_indptr, gt_indices):
+    """The held-out lists of the users `user_rows` (int64, any order; None: every user) of the
+    ground-truth CSR (gt_indptr int64 [n_users + 1], gt_indices) as pairs, the lists
+    concatenated in user_rows order and each in CSR order -> (users int64 [E], items int64
+    [E]): the order of rank_lists' results, and what ranks_to_metrics takes beside its ranks.
+    Plain torch on the tensors' own device; one host read (the extremes of user_rows and E)."""
+    gt_indptr, gt_indices = gt_indptr.reshape(-1), gt_indices.reshape(-1)
+    n_users = gt_indptr.numel() - 1
+    if user_rows is None:
+        user_rows = torch.arange(n_users, device=gt_indptr.device)
+    user_rows = user_rows.reshape(-1)
+    if user_rows.numel() == 0:
+        none = torch.empty(0, dtype=torch.int64, device=gt_indptr.device)
+        return none, none.clone()
+    uc = user_rows.clamp(0, max(n_users - 1, 0))
+    lens = (gt_indptr[uc + 1] - gt_indptr[uc]).clamp(min=0)
+    lo, hi, E = torch.stack([user_rows.min(), user_rows.max(), lens.sum()]).tolist()
+    if lo < 0 or hi >= n_users:
+        raise ValueError(f'list_pairs: user ids out of range of {n_users} users')
+    return _expand_lists(user_rows, gt_indptr, gt_indices, lens, E)[:2]
+
+
+def _list_row_plan(lens, budget, n_rows=None):
+    """The rows of the list count pass for lists of `lens` entries (int64 [U]) whose slots lie
+    back to back in list order: a list takes ceil(len / budget) rows of at most `budget`
+    consecutive slots, an empty list none -> (owner int64 [R]: the row's list, lptr int64
+    [R + 1]: row r's slots are [lptr[r], lptr[r + 1])).  n_rows: R where the caller has read it
+    (sum of ceil(lens / budget)), else read here.  Torch ops only, on any device."""
+    dev = lens.device
+    rows_per = (lens + (budget - 1)) // budget
+    rptr, eptr = _ptr(rows_per), _ptr(lens)
+    if n_rows is None:
+        n_rows = int(rptr[-1])
+    owner = torch.repeat_interleave(torch.arange(lens.numel(), device=dev), rows_per,
+                                    output_size=n_rows)
+    lptr = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+    lptr[:n_rows] = eptr[owner] + (torch.arange(n_rows, device=dev) - rptr[owner]) * budget
+    lptr[n_rows] = eptr[-1]      # a row ends where the next begins: the lists lie back to back
+    return owner, lptr
+
+
+def _lists_check(user_rows, gt_indptr, gt_indices, n_users, n_items, extra=()):
+    """rank_lists' id check, one host read: the id extremes of user_rows and of the served
+    lists, the distinct users among user_rows and the served entries, then whatever `extra`
+    (a function of (lens, served) returning device scalars / vectors) adds to the same read
+    -> (lens, served, n_pairs, extra's values as ints).  Raises ValueError on an id out of
+    range or a repeated user.  Torch ops only, on any device."""
+    dev = gt_indptr.device
+    U, nnz = user_rows.numel(), gt_indices.numel()
+    uc = user_rows.clamp(0, max(n_users - 1, 0))
+    served = torch.zeros(n_users, dtype=torch.bool, device=dev)
+    served[uc] = True
+    lens = (gt_indptr[uc + 1] - gt_indptr[uc]).clamp(min=0)
+    zero = torch.zeros((), dtype=torch.int64, device=dev)
+    if nnz:     # the entries of the served lists, wherever they lie in the CSR
+        row = torch.searchsorted(gt_indptr[1:].contiguous(), torch.arange(nnz, device=dev),
+                                 right=True).clamp(max=n_users - 1)
+        ids = gt_indices.to(torch.int64) * served[row]      # 0, a valid id, elsewhere
+        lo_i, hi_i = ids.min(), ids.max()
+    else:
+        lo_i = hi_i = zero
+    head = [user_rows.min(), user_rows.max(), served.sum(), lens.sum(), lo_i, hi_i,
+            gt_indptr[0], gt_indptr[-1], (gt_indptr[1:] < gt_indptr[:-1]).sum()]
+    more = [t.reshape(-1).to(torch.int64) for t in (extra(lens, served) if extra else ())]
+    got = torch.cat([torch.stack(head).to(torch.int64)] + more).tolist()   # the one read
+    lo_u, hi_u, n_distinct, n_pairs, lo_i, hi_i, p0, p1, n_desc = got[:len(head)]
+    if p0 != 0 or p1 != nnz or n_desc:
+        raise ValueError(f'rank_lists: gt_indptr is not the indptr of {nnz} entries')
+    if lo_u < 0 or hi_u >= n_users or (n_pairs and (lo_i < 0 or hi_i >= n_items)):
+        raise ValueError(f'rank_lists: ids out of range (users in [{lo_u}, {hi_u}] of {n_users}, '
+                         f'items of the served lists in [{lo_i}, {hi_i}] of {n_items})')
+    if n_distinct != U:
+        raise ValueError(f'rank_lists: user_rows holds a repeated user ({U} rows, {n_distinct} '
+                         f'distinct)')
+    return lens, served, n_pairs, got[len(head):]
+
+
+def _rank_lists_mlp(scorer, user_rows, pairs, plan, cuts, exclude, batch_size, rank, vals):
+    """rank_lists' loop for the MLP head.  pairs: (users, items, owner) of every served entry;
+    plan: _list_row_plan's (owner, lptr) over all served users; cuts: per batch boundary the
+    slots and the rows before it (host ints, read with the id check).  Per batch of users: P,
+    Z with a popularity, the entries' own scores, one list count pass, one list resolve."""
+    ex0, ex1 = exclude
+    _, items, owner = pairs
+    row_owner, lptr = plan
+    n_users = scorer.h_user.shape[0]
+    for i, u0 in enumerate(range(0, user_rows.numel(), batch_size)):
+        (e0, r0), (e1, r1) = cuts[i], cuts[i + 1]
+        if e1 == e0:
+            continue
+        ub = user_rows[u0:u0 + batch_size]
+        P = scorer.P(ub)                                   # one row per user
+        gb = items[e0:e1]
+        s = ops.edge_mlp(owner[e0:e1] - u0, gb, P, scorer.Q, *scorer.tail)
+        gid = gb.to(torch.int32)
+        ro = row_owner[r0:r1] - u0
+        lp = (lptr[r0:r1 + 1] - e0).contiguous()
+        Pr = P[ro]                                         # a long list's rows repeat the P row
+        if scorer.p is None:
+            Zr = None
+            ahead = ops.edge_mlp_dense_count_lists(Pr, scorer.Q, *scorer.tail, lp, s, gid)
+        else:
+            Zr = scorer.denominators(P)[ro].contiguous()   # recommend's Z_u, per user
+            ahead = ops.edge_mlp_dense_count_lists_rating(Pr, scorer.Q, *scorer.tail, Zr,
+                                                          scorer.p, lp, s, gid)
+        ops.rank_resolve_mlp_lists(ub[ro].contiguous(), lp, s, gid, ahead, n_users, Pr, scorer.Q,
+                                   *scorer.tail, ex0, ex1, Zr, scorer.p, rank[e0:e1],
+                                   vals[e0:e1])
+
+
+def _rank_lists(h_user, h_item, user_rows, gt_indptr, gt_indices, exclude, head, popularity,
+                weight_popularity, batch_size, cand_cap):
+    """rank_lists -> (rank, vals, stats, users, items)."""
+    if popularity is not None and head is None:
+        raise NotImplementedError(
+            'rank_lists: popularity= needs head= (rank_items: the cosine head has no proved band '
+            'in rating space for its count pass; DESIGN.md §24)')
+    if h_user.dim() != 2 or h_item.dim() != 2 or h_user.shape[1] != h_item.shape[1]:
+        raise ValueError(f'h_user / h_item must be 2-D with one feature size, got '
+                         f'{tuple(h_user.shape)} and {tuple(h_item.shape)}')
+    (n_users, d), n_items = h_user.shape, h_item.shape[0]
+    if gt_indptr.dtype != torch.int64 or gt_indptr.numel() != n_users + 1:
+        raise ValueError(f'rank_lists: gt_indptr must be int64 [n_users + 1 = {n_users + 1}], got '
+                         f'{gt_indptr.dtype} {tuple(gt_indptr.shape)}')
+    if gt_indices.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'rank_lists: gt_indices must be int32 or int64, got {gt_indices.dtype}')
+    batch_size, cand_cap = int(batch_size), int(cand_cap)
+    if batch_size < 1 or not 1 <= cand_cap <= REC_MAX_CAP:
+        raise ValueError(f'rank_lists: batch_size must be >= 1 and cand_cap in '
+                         f'[1, {REC_MAX_CAP}]')
+    ops._dev(h_user, 'h_user', torch.float32)
+    ops._dev(h_item, 'h_item', torch.float32)
+    ops._dev(gt_indptr, 'gt_indptr', torch.int64)
+    ops._dev(gt_indices, 'gt_indices')
+    dev = h_item.device
+    if user_rows is None:
+        user_rows = torch.arange(n_users, device=dev)
+    ops._dev(user_rows, 'user_rows', torch.int64)
+    user_rows = user_rows.reshape(-1).contiguous()
+    gt_indptr, gt_indices = gt_indptr.reshape(-1).contiguous(), gt_indices.reshape(-1).contiguous()
+    if exclude is not None:
+        ex_ptr, ex_idx = exclude
+        ops._dev(ex_ptr, 'exclude indptr', torch.int64)
+        ops._dev(ex_idx, 'exclude indices', torch.int32)
+        if ex_ptr.numel() != n_users + 1:
+            raise ValueError(f'exclude indptr must have n_users + 1 = {n_users + 1} entries, '
+                             f'got {ex_ptr.numel()}')
+        exclude = (ex_ptr.contiguous(), ex_idx.contiguous())
+    p = None if popularity is None else _popularity_vector(popularity, weight_popularity, n_items)
+    U = user_rows.numel()
+    mlp = head is not None
+    stats = {'band_mean': 0.0, 'band_max': 0, 'overflow_rows': 0, 'fast_path': mlp,
+             'eps': 0.0 if mlp else rank_eps(d), 'cand_cap': cand_cap}
+    none = torch.empty(0, dtype=torch.int64, device=dev)
+    empty = (none, torch.empty(0, dtype=torch.float32, device=dev), stats, none, none)
+    if mlp:
+        stats.update(rows=0, pairs=0)
+    if U == 0:
+        return empty
+    if n_users == 0:
+        raise ValueError(f'rank_lists: ids out of range ({U} user rows for no users)')
+    budget = ops.rank_list_slots() if mlp else 1
+    starts = torch.arange(0, U + batch_size, batch_size, device=dev).clamp(max=U)
+
+    def sizes(lens, served):
+        out = []
+        if mlp:     # the batches' first slots and rows, the last one's end
+            out += [_ptr(lens)[starts], _ptr((lens + (budget - 1)) // budget)[starts]]
+            if exclude is not None:     # what the exclusion sort needs to size itself
+                deg = exclude[0][1:] - exclude[0][:-1]
+                out += [served.sum(), (deg * served).sum()]
+        return out
+
+    lens, served, E, more = _lists_check(user_rows, gt_indptr, gt_indices, n_users, n_items, sizes)
+    if E == 0:
+        return empty
+    pairs = _expand_lists(user_rows, gt_indptr, gt_indices, lens, E)
+    if not mlp:     # the cosine head: rank_items on the expanded pairs, as it is
+        rank, vals, stats = rank_items(h_user, h_item, pairs[0], pairs[1], exclude,
+                                       batch_size=batch_size, cand_cap=cand_cap,
+                                       return_stats=True)
+        return rank, vals, stats, pairs[0], pairs[1]
+    nb = starts.numel()
+    cuts = list(zip(more[:nb], more[nb:2 * nb]))
+    h_user, h_item = h_user.contiguous(), h_item.contiguous()
+    scorer = _MlpHead(head, h_user, h_item, p)               # Q formed once per call
+    ex = (None, None) if exclude is None else \
+        _distinct_exclusions(exclude, served, *more[2 * nb:], n_items)
+    plan = _list_row_plan(lens, budget, cuts[-1][1])
+    rank = torch.empty(E, dtype=torch.int64, device=dev)
+    vals = torch.empty(E, dtype=torch.float32, device=dev)
+    _rank_lists_mlp(scorer, user_rows, pairs, plan, cuts, ex, batch_size, rank, vals)
+    stats.update(rows=cuts[-1][1], pairs=E)
+    return rank, vals, stats, pairs[0], pairs[1]
+
+
+def rank_lists(h_user, h_item, user_rows, gt_indptr, gt_indices, exclude=None, *, head=None,
+               popularity=None, weight_popularity=1.0, batch_size=8192, cand_cap=1024,
+               return_stats=False):
+    """rank_items for held-out LISTS: the exact position of every item of the served users'
+    ground-truth lists — the set the reference's create_ground_truth builds, one item list per
+    user — with each distinct user scored once per batch for the MLP head.
+
+    (gt_indptr int64 [n_users + 1], gt_indices int32 or int64): the ground-truth CSR over all
+    users, the pair recs_to_metrics_device takes; lists may be empty and unsorted, and an item
+    listed twice gets its rank twice.  user_rows: int64 device tensor of DISTINCT users in any
+    order (None: every user).  exclude, head, popularity, weight_popularity, cand_cap: as for
+    rank_items.  -> (rank int64 [E], vals fp32 [E]) [, stats]; entry e is entry e of
+    list_pairs(user_rows, gt_indptr, gt_indices), and
+
+        rank_lists(...) == rank_items(h_user, h_item, *list_pairs(...), exclude, ...)
+
+    ranks equal, vals bit for bit, for every head and popularity setting rank_items accepts:
+    its definition, tie rule, exclusion semantics and vals carry over.  A repeated user or an
+    id out of range (in user_rows or a served list) raises ValueError before any kernel of the
+    pass is launched.
+
+    head=None (cosine): the lists are expanded and rank_items' cosine machinery runs on the
+    pairs as it is — no new kernel and NO speed-up: the stats are rank_items', and a user with
+    G items is still scored G times.  Its count pass keeps its counters in registers, which
+    makes a grouped epilogue a different job; it is not done here.  popularity= without head=
+    raises rank_items' NotImplementedError.
+
+    head= a PredictingLayer: Q = h_item W1b^T once per call; per batch of at most `batch_size`
+    USERS P = h_user[rows] W1a^T + b1 (one row per user), with a popularity Z_u of those rows
+    (recommend's denominators: the same bits in any batch), the entries' own scores
+    (ops.edge_mlp), one pass of the dense kernel over all items whose epilogue, after a user's
+    32 scores of a tile are formed, loops over that user's entries and counts each against
+    them (ops.edge_mlp_dense_count_lists), and one resolve launch that walks the user's
+    exclusion row once for all of its entries (ops.rank_resolve_mlp_lists).  A row of the pass
+    holds at most ops.rank_list_slots() entries; a longer list takes several rows that repeat
+    the user's P row (the plan is built on the device; there is no cap on a list's length).
+    The results do not depend on batch_size.  One host read per call (rank_lists(head=) itself:
+    list_pairs and rank_lists_for_graph make reads of their own): the id check, which carries
+    the id extremes of user_rows and of the served lists, the number of entries, the batches'
+    slot and row offsets and the served exclusion sizes.
+    Memory: a batch is batch_size USERS, and the count pass's workspace is int32
+    [ceil(n_items / 1024), entries of the batch] — 256 MB at 1M items and 8,192 users with 8
+    items each, as for rank_items' 65,536 pairs, but 3.2 GB with 100 items each: lower batch_size
+    for long lists (the results do not change).  A served user with an empty list still gets its
+    P row, and with a popularity its Z, in the batch; it takes no row of the pass.  stats: rank_items(head=)'s
+    (fast_path True, band_mean 0.0, band_max 0, overflow_rows 0, eps 0.0, cand_cap accepted
+    and unused) plus rows, the dense-kernel rows scored, and pairs = E."""
+    rank, vals, stats, _, _ = _rank_lists(h_user, h_item, user_rows, gt_indptr, gt_indices,
+                                          exclude, head, popularity, weight_popularity,
+                                          batch_size, cand_cap)
+    return (rank, vals, stats) if return_stats else (rank, vals)
+
+
+def rank_lists_for_graph(g, h, ground_truth, etype='bought-by', use_popularity=False,
+                         weight_popularity=1, **kw):
+    """rank_lists() for the held-out pairs ground_truth = (users, items) of a graph, grouped
+    by user on the device (ops.membership_csr: each user's list ascending by item, repeats
+    kept), the distinct users among them served in ascending order and the items each has an
+    `etype` edge from excluded through g.in_csr(etype), as in rank_for_graph.
+    -> (rank, vals, users, items) [, stats with return_stats=True]: users / items are the
+    pairs in result order (a permutation of ground_truth), what ranks_to_metrics takes.
+    head= (in kw) ranks by the MLP head, one scored row per user; use_popularity as for
+    rank_for_graph (the MLP head only).  Host reads: the pairs' id extremes before the CSR build
+    and the number of distinct users (torch.nonzero), then rank_lists' one."""
+    dev = h['item'].device
+    if use_popularity:
+        if kw.get('head') is None:      # rank_items' refusal, before the graph is touched
+            raise NotImplementedError(
+                'rank_lists_for_graph: use_popularity=True needs head= (rank_items: popularity= '
+                'needs head=; DESIGN.md §24)')
+        try:
+            pop = g.ndata['popularity']['item']
+        except (KeyError, AttributeError, TypeError) as exc:
+            raise KeyError("rank_lists_for_graph(use_popularity=True): the graph has no "
+                           "ndata['popularity']['item']") from exc
+        kw = dict(kw, popularity=torch.as_tensor(pop).to(dev).float(),
+                  weight_popularity=weight_popularity)
+    return_stats = kw.pop('return_stats', False)
+    users, items = ground_truth
+    users = torch.as_tensor(users, dtype=torch.int64, device=dev).reshape(-1)
+    items = torch.as_tensor(items, dtype=torch.int64, device=dev).reshape(-1)
+    n_users, n_items = h['user'].shape[0], h['item'].shape[0]
+    if users.numel() != items.numel():
+        raise ValueError(f'rank_lists_for_graph: {users.numel()} users for {items.numel()} items')
+    if users.numel():       # the CSR build sorts by these ids: checked before it runs
+        lo_u, hi_u, lo_i, hi_i = torch.stack([users.min(), users.max(), items.min(),
+                                              items.max()]).tolist()
+        if lo_u < 0 or hi_u >= n_users or lo_i < 0 or hi_i >= n_items:
+            raise ValueError(f'rank_lists_for_graph: ids out of range (users in [{lo_u}, {hi_u}] '
+                             f'of {n_users}, items in [{lo_i}, {hi_i}] of {n_items})')
+    gt_ptr, gt_idx = ops.membership_csr(items, users, n_items, n_users)
+    user_rows = torch.nonzero(gt_ptr[1:] > gt_ptr[:-1]).reshape(-1)
+    ex_ptr, ex_idx = g.in_csr(etype)[:2]
+    kw.setdefault('head', None)
+    kw.setdefault('popularity', None)
+    kw.setdefault('weight_popularity', 1.0)
+    kw.setdefault('batch_size', 8192)
+    kw.setdefault('cand_cap', 1024)
+    rank, vals, stats, us, gs = _rank_lists(h['user'], h['item'], user_rows, gt_ptr, gt_idx,
+                                            (ex_ptr.to(dev), ex_idx.to(dev)), **kw)
+    return (rank, vals, us, gs, stats) if return_stats else (rank, vals, us, gs)
 
 
 def ranks_to_metrics(rank, users, ks=(10,)):

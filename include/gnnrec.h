@@ -891,6 +891,48 @@ int gnnrec_rank_resolve_mlp_f32(const int64_t* users, const int64_t* items, cons
                                 const float* p_col, const int64_t* exclude_indptr,
                                 const int32_t* exclude_indices, int64_t* rank, float* vals,
                                 void* stream);
+/* ---- the list forms of f1f for the MLP head (csrc/heads.hip) ----
+ * A row is a USER (or gnnrec_rank_list_slots() entries of a longer held-out list: the caller
+ * splits a long list over rows that repeat the user's P row): P [n_rows, 128], and row r's
+ * entries are the slots [lptr[r], lptr[r + 1]) (lptr int64 [n_rows + 1], ascending from 0 to
+ * n_slots, at most gnnrec_rank_list_slots() slots a row) of thr (the entry's own
+ * gnnrec_edge_mlp_f32 score) and gid (its item, int32; an id < 0 or >= n_items is compared as
+ * it is and reads nothing).  The row is scored once per item tile and every slot counted from
+ * those scores: ahead[j] = gnnrec_edge_mlp_dense_count_f32's count for the pair (row of j,
+ * gid[j]).  parts: workspace [gnnrec_cos_denominator_parts(n_items), n_slots] int32.  A row
+ * whose bounds lie outside [0, n_slots], or that spans more than gnnrec_rank_list_slots()
+ * slots, is out of contract and has no slots: nothing is read or written for it, and ahead[j]
+ * of a slot that no valid row covers is undefined (lptr lives on the device: the entry cannot
+ * refuse it).  n_slots = 0 does nothing; n_items = 0 launches nothing and writes ahead = 0. */
+int64_t gnnrec_rank_list_slots(void);
+int gnnrec_edge_mlp_dense_count_lists_f32(const float* P, int64_t n_rows, const float* Q,
+                                          int64_t n_items, const float* W2, const float* b2,
+                                          const float* w3, const float* b3, const int64_t* lptr,
+                                          int64_t n_slots, const float* thr, const int32_t* gid,
+                                          int32_t* parts, int32_t* ahead, void* stream);
+/* The same on R = expf(score) / Z[r] + p_col[v] (Z [n_rows]), slot j's threshold its own
+ * R = expf(s[j]) / Z[r] + p_col[gid[j]], formed in the kernel by the same inline function. */
+int gnnrec_edge_mlp_dense_count_lists_rating_f32(const float* P, int64_t n_rows, const float* Q,
+                                                 int64_t n_items, const float* W2, const float* b2,
+                                                 const float* w3, const float* b3, const float* Z,
+                                                 const float* p_col, const int64_t* lptr,
+                                                 int64_t n_slots, const float* s,
+                                                 const int32_t* gid, int32_t* parts,
+                                                 int32_t* ahead, void* stream);
+/* gnnrec_rank_resolve_mlp_f32 for the rows of that plan: row_user[r] (int64) names the user
+ * whose exclusion row is walked — once per row, each tile of 32 entries scored once — and every
+ * slot j of the row gets rank[j] = 1 + ahead[j] - (excluded items exactly ahead of slot j), or
+ * 0 where gid[j] is excluded, and vals[j] = s[j] or the slot's R (Z [n_rows] and p_col given).
+ * Slots whose item, and rows whose user, are out of range are left unwritten. */
+int gnnrec_rank_resolve_mlp_lists_f32(const int64_t* row_user, const int64_t* lptr,
+                                      int64_t n_rows, const float* s, const int32_t* gid,
+                                      const int32_t* ahead, int64_t n_slots, int64_t n_users,
+                                      const float* P, const float* Q, int64_t n_items,
+                                      const float* W2, const float* b2, const float* w3,
+                                      const float* b3, const float* Z, const float* p_col,
+                                      const int64_t* exclude_indptr,
+                                      const int32_t* exclude_indices, int64_t* rank, float* vals,
+                                      void* stream);
 /* Z[r] = sum over the columns of expf(scores[r][c]), in a fixed order (one block per row). */
 int gnnrec_exp_rowsum_f32(const float* scores, int64_t ld, int64_t n_rows, int64_t n_cols,
                           float* Z, void* stream);
