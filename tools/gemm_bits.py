@@ -7,7 +7,11 @@ ops.gemm runs on inputs from seeded CPU generators and the sha256 of everything 
     python tools/gemm_bits.py --out tests/gemm_bits_parent.json
 
 tests/test_gpu_gemm_bits.py asserts the digests of a build against the committed file.
-`cases()` is the list: (group, name, thunk returning the written tensors).  Every case runs at
+`cases()` is the list: (group, name, thunk returning the written tensors).  `described()` is
+the same list with each case as a `Case`: the CPU inputs and keyword arguments of its ops.gemm
+calls, its M, N and pad, and which tensors it writes.  The thunk uploads and runs that
+description (`run_case`); tests/gemm_reference.py computes from it, in fp64, what the case
+must write (tests/test_gpu_gemm_reference.py).  Every case runs at
 M = 1 (a partial wave), 129 (one row past a block) and 300 (three blocks, the last ragged);
 the name ends in the M.  The groups are the kernels the dispatch of launch_gemm picks
 (depth = K-tile depth of the LDS-DMA kernel, bn = output columns per block):
@@ -28,11 +32,13 @@ the name ends in the M.  The groups are the kernels the dispatch of launch_gemm 
     general     the register-staged kernel: K = 5, K = 34, an A1 that is not 16-B aligned
 """
 import argparse
+import dataclasses
 import functools
 import hashlib
 import json
 import os
 import sys
+from typing import List, Optional
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _PKG = os.path.join(ROOT, "gnn-recsys_amd")
@@ -53,67 +59,157 @@ def _randn(shape, seed):
 
 @functools.lru_cache(None)
 def operand(m, k, seed):
-    return _randn((m, k), 1000 * seed + 7 * m + k).cuda()
+    return _randn((m, k), 1000 * seed + 7 * m + k)
 
 
 @functools.lru_cache(None)
 def weight(n, k, seed):
-    return (_randn((n, k), 50000 + 1000 * seed + 7 * n + k) / 8).cuda()
+    return _randn((n, k), 50000 + 1000 * seed + 7 * n + k) / 8
 
 
 @functools.lru_cache(None)
 def vec(n, seed):
-    return _randn((n,), 90000 + 100 * seed + n).cuda()
+    return _randn((n,), 90000 + 100 * seed + n)
 
 
 @functools.lru_cache(None)
 def degrees(m):
     return torch.randint(0, 8, (m,), generator=torch.Generator().manual_seed(300 + m),
-                         dtype=torch.int32).cuda()
+                         dtype=torch.int32)
 
 
 def base_out(m, n):
-    return _randn((m, n), 2000 + m + n).cuda()
+    return _randn((m, n), 2000 + m + n)
+
+
+@dataclasses.dataclass
+class Call:
+    """One ops.gemm call of a case: its CPU inputs and keyword arguments.  A1 is columns
+    [a1_shift, a1_shift + k1) of a1_table (a view of a wider table when the two differ)."""
+    a1_table: torch.Tensor
+    k1: int
+    w1: torch.Tensor
+    a1_shift: int = 0
+    a2: Optional[torch.Tensor] = None
+    w2: Optional[torch.Tensor] = None
+    a2_deg: Optional[torch.Tensor] = None
+    a2_mode: Optional[str] = None          # None | "div" | "zero"
+    bias: Optional[torch.Tensor] = None
+    bias_nonempty: Optional[torch.Tensor] = None
+    attn_vec: Optional[torch.Tensor] = None
+    relu: bool = False
+    l2norm: bool = False
+    sigmoid: bool = False
+    accum: str = "store"
+    out_div: float = 0.0
+
+    @property
+    def a1(self):
+        return self.a1_table[:, self.a1_shift:self.a1_shift + self.k1]
+
+
+@dataclasses.dataclass
+class Case:
+    """What a case runs: `calls` in order into one output, the [m, n] window at column `col`
+    of the table `out_init` ([m + guard, col + n + pad]: `guard` rows the calls are not given).
+    row_norm_init / attn_state_init: the initial row_norm [m + guard] / attn_state
+    [m + guard, 2] where the calls have one.  `writes` names the tensors run_case returns."""
+    m: int
+    n: int
+    calls: List[Call]
+    out_init: torch.Tensor
+    pad: int = 0
+    col: int = 0
+    guard: int = 0
+    row_norm_init: Optional[torch.Tensor] = None
+    attn_state_init: Optional[torch.Tensor] = None
+
+    @property
+    def writes(self):
+        return ("out",) + (("row_norm",) if self.row_norm_init is not None else ()) + (
+            ("attn_state",) if self.attn_state_init is not None else ())
+
+
+_DEVICE = {}  # id(CPU tensor of a cached generator) -> (the tensor, its upload)
+
+
+def _up(t):
+    """The device copy of a generator's tensor, uploaded once (the generators cache their CPU
+    tensors, so the id is stable)."""
+    if t is None:
+        return None
+    hit = _DEVICE.get(id(t))
+    if hit is None or hit[0] is not t:
+        hit = _DEVICE[id(t)] = (t, t.cuda())
+    return hit[1]
+
+
+def run_case(case, after_call=None):
+    """Run a case on the device -> the tensors it wrote, whole (guard rows and pad columns
+    included), in the order of case.writes.  after_call(j, written) sees them after call j."""
+    from gnnrec import _lib, ops
+    m, n = case.m, case.n
+    wide = case.out_init.cuda()
+    whole = case.col == 0 and case.pad == 0
+    out = wide[:m] if whole else wide[:m, case.col:case.col + n]
+    written = [wide]
+    row_norm = state = None
+    if case.row_norm_init is not None:
+        row_norm = case.row_norm_init.cuda()
+        written.append(row_norm)
+    if case.attn_state_init is not None:
+        state = case.attn_state_init.cuda()
+        written.append(state)
+    for j, c in enumerate(case.calls):
+        a1 = _up(c.a1_table)
+        if c.a1_shift or c.k1 != c.a1_table.shape[1]:
+            a1 = a1[:, c.a1_shift:c.a1_shift + c.k1]
+        kw = {}
+        if c.a2_deg is not None:
+            kw["a2_deg"] = _up(c.a2_deg)
+        if c.a2_mode is not None:
+            kw["a2_mode"] = {"div": _lib.A2_DIV_DEG, "zero": _lib.A2_ZERO_DEG}[c.a2_mode]
+        if row_norm is not None:
+            kw["row_norm"] = row_norm[:m]
+        if c.attn_vec is not None:
+            kw["attn_vec"] = _up(c.attn_vec)
+            kw["attn_state"] = state[:m]
+        ops.gemm(a1, _up(c.w1), _up(c.a2), _up(c.w2), _up(c.bias), relu=c.relu, l2norm=c.l2norm,
+                 sigmoid=c.sigmoid, accum=c.accum, out_div=c.out_div, out=out,
+                 bias_nonempty=_up(c.bias_nonempty), **kw)
+        if after_call is not None:
+            after_call(j, written)
+    return written
 
 
 def _gemm(m, n, k1, k2=0, mode=None, bias=False, relu=False, l2=False, sigmoid=False,
           accum="store", out_div=0.0, pad=0, bias_ne=False, row_norm=False, a1_shift=0):
-    """One ops.gemm call -> the tensors it wrote.  pad: the output is the first n columns of a
-    [m, n + pad] table (returned whole).  a1_shift: A1 is a view `a1_shift` columns into a
-    wider table."""
-    from gnnrec import _lib, ops
-    a1 = operand(m, k1 + 4, 1)[:, a1_shift:a1_shift + k1] if a1_shift else operand(m, k1, 1)
-    kw = {}
-    a2 = w2 = None
+    """One ops.gemm call.  pad: the output is the first n columns of a [m, n + pad] table
+    (returned whole).  a1_shift: A1 is a view `a1_shift` columns into a wider table."""
+    call = Call(a1_table=operand(m, k1 + 4, 1) if a1_shift else operand(m, k1, 1), k1=k1,
+                w1=weight(n, k1, 1), a1_shift=a1_shift, a2_mode=mode,
+                bias=vec(n, 0) if bias else None, bias_nonempty=vec(n, 1) if bias_ne else None,
+                relu=relu, l2norm=l2, sigmoid=sigmoid, accum=accum, out_div=out_div)
     if k2:
-        a2, w2 = operand(m, k2, 2), weight(n, k2, 2)
+        call.a2, call.w2 = operand(m, k2, 2), weight(n, k2, 2)
     if mode is not None or bias_ne:
-        kw["a2_deg"] = degrees(m)
-    if mode is not None:
-        kw["a2_mode"] = {"div": _lib.A2_DIV_DEG, "zero": _lib.A2_ZERO_DEG}[mode]
+        call.a2_deg = degrees(m)
     if accum == "store":
-        wide = torch.full((m, n + pad), 3.0, device="cuda")
+        wide = torch.full((m, n + pad), 3.0)
     else:
         wide = base_out(m, n + pad)
-    written = [wide]
-    if row_norm:
-        kw["row_norm"] = torch.full((m,), -1.0, device="cuda")
-        written.append(kw["row_norm"])
-    ops.gemm(a1, weight(n, k1, 1), a2, w2, vec(n, 0) if bias else None, relu=relu, l2norm=l2,
-             sigmoid=sigmoid, accum=accum, out_div=out_div, out=wide[:, :n] if pad else wide,
-             bias_nonempty=vec(n, 1) if bias_ne else None, **kw)
-    return written
+    return Case(m=m, n=n, calls=[call], out_init=wide, pad=pad,
+                row_norm_init=torch.full((m,), -1.0) if row_norm else None)
 
 
 def _attention(m, n, k, l2=True):
-    """Three relations into one output: attn_first, attn, attn_last over one state."""
-    from gnnrec import ops
-    out = torch.empty(m, n, device="cuda")
-    state = torch.empty(m, 2, device="cuda")
-    for j, accum in enumerate(("attn_first", "attn", "attn_last")):
-        ops.gemm(operand(m, k, 3 + j), weight(n, k, 3 + j), bias=vec(n, 0), relu=True, l2norm=l2,
-                 accum=accum, out=out, attn_vec=vec(n, 2), attn_state=state)
-    return [out, state]
+    """Three relations into one output: attn_first, attn, attn_last over one state (the first
+    call overwrites all of out and state, so their initial values never reach a result)."""
+    calls = [Call(a1_table=operand(m, k, 3 + j), k1=k, w1=weight(n, k, 3 + j), bias=vec(n, 0),
+                  relu=True, l2norm=l2, accum=accum, attn_vec=vec(n, 2))
+             for j, accum in enumerate(("attn_first", "attn", "attn_last"))]
+    return Case(m=m, n=n, calls=calls, out_init=torch.full((m, n), 3.0),
+                attn_state_init=torch.full((m, 2), -1.0))
 
 
 def _runtime_paths(add, n, k):
@@ -129,6 +225,18 @@ def _runtime_paths(add, n, k):
 
 def cases():
     """[(group, name, thunk)]: the thunk runs the case and returns the tensors it wrote."""
+    return [(group, name, functools.partial(_run_described, describe))
+            for group, name, describe in described()]
+
+
+def _run_described(describe):
+    return run_case(describe())
+
+
+def described():
+    """[(group, name, describe)] in the order of cases(): describe() returns the Case (CPU
+    inputs, keyword arguments, sizes, what is written) that both the thunk of cases() and
+    the fp64 reference of tests/gemm_reference.py run from."""
     P = functools.partial
     c = []
 
