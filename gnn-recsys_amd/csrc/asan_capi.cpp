@@ -399,81 +399,8 @@ static void validation() {
                                 nullptr, 16, 4, nullptr, 16, 9, 16, nullptr, nullptr, nullptr,
                                 nullptr) == GNNREC_OK,
         "rank resolve no pairs");
-  // the same evaluation for the MLP head (heads.hip): every refusal comes before a launch
-  CHECK(gnnrec_edge_mlp_dense_count_f32(nullptr, 4, f16, 9, f16, f16, f16, f16, f16, i16, i16,
-                                        i16, nullptr) == GNNREC_EINVAL &&
-            err_has("null pointer"),
-        "dense count null P");
-  CHECK(gnnrec_edge_mlp_dense_count_f32(f16, 4, reinterpret_cast<float*>(8), 9, f16, f16, f16, f16,
-                                        f16, i16, i16, i16, nullptr) == GNNREC_EINVAL &&
-            err_has("16-byte aligned"),
-        "dense count unaligned Q");
-  CHECK(gnnrec_edge_mlp_dense_count_f32(f16, 4, f16, 9, f16, f16, f16, f16, f16, i16, nullptr,
-                                        i16, nullptr) == GNNREC_EINVAL && err_has("parts"),
-        "dense count null parts");
-  CHECK(gnnrec_edge_mlp_dense_count_f32(f16, 4, f16, 9, f16, f16, f16, f16, f16, nullptr, i16,
-                                        i16, nullptr) == GNNREC_EINVAL && err_has("gid"),
-        "dense count null gid");
-  CHECK(gnnrec_edge_mlp_dense_count_f32(f16, 4, f16, 9, f16, f16, f16, f16, f16, i16, i16,
-                                        nullptr, nullptr) == GNNREC_EINVAL &&
-            err_has("null ahead"),
-        "dense count null ahead");
-  CHECK(gnnrec_edge_mlp_dense_count_f32(f16, 4, nullptr, 0, f16, f16, f16, f16, f16, i16, i16,
-                                        nullptr, nullptr) == GNNREC_EINVAL &&
-            err_has("null ahead"),
-        "dense count no items, null ahead");
-  CHECK(gnnrec_edge_mlp_dense_count_f32(f16, -1, f16, 9, f16, f16, f16, f16, f16, i16, i16, i16,
-                                        nullptr) == GNNREC_EINVAL && err_has("negative size"),
-        "dense count negative rows");
-  CHECK(gnnrec_edge_mlp_dense_count_f32(nullptr, 0, nullptr, 9, nullptr, nullptr, nullptr,
-                                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) ==
-            GNNREC_OK,
-        "dense count no rows");
-  CHECK(gnnrec_edge_mlp_dense_count_rating_f32(f16, 4, f16, 9, f16, f16, f16, f16, nullptr, f16,
-                                               f16, i16, i16, i16, nullptr) == GNNREC_EINVAL &&
-            err_has("null Z"),
-        "dense count rating null Z");
-  CHECK(gnnrec_edge_mlp_dense_count_rating_f32(f16, 4, f16, 9, f16, f16, f16, f16, f16, f16,
-                                               nullptr, i16, i16, i16, nullptr) ==
-            GNNREC_EINVAL && err_has("null thr"),
-        "dense count rating null scores");
-  CHECK(gnnrec_edge_mlp_dense_count_rating_f32(f16, 4, f16, 9, reinterpret_cast<float*>(8), f16,
-                                               f16, f16, f16, f16, f16, i16, i16, i16, nullptr) ==
-            GNNREC_EINVAL && err_has("16-byte aligned"),
-        "dense count rating unaligned W2");
-  CHECK(gnnrec_edge_mlp_dense_count_rating_f32(nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr,
-                                               nullptr, nullptr, nullptr, nullptr, nullptr,
-                                               nullptr, nullptr, nullptr) == GNNREC_OK,
-        "dense count rating empty");
-  CHECK(gnnrec_rank_resolve_mlp_f32(l16, l16, f16, i16, 3, 4, f16, f16, 9, f16, f16, f16, f16,
-                                    nullptr, nullptr, l16, nullptr, l16, f16, nullptr) ==
-            GNNREC_EINVAL && err_has("come together"),
-        "resolve mlp indptr without indices");
-  CHECK(gnnrec_rank_resolve_mlp_f32(l16, l16, f16, i16, 3, 4, f16, f16, 9, f16, f16, f16, f16,
-                                    f16, nullptr, nullptr, nullptr, l16, f16, nullptr) ==
-            GNNREC_EINVAL && err_has("Z and p_col"),
-        "resolve mlp Z without p_col");
-  CHECK(gnnrec_rank_resolve_mlp_f32(l16, l16, f16, i16, 3, 4, f16, f16, 9, f16, f16, f16, f16,
-                                    nullptr, nullptr, nullptr, nullptr, l16, nullptr, nullptr) ==
-            GNNREC_EINVAL && err_has("null pointer"),
-        "resolve mlp null vals");
-  CHECK(gnnrec_rank_resolve_mlp_f32(l16, l16, f16, i16, 3, 4, reinterpret_cast<float*>(8), f16, 9,
-                                    f16, f16, f16, f16, nullptr, nullptr, nullptr, nullptr, l16,
-                                    f16, nullptr) == GNNREC_EINVAL && err_has("16-byte aligned"),
-        "resolve mlp unaligned P");
-  CHECK(gnnrec_rank_resolve_mlp_f32(l16, l16, f16, i16, 3, 4, f16, nullptr, 0, f16, f16, f16, f16,
-                                    nullptr, nullptr, nullptr, nullptr, l16, f16, nullptr) ==
-            GNNREC_EINVAL && err_has("without users or items"),
-        "resolve mlp pairs without items");
-  CHECK(gnnrec_rank_resolve_mlp_f32(l16, l16, f16, i16, -1, 4, f16, f16, 9, f16, f16, f16, f16,
-                                    nullptr, nullptr, nullptr, nullptr, l16, f16, nullptr) ==
-            GNNREC_EINVAL && err_has("bad size"),
-        "resolve mlp negative pairs");
-  CHECK(gnnrec_rank_resolve_mlp_f32(nullptr, nullptr, nullptr, nullptr, 0, 4, nullptr, nullptr, 9,
-                                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, nullptr, nullptr) == GNNREC_OK,
-        "resolve mlp no pairs");
-  // its list forms: one scored row per user
+  // the same evaluation for the MLP head (heads.hip), one scored row per user: every refusal
+  // comes before a launch
   CHECK(gnnrec_rank_list_slots() == 16, "list slots");
   CHECK(gnnrec_edge_mlp_dense_count_lists_f32(f16, 4, f16, 9, f16, f16, f16, f16, l16, 65, f16,
                                               i16, i16, i16, nullptr) == GNNREC_EINVAL &&
@@ -495,6 +422,34 @@ static void validation() {
                                               nullptr, nullptr, nullptr, nullptr, nullptr) ==
             GNNREC_OK,
         "list count no slots");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_f32(nullptr, 4, f16, 9, f16, f16, f16, f16, l16, 5, f16,
+                                              i16, i16, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "list count null P");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_f32(f16, 4, reinterpret_cast<float*>(8), 9, f16, f16,
+                                              f16, f16, l16, 5, f16, i16, i16, i16, nullptr) ==
+            GNNREC_EINVAL && err_has("16-byte aligned"),
+        "list count unaligned Q");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_f32(f16, 4, f16, 9, f16, f16, f16, f16, l16, 5, f16,
+                                              i16, nullptr, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("parts"),
+        "list count null parts");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_f32(f16, 4, f16, 9, f16, f16, f16, f16, l16, 5, f16,
+                                              nullptr, i16, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("gid"),
+        "list count null gid");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_f32(f16, 4, nullptr, 0, f16, f16, f16, f16, l16, 5, f16,
+                                              i16, i16, nullptr, nullptr) == GNNREC_EINVAL &&
+            err_has("null ahead"),
+        "list count no items, null ahead");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_f32(f16, -1, f16, 9, f16, f16, f16, f16, l16, 0, f16,
+                                              i16, i16, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("negative size"),
+        "list count negative rows");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_f32(nullptr, 0, nullptr, 9, nullptr, nullptr, nullptr,
+                                              nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                                              nullptr, nullptr) == GNNREC_OK,
+        "list count no rows");
   CHECK(gnnrec_edge_mlp_dense_count_lists_rating_f32(f16, 4, f16, 9, f16, f16, f16, f16, nullptr,
                                                      f16, l16, 5, f16, i16, i16, i16, nullptr) ==
             GNNREC_EINVAL && err_has("null Z"),
@@ -504,6 +459,20 @@ static void validation() {
                                                      i16, i16, nullptr) == GNNREC_EINVAL &&
             err_has("16-byte aligned"),
         "list count rating unaligned Q");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_rating_f32(f16, 4, f16, 9, f16, f16, f16, f16, f16, f16,
+                                                     l16, 5, nullptr, i16, i16, i16, nullptr) ==
+            GNNREC_EINVAL && err_has("/ thr /"),
+        "list count rating null scores");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_rating_f32(f16, 4, f16, 9, reinterpret_cast<float*>(8),
+                                                     f16, f16, f16, f16, f16, l16, 5, f16, i16,
+                                                     i16, i16, nullptr) == GNNREC_EINVAL &&
+            err_has("16-byte aligned"),
+        "list count rating unaligned W2");
+  CHECK(gnnrec_edge_mlp_dense_count_lists_rating_f32(nullptr, 0, nullptr, 0, nullptr, nullptr,
+                                                     nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                     0, nullptr, nullptr, nullptr, nullptr,
+                                                     nullptr) == GNNREC_OK,
+        "list count rating empty");
   CHECK(gnnrec_rank_resolve_mlp_lists_f32(l16, l16, 3, f16, i16, i16, 5, 4, f16, f16, 9, f16, f16,
                                           f16, f16, nullptr, nullptr, l16, nullptr, l16, f16,
                                           nullptr) == GNNREC_EINVAL && err_has("come together"),
@@ -521,6 +490,29 @@ static void validation() {
                                           f16, nullptr) == GNNREC_EINVAL &&
             err_has("null pointer"),
         "list resolve null lptr");
+  CHECK(gnnrec_rank_resolve_mlp_lists_f32(l16, l16, 3, f16, i16, i16, 5, 4, f16, f16, 9, f16, f16,
+                                          f16, f16, f16, nullptr, nullptr, nullptr, l16, f16,
+                                          nullptr) == GNNREC_EINVAL && err_has("Z and p_col"),
+        "list resolve Z without p_col");
+  CHECK(gnnrec_rank_resolve_mlp_lists_f32(l16, l16, 3, f16, i16, i16, 5, 4, f16, f16, 9, f16, f16,
+                                          f16, f16, nullptr, nullptr, nullptr, nullptr, l16,
+                                          nullptr, nullptr) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "list resolve null vals");
+  CHECK(gnnrec_rank_resolve_mlp_lists_f32(l16, l16, 3, f16, i16, i16, 5, 4,
+                                          reinterpret_cast<float*>(8), f16, 9, f16, f16, f16, f16,
+                                          nullptr, nullptr, nullptr, nullptr, l16, f16, nullptr) ==
+            GNNREC_EINVAL && err_has("16-byte aligned"),
+        "list resolve unaligned P");
+  CHECK(gnnrec_rank_resolve_mlp_lists_f32(l16, l16, 3, f16, i16, i16, 5, 4, f16, nullptr, 0, f16,
+                                          f16, f16, f16, nullptr, nullptr, nullptr, nullptr, l16,
+                                          f16, nullptr) == GNNREC_EINVAL &&
+            err_has("without users or items"),
+        "list resolve entries without items");
+  CHECK(gnnrec_rank_resolve_mlp_lists_f32(l16, l16, -1, f16, i16, i16, 0, 4, f16, f16, 9, f16,
+                                          f16, f16, f16, nullptr, nullptr, nullptr, nullptr, l16,
+                                          f16, nullptr) == GNNREC_EINVAL && err_has("bad size"),
+        "list resolve negative rows");
   CHECK(gnnrec_rank_resolve_mlp_lists_f32(nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 4,
                                           nullptr, nullptr, 9, nullptr, nullptr, nullptr, nullptr,
                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,

@@ -417,33 +417,27 @@ int launch_edge_mlp_lds(bool grouped, EdgeMlpArgs& a, hipStream_t s) {
 // partials [chunks, n_users] are folded in index order by gnnrec_fold_partials_f32.  No float
 // atomics; a user's sums do not depend on the group it is scored in.
 //
-// Full-ranking evaluation (f1f for this head) adds two epilogues on DENOM's
-// work decomposition, COUNT and COUNT_R.  The rows are PAIRS (u_r, g_r): row r of P is the P
-// row of u_r, gid[r] = g_r the held-out item.  An item v counts for row r where
-//   v != gid[r]  and  (x > t_r  or  (x == t_r and v < gid[r]))
-// with x the final fp32 score and t_r = thr[r] (the pair's own edge_mlp score), or for COUNT_R
-// x = rating(score, Z[r], pcol[v]) and t_r = rating(thr[r], Z[r], pcol[gid[r]]) formed here by
-// the same inline function.  No band: x is the very value the ranking is defined on.  The
-// count of a (row, tile) is the popcount of a ballot — wave-uniform — which lane 0 adds to
-// the row's int slot in the wave's LDS; after the chunk the slots go to part[chunk, row]
-// (int32) and fold_partials_i32_kernel sums them.  Integers: no order to fix, no atomics.
-//
-// The list forms of that evaluation, COUNT_L and COUNT_LR, share one scored row
-// among a user's held-out items.  A row r is a USER (or kDenseListSlots entries of a longer
-// list: the caller splits it over rows that repeat the user's P row); its entries are the
-// slots [lptr[r], lptr[r + 1]) of thr (the entry's own edge_mlp score) and gid (its item).
+// Full-ranking evaluation (f1f for this head) adds two epilogues on
+// DENOM's work decomposition, COUNT_L and COUNT_LR, which share one scored row among a user's
+// held-out items.  A row r is a USER (or kDenseListSlots entries of a longer list: the caller
+// splits it over rows that repeat the user's P row; a single pair (u, g) is a row with one
+// slot); its entries are the slots [lptr[r], lptr[r + 1]) of thr (the entry's own edge_mlp
+// score) and gid (its held-out item).  An item v counts for slot j of row r where
+//   v != gid[j]  and  (x > t_j  or  (x == t_j and v < gid[j]))
+// with x the final fp32 score and t_j = thr[j], or for COUNT_LR x = rating(score, Z[r], pcol[v])
+// and t_j = rating(thr[j], Z[r], pcol[gid[j]]) formed here by the same inline function.  No
+// band: x is the very value the ranking is defined on.
 // After a (row, tile) is scored, lane j loads slot j's threshold and item — for COUNT_LR the
-// threshold becomes rating(thr_j, Z[r], pcol[gid_j]) by the function that rates the items
-// (loading them before the row's 64 MFMAs spilled 360 B a lane around the MFMA chain) — and
-// a wave-uniform loop over the row's slots reads them back by v_readlane and counts, per
-// slot, COUNT's compare by ballot and popcount; lane j keeps slot j's count and
-// adds it to the slot's 16-bit counter in the wave's LDS (a chunk holds 1024 items: no
+// threshold is rated then (loading them before the row's 64 MFMAs spilled 360 B a lane around
+// the MFMA chain) — and a wave-uniform loop over the row's slots reads them back by v_readlane
+// and counts, per slot, the compare above by ballot and popcount; lane j keeps slot j's count
+// and adds it to the slot's 16-bit counter in the wave's LDS (a chunk holds 1024 items: no
 // overflow), 64 rows x 16 slots x 2 B = the 2 KB a wave has left beside the image and the P
-// stage with two blocks on a CU.  After the chunk the counters go to part[chunk, slot].
+// stage with two blocks on a CU.  After the chunk the counters go to part[chunk, slot] (int32)
+// and fold_partials_i32_kernel sums them.  Integers: no order to fix, no atomics.
 constexpr int kDenseZTiles = 32;  // item tiles (1024 items) per partial of the denominators
 enum DenseMode { kDenseStore = 0, kDenseFilter = 1, kDenseDenom = 2, kDenseStoreR = 3,
-                 kDenseFilterR = 4, kDenseCount = 5, kDenseCountR = 6, kDenseCountL = 7,
-                 kDenseCountLR = 8 };
+                 kDenseFilterR = 4, kDenseCountL = 5, kDenseCountLR = 6 };
 constexpr int kDenseListSlots = 16;  // COUNT_L / COUNT_LR: list entries per row, at most
 static_assert(kDenseZTiles * kMlpTile <= 65535, "a chunk's count fits a 16-bit counter");
 constexpr int kDenseUsers = 64;  // users scored per staged item tile, at most
@@ -459,7 +453,7 @@ struct DenseMlpArgs {
   int64_t work;         // work items: item tiles x user groups
   float* out;           // STORE
   int64_t ldo;
-  const float* tau;     // FILTER; COUNT / COUNT_R: the row's own raw score
+  const float* tau;     // FILTER; COUNT_L / COUNT_LR: the slot's own raw score
   int* counts;
   int* cand_items;
   float* cand_scores;
@@ -467,9 +461,9 @@ struct DenseMlpArgs {
   const float* Z;       // STORE_R / FILTER_R: per user row
   const float* pcol;    //                     per column of Q
   float* part;          // DENOM: [chunks, n_users]
-  int64_t n_tiles;      // DENOM / COUNT: item tiles
-  const int* gid;       // COUNT / COUNT_R: the row's held-out item
-  int* ipart;           // COUNT / COUNT_R: [chunks, n_users]; COUNT_L / COUNT_LR: [chunks, n_slots]
+  int64_t n_tiles;      // DENOM / COUNT_L / COUNT_LR: item tiles
+  const int* gid;       // COUNT_L / COUNT_LR: the slot's held-out item
+  int* ipart;           // COUNT_L / COUNT_LR: [chunks, n_slots]
   const int64_t* lptr;  // COUNT_L / COUNT_LR: [n_users + 1], row r's slots of tau / gid
   int64_t n_slots;
 };
@@ -501,17 +495,13 @@ template <int MODE>
 __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) {
   constexpr bool FILTER = MODE == kDenseFilter || MODE == kDenseFilterR;
   constexpr bool RATING = MODE == kDenseStoreR || MODE == kDenseFilterR ||
-                          MODE == kDenseCountR || MODE == kDenseCountLR;
+                          MODE == kDenseCountLR;
   constexpr bool DENOM = MODE == kDenseDenom;
-  constexpr bool COUNT = MODE == kDenseCount || MODE == kDenseCountR;
   constexpr bool LISTS = MODE == kDenseCountL || MODE == kDenseCountLR;
-  constexpr bool CHUNKED = DENOM || COUNT || LISTS;  // a work item walks a chunk of tiles
+  constexpr bool CHUNKED = DENOM || LISTS;  // a work item walks a chunk of tiles
   __shared__ float4 image[kMlpWaves][kMlpTile * 32];     // 16 KB per wave
   __shared__ float4 pstage[kMlpWaves][kDenseStage * 32];  // 2 KB per wave
   __shared__ float zsum[kMlpWaves][DENOM ? kDenseUsers : 1];  // DENOM: the group's sums
-  __shared__ int csum[kMlpWaves][COUNT ? kDenseUsers : 1];    // COUNT: the group's counts,
-  __shared__ float cthr[kMlpWaves][COUNT ? kDenseUsers : 1];  //   thresholds
-  __shared__ int cgid[kMlpWaves][COUNT ? kDenseUsers : 1];    //   and held-out items
   // LISTS: the group's slot counters, [row][slot], two to a word
   __shared__ unsigned short lsum[kMlpWaves][LISTS ? kDenseUsers * kDenseListSlots : 2];
   static_assert(kDenseStage * 32 == 2 * kWave, "a stage is two chunks per lane");
@@ -534,22 +524,6 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) 
     const int64_t t_beg = CHUNKED ? t0 * kDenseZTiles : t0;
     const int64_t n_walk = CHUNKED ? min<int64_t>(kDenseZTiles, a.n_tiles - t_beg) : 1;
     if constexpr (DENOM) zsum[wv][lane] = 0.f;  // only lane 0 touches it until the write-out
-    if constexpr (COUNT) {
-      // lane l: row l of the group.  Its threshold is formed once per work item — for
-      // COUNT_R the row's own R, by the function that forms the items' — and read back per
-      // row as an LDS broadcast (the fence before the first tile's staging orders it)
-      const int64_t ul = g * a.per_group + lane;
-      float tl = 0.f;
-      int gl = -1;
-      if (lane < a.per_group && ul < a.n_users) {
-        tl = a.tau[ul];
-        gl = a.gid[ul];
-        if constexpr (RATING) tl = rating(tl, a.Z[ul], gl >= 0 && gl < a.n_cols ? a.pcol[gl] : 0.f);
-      }
-      csum[wv][lane] = 0;
-      cthr[wv][lane] = tl;
-      cgid[wv][lane] = gl;
-    }
     if constexpr (LISTS) {
       unsigned* z = reinterpret_cast<unsigned*>(lsum[wv]);
 #pragma unroll
@@ -597,10 +571,6 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) 
         int gu = -1;
         if constexpr (FILTER) thr = a.tau[u];
         if constexpr (RATING) zu = a.Z[u];
-        if constexpr (COUNT) {
-          thr = cthr[wv][u - u_beg];
-          gu = cgid[wv][u - u_beg];
-        }
         float sc = mlp_tile_score<true>(a.m, S, w, pc, r, h, b3v);
         if constexpr (RATING) sc = rating(sc, zu, pv);
         int ns = 0;  // LISTS: the row's slots, lane j holding slot j's threshold and item
@@ -614,17 +584,13 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) 
               thr = rating(thr, zu, gu >= 0 && gu < a.n_cols ? a.pcol[gu] : 0.f);
           }
         }
-        if constexpr (COUNT) {
-          const bool ahead = h == 0 && v >= 0 && v != gu && (sc > thr || (sc == thr && v < gu));
-          const int n_ahead = __popcll(__ballot(ahead));  // wave-uniform
-          if (lane == 0) csum[wv][u - u_beg] += n_ahead;
-        } else if constexpr (LISTS) {
+        if constexpr (LISTS) {
           int mine = 0;
           const bool live = h == 0 && v >= 0;
           for (int sl = 0; sl < ns; ++sl) {  // wave-uniform
             const float tj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(thr), sl));
             const int gj = __builtin_amdgcn_readlane(gu, sl);
-            // COUNT's compare, its terms combined without branches (| and & on bools: every
+            // the compare, its terms combined without branches (| and & on bools: every
             // term is a lane mask, and a short-circuit form compiled to two branches a slot)
             const bool ahead = live & (v != gj) & ((sc > tj) | ((sc == tj) & (v < gj)));
             const int n_ahead = __popcll(__ballot(ahead));
@@ -677,13 +643,10 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_dense_kernel(DenseMlpArgs a) 
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    } else if constexpr (CHUNKED) {
+    } else if constexpr (DENOM) {
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // lane 0's sums are visible
       const int64_t u = g * a.per_group + lane;
-      if (lane < a.per_group && u < a.n_users) {
-        if constexpr (DENOM) a.part[t0 * a.n_users + u] = zsum[wv][lane];
-        else a.ipart[t0 * a.n_users + u] = csum[wv][lane];
-      }
+      if (lane < a.per_group && u < a.n_users) a.part[t0 * a.n_users + u] = zsum[wv][lane];
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
   }
@@ -706,8 +669,7 @@ int launch_edge_mlp_dense(int mode, const char* fn, DenseMlpArgs& a, hipStream_t
   a.groups = (a.n_users + kDenseUsers - 1) / kDenseUsers;
   a.per_group = (a.n_users + a.groups - 1) / a.groups;
   a.n_tiles = (a.n_cols + kMlpTile - 1) / kMlpTile;
-  const bool chunked = mode == kDenseDenom || mode == kDenseCount || mode == kDenseCountR ||
-                       mode == kDenseCountL || mode == kDenseCountLR;
+  const bool chunked = mode == kDenseDenom || mode == kDenseCountL || mode == kDenseCountLR;
   a.work = (chunked ? (a.n_tiles + kDenseZTiles - 1) / kDenseZTiles : a.n_tiles) * a.groups;
   int64_t blocks = (a.work + kMlpWaves - 1) / kMlpWaves;
   if (blocks > kMlpResidentWaves / kMlpWaves) blocks = kMlpResidentWaves / kMlpWaves;
@@ -717,8 +679,6 @@ int launch_edge_mlp_dense(int mode, const char* fn, DenseMlpArgs& a, hipStream_t
   else if (mode == kDenseStore) GNNREC_LAUNCH_DENSE(kDenseStore);
   else if (mode == kDenseDenom) GNNREC_LAUNCH_DENSE(kDenseDenom);
   else if (mode == kDenseStoreR) GNNREC_LAUNCH_DENSE(kDenseStoreR);
-  else if (mode == kDenseCount) GNNREC_LAUNCH_DENSE(kDenseCount);
-  else if (mode == kDenseCountR) GNNREC_LAUNCH_DENSE(kDenseCountR);
   else if (mode == kDenseCountL) GNNREC_LAUNCH_DENSE(kDenseCountL);
   else if (mode == kDenseCountLR) GNNREC_LAUNCH_DENSE(kDenseCountLR);
   else GNNREC_LAUNCH_DENSE(kDenseFilterR);
@@ -726,15 +686,7 @@ int launch_edge_mlp_dense(int mode, const char* fn, DenseMlpArgs& a, hipStream_t
   return check_launch(fn);
 }
 
-// The count pass's launch for either form, then the fold of its partials into ahead.
-int launch_dense_count(int mode, const char* fn, DenseMlpArgs& a, int32_t* ahead, hipStream_t s) {
-  const int rc = launch_edge_mlp_dense(mode, fn, a, s);
-  if (rc != GNNREC_OK) return rc;
-  return launch_fold_partials_i32(fn, a.ipart, (a.n_tiles + kDenseZTiles - 1) / kDenseZTiles,
-                                  a.n_users, ahead, s);
-}
-
-// The list forms' launch, then the fold of the slots' partials into ahead.
+// The count pass's launch for either form, then the fold of the slots' partials into ahead.
 int launch_dense_count_lists(int mode, const char* fn, DenseMlpArgs& a, int32_t* ahead,
                              hipStream_t s) {
   const int rc = launch_edge_mlp_dense(mode, fn, a, s);
@@ -744,89 +696,22 @@ int launch_dense_count_lists(int mode, const char* fn, DenseMlpArgs& a, int32_t*
 }
 
 // ------------------------------------------------- rank resolve, MLP head ----
-// One wave per pair (u, g) of the full-ranking evaluation: the count pass
-// counted EVERY item exactly ahead of g, the user's excluded ones too.  The user's exclusion
-// row (a CSR over the users whose repeats and out-of-table ids the caller struck to -1) is
-// walked in tiles of 32 entries: the tile's Q rows staged as the dense kernel stages an item
-// tile, scored against the pair's P row by mlp_tile_score<true> (edge_mlp's bits), turned into
-// R = rating(score, Z, p[v]) for the rating form, and the entries exactly ahead under the same
-// rule counted.  An excluded item was counted by the pass exactly when it is exactly ahead, so
+// One wave per list row — a user, kDenseListSlots entries of a longer list, or a single pair —
+// of the count pass's row plan: P row b, slots [lptr[b], lptr[b + 1]) of
+// sraw / gid / ahead, row_user[b] the user whose exclusion row is walked.  The count pass
+// counted EVERY item exactly ahead of a slot's item g, the user's excluded ones too.  The
+// user's exclusion row (a CSR over the users whose repeats and out-of-table ids the caller
+// struck to -1) is walked ONCE, in tiles of 32 entries: the tile's Q rows staged as the dense
+// kernel stages an item tile and scored against the row's P row by mlp_tile_score<true>
+// (edge_mlp's bits), turned into R = rating(score, Z, p[v]) for the rating form; a
+// wave-uniform loop over the row's slots (lane j holds slot j's threshold and item, read back
+// by v_readlane) counts the entries exactly ahead of each slot under the count pass's rule and
+// notes a slot whose item is among them.  An excluded item was counted by the pass exactly
+// when it is exactly ahead, so
 //   rank = (g is in the row) ? 0 : 1 + ahead - excluded_ahead
-// is exact arithmetic (rank.hip's header).  vals[b] = the value the pair is ranked by: its
-// raw score s[b], or its R.
-template <bool RATING>
-__global__ __launch_bounds__(256) void rank_resolve_mlp_kernel(
-    EdgeMlpArgs m, const int64_t* __restrict__ users, const int64_t* __restrict__ items,
-    const float* __restrict__ sraw, const int* __restrict__ ahead, int64_t n_pairs,
-    int64_t n_users, int64_t n_cols, const float* __restrict__ Z, const float* __restrict__ pcol,
-    const int64_t* __restrict__ ex_ptr, const int32_t* __restrict__ ex_idx,
-    int64_t* __restrict__ rank, float* __restrict__ vals) {
-  __shared__ float4 image[kMlpWaves][kMlpTile * 32];  // 16 KB per wave
-  const int lane = threadIdx.x & 63;
-  const int wv = threadIdx.x >> 6;
-  const int r = lane & 31;
-  const int h = lane >> 5;
-  const int64_t b = (int64_t)blockIdx.x * kMlpWaves + wv;
-  if (b >= n_pairs) return;  // wave-uniform, as every exit below; no block-wide barrier follows
-  const int64_t u = users[b], g = items[b];
-  if (u < 0 || u >= n_users || g < 0 || g >= n_cols) return;
-  float4* S = image[wv];
-  const float4* P4 = reinterpret_cast<const float4*>(m.P);
-  const float4* Q4 = reinterpret_cast<const float4*>(m.Q);
-  float zb = 1.f;
-  float t = sraw[b];
-  if constexpr (RATING) {
-    zb = Z[b];
-    t = rating(t, zb, pcol[g]);
-  }
-  if (lane == 0) vals[b] = t;
-  int behind = 0;  // excluded items exactly ahead: wave-uniform
-  bool excluded = false;
-  if (ex_ptr) {
-    const int64_t e0 = ex_ptr[u], e1 = ex_ptr[u + 1];
-    if (e0 < e1) {
-      float4 w[16], pc[16];
-      mlp_load_w2(m, r, h, w);
-      const float b3v = m.b3[0];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) pc[c] = P4[b * 32 + 16 * h + c];  // the pair's P row
-      for (int64_t base = e0; base < e1; base += kMlpTile) {  // wave-uniform bound
-        const int64_t e = base + r;
-        const int64_t c = e < e1 ? ex_idx[e] : -1;  // -1: a repeat or an id past the table
-        const int v = c >= 0 && c < n_cols ? (int)c : -1;
-        excluded |= c == g;
-        float pv = 0.f;
-        if constexpr (RATING) pv = v >= 0 ? pcol[v] : 0.f;
-        // the previous tile's reads of the image are done before it is overwritten
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          float4 q[8], p[8];
-          mlp_load<true, 8>(Q4, P4, v, 0, r, h, 8 * half, q, p);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) S[(2 * (8 * half + i) + h) * 32 + r] = q[i];
-        }
-        // the staging stores are visible to the MFMA-layout reads (lane r reads row r)
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        float sc = mlp_tile_score<true>(m, S, w, pc, r, h, b3v);
-        if constexpr (RATING) sc = rating(sc, zb, pv);
-        const bool is_ahead = h == 0 && v >= 0 && v != g && (sc > t || (sc == t && v < g));
-        behind += __popcll(__ballot(is_ahead));
-      }
-    }
-  }
-  const bool any_excluded = __ballot(excluded) != 0;
-  if (lane == 0) rank[b] = any_excluded ? 0 : 1 + (int64_t)ahead[b] - behind;
-}
-
-// The list form: one wave per list row — a user, or kDenseListSlots entries of
-// a longer list — of the count pass's row plan: P row b, slots [lptr[b], lptr[b + 1]) of sraw /
-// gid / ahead, row_user[b] the user whose exclusion row is walked.  That row is walked ONCE: a
-// tile of 32 entries is staged and scored once, as above, and a wave-uniform loop over the
-// row's slots (lane j holds slot j's threshold and item, read back by v_readlane) counts the
-// entries exactly ahead of each slot and notes a slot whose item is among them; lane j keeps
-// slot j's two results and writes rank and vals of its slot.  A slot whose item is out of
-// range, and a row whose user is, are left unwritten.
+// is exact arithmetic (rank.hip's header).  Lane j keeps slot j's two results and writes rank
+// and vals of its slot, vals = the value the entry is ranked by: its raw score, or its R.  A
+// slot whose item is out of range, and a row whose user is, are left unwritten.
 template <bool RATING>
 __global__ __launch_bounds__(256) void rank_resolve_mlp_lists_kernel(
     EdgeMlpArgs m, const int64_t* __restrict__ row_user, const int64_t* __restrict__ lptr,
@@ -1093,104 +978,11 @@ extern "C" int gnnrec_edge_mlp_dense_filter_rating_f32(
   return launch_edge_mlp_dense(kDenseFilterR, fn, a, as_stream(stream));
 }
 
-// the per-row operands of a count pass, after check_dense: ahead is zeroed where there is
-// nothing to count, and no kernel is launched then
-static int dense_count_operands(const char* fn, int64_t n_rows, int64_t n_items, const void* thr,
-                                const void* gid, const void* parts, int32_t* ahead, void* stream,
-                                bool* empty) {
-  using namespace gnnrec;
-  *empty = n_rows == 0 || n_items == 0;
-  if (n_rows == 0) return GNNREC_OK;
-  GNNREC_REQUIRE(ahead, "%s: null ahead", fn);
-  GNNREC_REQUIRE((n_rows + 255) / 256 < (int64_t(1) << 31), "%s: too many rows", fn);
-  if (n_items == 0) {
-    const hipError_t e = hipMemsetAsync(ahead, 0, (size_t)n_rows * sizeof(int32_t),
-                                        as_stream(stream));
-    GNNREC_REQUIRE(e == hipSuccess, "%s: %s", fn, hipGetErrorString(e));
-    return GNNREC_OK;
-  }
-  GNNREC_REQUIRE(thr && gid && parts, "%s: null thr / gid / parts", fn);
-  return GNNREC_OK;
-}
-
-extern "C" int gnnrec_edge_mlp_dense_count_f32(const float* P, int64_t n_rows, const float* Q,
-                                               int64_t n_items, const float* W2, const float* b2,
-                                               const float* w3, const float* b3, const float* thr,
-                                               const int32_t* gid, int32_t* parts, int32_t* ahead,
-                                               void* stream) {
-  using namespace gnnrec;
-  const char* fn = "gnnrec_edge_mlp_dense_count_f32";
-  int rc = check_dense(fn, P, n_rows, Q, n_items, W2, b2, w3, b3);
-  if (rc != GNNREC_OK) return rc;
-  bool empty;
-  rc = dense_count_operands(fn, n_rows, n_items, thr, gid, parts, ahead, stream, &empty);
-  if (rc != GNNREC_OK || empty) return rc;
-  DenseMlpArgs a{};
-  a.m.P = P; a.m.Q = Q; a.m.W2 = W2; a.m.b2 = b2; a.m.w3 = w3; a.m.b3 = b3;
-  a.n_users = n_rows; a.n_cols = n_items;
-  a.tau = thr; a.gid = gid; a.ipart = parts;
-  return launch_dense_count(kDenseCount, fn, a, ahead, as_stream(stream));
-}
-
-extern "C" int gnnrec_edge_mlp_dense_count_rating_f32(
-    const float* P, int64_t n_rows, const float* Q, int64_t n_items, const float* W2,
-    const float* b2, const float* w3, const float* b3, const float* Z, const float* p_col,
-    const float* s, const int32_t* gid, int32_t* parts, int32_t* ahead, void* stream) {
-  using namespace gnnrec;
-  const char* fn = "gnnrec_edge_mlp_dense_count_rating_f32";
-  int rc = check_dense(fn, P, n_rows, Q, n_items, W2, b2, w3, b3);
-  if (rc != GNNREC_OK) return rc;
-  bool empty;
-  rc = dense_count_operands(fn, n_rows, n_items, s, gid, parts, ahead, stream, &empty);
-  if (rc != GNNREC_OK || empty) return rc;
-  GNNREC_REQUIRE(Z && p_col, "%s: null Z / p_col", fn);
-  DenseMlpArgs a{};
-  a.m.P = P; a.m.Q = Q; a.m.W2 = W2; a.m.b2 = b2; a.m.w3 = w3; a.m.b3 = b3;
-  a.n_users = n_rows; a.n_cols = n_items;
-  a.tau = s; a.gid = gid; a.ipart = parts; a.Z = Z; a.pcol = p_col;
-  return launch_dense_count(kDenseCountR, fn, a, ahead, as_stream(stream));
-}
-
-extern "C" int gnnrec_rank_resolve_mlp_f32(const int64_t* users, const int64_t* items,
-                                           const float* s, const int32_t* ahead, int64_t n_pairs,
-                                           int64_t n_users, const float* P, const float* Q,
-                                           int64_t n_items, const float* W2, const float* b2,
-                                           const float* w3, const float* b3, const float* Z,
-                                           const float* p_col, const int64_t* exclude_indptr,
-                                           const int32_t* exclude_indices, int64_t* rank,
-                                           float* vals, void* stream) {
-  using namespace gnnrec;
-  const char* fn = "gnnrec_rank_resolve_mlp_f32";
-  GNNREC_REQUIRE(n_pairs >= 0 && (n_pairs + kMlpWaves - 1) / kMlpWaves < (int64_t(1) << 31) &&
-                     n_users >= 0,
-                 "%s: bad size", fn);
-  const int rc = check_dense(fn, P, n_pairs, Q, n_items, W2, b2, w3, b3);
-  if (rc != GNNREC_OK) return rc;
-  GNNREC_REQUIRE(!exclude_indptr == !exclude_indices,
-                 "%s: exclusion indptr and indices come together", fn);
-  GNNREC_REQUIRE(!Z == !p_col, "%s: Z and p_col come together", fn);
-  if (n_pairs == 0) return GNNREC_OK;
-  GNNREC_REQUIRE(n_items > 0 && n_users > 0, "%s: pairs without users or items", fn);
-  GNNREC_REQUIRE(users && items && s && ahead && rank && vals, "%s: null pointer", fn);
-  EdgeMlpArgs m{};
-  m.P = P; m.Q = Q; m.W2 = W2; m.b2 = b2; m.w3 = w3; m.b3 = b3;
-  const dim3 grid((unsigned)((n_pairs + kMlpWaves - 1) / kMlpWaves)), block(256);
-  hipStream_t st = as_stream(stream);
-  if (Z)
-    hipLaunchKernelGGL(rank_resolve_mlp_kernel<true>, grid, block, 0, st, m, users, items, s,
-                       ahead, n_pairs, n_users, n_items, Z, p_col, exclude_indptr,
-                       exclude_indices, rank, vals);
-  else
-    hipLaunchKernelGGL(rank_resolve_mlp_kernel<false>, grid, block, 0, st, m, users, items, s,
-                       ahead, n_pairs, n_users, n_items, Z, p_col, exclude_indptr,
-                       exclude_indices, rank, vals);
-  return check_launch(fn);
-}
-
-// ---- the list forms of the full-ranking evaluation ----
+// ---- the full-ranking evaluation ----
 extern "C" int64_t gnnrec_rank_list_slots(void) { return gnnrec::kDenseListSlots; }
 
-// the slot operands of a list count pass, after check_dense; as dense_count_operands
+// the slot operands of a count pass, after check_dense: ahead is zeroed where there is nothing
+// to count, and no kernel is launched then
 static int dense_count_lists_operands(const char* fn, int64_t n_rows, int64_t n_items,
                                       const void* lptr, int64_t n_slots, const void* thr,
                                       const void* gid, const void* parts, int32_t* ahead,

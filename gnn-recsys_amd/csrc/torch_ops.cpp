@@ -1359,106 +1359,7 @@ void edge_mlp_dense_filter_rating(const Tensor& P, const Tensor& Q, const Tensor
 }
 
 // ---------------------------------------------------------------- f1f for the MLP head
-// the per-row operands of a count pass over B pair rows and n items -> nothing; all checked
-void dense_count_rows(const Tensor& thr, const Tensor& gid, const Tensor& parts,
-                      const Tensor& ahead, int64_t B, int64_t n) {
-  rating_vec(thr, "thr", B);
-  dev(gid, "gid", at::kInt);
-  dev(parts, "parts", at::kInt);
-  dev(ahead, "ahead", at::kInt);
-  TORCH_CHECK_VALUE(gid.numel() == B && ahead.numel() == B && gid.is_contiguous() &&
-                        ahead.is_contiguous(),
-                    "gid / ahead must be contiguous [", B, "]");
-  const int64_t n_part = gnnrec_cos_denominator_parts(n);
-  TORCH_CHECK_VALUE(parts.dim() == 2 && parts.size(0) == n_part && parts.size(1) == B &&
-                        parts.is_contiguous(),
-                    "parts must be a contiguous [", n_part, ", ", B, "], got ", parts.sizes());
-}
-
-void edge_mlp_dense_count(const Tensor& P, const Tensor& Q, const Tensor& W2, const Tensor& b2,
-                          const Tensor& w3, const Tensor& b3, const Tensor& thr,
-                          const Tensor& gid, Tensor& parts, Tensor& ahead) {
-  const OneDevice one_device_;
-  dense_mlp_tables(P, Q, W2, b2, w3, b3);
-  const int64_t B = P.size(0), n = Q.size(0);
-  dense_count_rows(thr, gid, parts, ahead, B, n);
-  if (meta(P)) return;
-  const c10::DeviceGuard g(P.device());
-  ck(gnnrec_edge_mlp_dense_count_f32(p<float>(P), B, p<float>(Q), n, p<float>(W2), p<float>(b2),
-                                     p<float>(w3), p<float>(b3), p<float>(thr), p<int32_t>(gid),
-                                     p<int32_t>(parts), p<int32_t>(ahead), stream_of(P)),
-     "gnnrec_edge_mlp_dense_count_f32");
-}
-
-void edge_mlp_dense_count_rating(const Tensor& P, const Tensor& Q, const Tensor& W2,
-                                 const Tensor& b2, const Tensor& w3, const Tensor& b3,
-                                 const Tensor& Z, const Tensor& p_col, const Tensor& s,
-                                 const Tensor& gid, Tensor& parts, Tensor& ahead) {
-  const OneDevice one_device_;
-  dense_mlp_tables(P, Q, W2, b2, w3, b3);
-  const int64_t B = P.size(0), n = Q.size(0);
-  rating_vec(Z, "Z", B);
-  rating_vec(p_col, "p_col", n);
-  dense_count_rows(s, gid, parts, ahead, B, n);
-  if (meta(P)) return;
-  const c10::DeviceGuard g(P.device());
-  ck(gnnrec_edge_mlp_dense_count_rating_f32(p<float>(P), B, p<float>(Q), n, p<float>(W2),
-                                            p<float>(b2), p<float>(w3), p<float>(b3),
-                                            p<float>(Z), p<float>(p_col), p<float>(s),
-                                            p<int32_t>(gid), p<int32_t>(parts),
-                                            p<int32_t>(ahead), stream_of(P)),
-     "gnnrec_edge_mlp_dense_count_rating_f32");
-}
-
-void rank_resolve_mlp(const Tensor& users, const Tensor& items, const Tensor& s,
-                      const Tensor& ahead, int64_t n_users, const Tensor& P, const Tensor& Q,
-                      const Tensor& W2, const Tensor& b2, const Tensor& w3, const Tensor& b3,
-                      const optional<Tensor>& Z, const optional<Tensor>& p_col,
-                      const optional<Tensor>& exclude_indptr,
-                      const optional<Tensor>& exclude_indices, Tensor& rank, Tensor& vals) {
-  const OneDevice one_device_;
-  dev(users, "users", at::kLong);
-  dev(items, "items", at::kLong);
-  dense_mlp_tables(P, Q, W2, b2, w3, b3);
-  dev(ahead, "ahead", at::kInt);
-  dev(exclude_indptr, "exclude_indptr", at::kLong);
-  dev(exclude_indices, "exclude_indices", at::kInt);
-  dev(rank, "rank", at::kLong);
-  const int64_t np = users.numel(), n = Q.size(0);
-  rating_vec(s, "s", np);
-  rating_vec(vals, "vals", np);
-  TORCH_CHECK_VALUE(P.size(0) == np, "P must hold one row per pair: [", np, ", 128], got ",
-                    P.sizes());
-  TORCH_CHECK_VALUE(items.numel() == np && ahead.numel() == np && rank.numel() == np &&
-                        users.is_contiguous() && items.is_contiguous() && ahead.is_contiguous() &&
-                        rank.is_contiguous(),
-                    "users / items / ahead / rank must be contiguous [", np, "]");
-  TORCH_CHECK_VALUE(n_users >= 0 && (np == 0 || (n_users > 0 && n > 0)),
-                    "pairs need users and items (n_users = ", n_users, ", n_items = ", n, ")");
-  TORCH_CHECK_VALUE(has(Z) == has(p_col), "Z and p_col come together");
-  if (has(Z)) {
-    rating_vec(*Z, "Z", np);
-    rating_vec(*p_col, "p_col", n);
-  }
-  TORCH_CHECK_VALUE(has(exclude_indptr) == has(exclude_indices),
-                    "exclude_indptr and exclude_indices come together");
-  TORCH_CHECK_VALUE(!has(exclude_indptr) ||
-                        (exclude_indptr->numel() == n_users + 1 &&
-                         exclude_indptr->is_contiguous() && exclude_indices->is_contiguous()),
-                    "exclude_indptr must be a contiguous [n_users + 1]");
-  if (meta(users)) return;
-  const c10::DeviceGuard g(users.device());
-  ck(gnnrec_rank_resolve_mlp_f32(p<int64_t>(users), p<int64_t>(items), p<float>(s),
-                                 p<int32_t>(ahead), np, n_users, p<float>(P), p<float>(Q), n,
-                                 p<float>(W2), p<float>(b2), p<float>(w3), p<float>(b3),
-                                 p<float>(Z), p<float>(p_col), p<int64_t>(exclude_indptr),
-                                 p<int32_t>(exclude_indices), p<int64_t>(rank), p<float>(vals),
-                                 stream_of(users)),
-     "gnnrec_rank_resolve_mlp_f32");
-}
-
-// ------------------------------------------------ f1f for the MLP head, the list forms
-// the slot operands of a list count pass over B rows and n items -> nothing; all checked
+// the slot operands of a count pass over B rows and n items -> nothing; all checked
 void dense_count_slots(const Tensor& lptr, const Tensor& thr, const Tensor& gid,
                        const Tensor& parts, const Tensor& ahead, int64_t B, int64_t n) {
   dev(lptr, "lptr", at::kLong);
@@ -2740,15 +2641,6 @@ TORCH_LIBRARY(gnnrec, m) {
   m.def("edge_mlp_dense_filter_rating_f32(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, "
         "Tensor b3, Tensor Z, Tensor p_col, Tensor tau, Tensor(a!) counts, "
         "Tensor(b!) cand_items, Tensor(c!) cand_scores) -> ()");
-  m.def("edge_mlp_dense_count_f32(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, Tensor b3, "
-        "Tensor thr, Tensor gid, Tensor(a!) parts, Tensor(b!) ahead) -> ()");
-  m.def("edge_mlp_dense_count_rating_f32(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, "
-        "Tensor b3, Tensor Z, Tensor p_col, Tensor s, Tensor gid, Tensor(a!) parts, "
-        "Tensor(b!) ahead) -> ()");
-  m.def("rank_resolve_mlp_f32(Tensor users, Tensor items, Tensor s, Tensor ahead, int n_users, "
-        "Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor? Z, "
-        "Tensor? p_col, Tensor? exclude_indptr, Tensor? exclude_indices, Tensor(a!) rank, "
-        "Tensor(b!) vals) -> ()");
   m.def("edge_mlp_dense_count_lists_f32(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, "
         "Tensor b3, Tensor lptr, Tensor thr, Tensor gid, Tensor(a!) parts, Tensor(b!) ahead) "
         "-> ()");
@@ -2910,9 +2802,6 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("fold_partials_f32", &fold_partials_f32);       \
   m.impl("edge_mlp_dense_store_rating_f32", &edge_mlp_dense_store_rating); \
   m.impl("edge_mlp_dense_filter_rating_f32", &edge_mlp_dense_filter_rating); \
-  m.impl("edge_mlp_dense_count_f32", &edge_mlp_dense_count); \
-  m.impl("edge_mlp_dense_count_rating_f32", &edge_mlp_dense_count_rating); \
-  m.impl("rank_resolve_mlp_f32", &rank_resolve_mlp);     \
   m.impl("edge_mlp_dense_count_lists_f32", &edge_mlp_dense_count_lists); \
   m.impl("edge_mlp_dense_count_lists_rating_f32", &edge_mlp_dense_count_lists_rating); \
   m.impl("rank_resolve_mlp_lists_f32", &rank_resolve_mlp_lists); \

@@ -198,14 +198,7 @@ SIGNATURES = {
                                                       _P, _I64, _P]),
     "gnnrec_edge_mlp_dense_filter_rating_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P,
                                                        _P, _P, _P, _P, _I64, _P]),
-    # full-ranking evaluation for the MLP head (csrc/heads.hip)
-    "gnnrec_edge_mlp_dense_count_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
-                                               _P]),
-    "gnnrec_edge_mlp_dense_count_rating_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P,
-                                                      _P, _P, _P, _P, _P]),
-    "gnnrec_rank_resolve_mlp_f32": (_INT, [_P, _P, _P, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P,
-                                           _P, _P, _P, _P, _P, _P, _P, _P]),
-    # its list forms: one scored row per user (csrc/heads.hip)
+    # full-ranking evaluation for the MLP head: one scored row per user (csrc/heads.hip)
     "gnnrec_rank_list_slots": (_I64, []),
     "gnnrec_edge_mlp_dense_count_lists_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64,
                                                      _P, _P, _P, _P, _P]),

@@ -2190,80 +2190,10 @@ def rank_resolve(users: torch.Tensor, items: torch.Tensor, thr: torch.Tensor,
     return out
 
 
-# ---- f1f for the MLP head (csrc/heads.hip) ----
-def _count_rows(P, Q, s, gid):
-    _dev(s, "thr", torch.float32)
-    _dev(gid, "gid", torch.int32)
-    R = P.shape[0]
-    parts = torch.empty((denominator_parts(Q.shape[0]), R), dtype=torch.int32, device=P.device)
-    ahead = torch.empty(R, dtype=torch.int32, device=P.device)
-    return parts, ahead
-
-
-def edge_mlp_dense_count(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor,
-                         w3: torch.Tensor, b3: torch.Tensor, thr: torch.Tensor,
-                         gid: torch.Tensor) -> torch.Tensor:
-    """One pass of the dense MLP kernel over all item rows of Q for the pair rows of P [R, 128]
-    (row r: the P row of pair r's user): -> ahead int32 [R], the items v != gid[r] (int32: the
-    pair's held-out item) with score > thr[r], or == thr[r] and v < gid[r].  thr[r] is
-    edge_mlp's score of the pair; the compared scores are bitwise edge_mlp's, so there is no
-    band and no candidate list."""
-    ops = _dense_mlp_operands(P, Q, W2, b2, w3, b3)
-    parts, ahead = _count_rows(P, Q, thr, gid)
-    _T().edge_mlp_dense_count_f32(*ops, thr, gid, parts, ahead)
-    return ahead
-
-
-def edge_mlp_dense_count_rating(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor,
-                                b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor,
-                                Z: torch.Tensor, p_col: torch.Tensor, s: torch.Tensor,
-                                gid: torch.Tensor) -> torch.Tensor:
-    """edge_mlp_dense_count on R = expf(score) / Z[r] + p_col[v]; the row's threshold is its
-    own R = expf(s[r]) / Z[r] + p_col[gid[r]], formed in the kernel from the pair's raw score
-    s[r] by the same function."""
-    ops = _dense_mlp_operands(P, Q, W2, b2, w3, b3)
-    _dev(Z, "Z", torch.float32)
-    _dev(p_col, "p_col", torch.float32)
-    parts, ahead = _count_rows(P, Q, s, gid)
-    _T().edge_mlp_dense_count_rating_f32(*ops, Z, p_col, s, gid, parts, ahead)
-    return ahead
-
-
-def rank_resolve_mlp(users: torch.Tensor, items: torch.Tensor, s: torch.Tensor,
-                     ahead: torch.Tensor, n_users: int, P: torch.Tensor, Q: torch.Tensor,
-                     W2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor,
-                     exclude_indptr: Optional[torch.Tensor] = None,
-                     exclude_indices: Optional[torch.Tensor] = None,
-                     Z: Optional[torch.Tensor] = None, p_col: Optional[torch.Tensor] = None,
-                     out: Optional[torch.Tensor] = None, vals: Optional[torch.Tensor] = None):
-    """Per pair (users[r], items[r]) with P row r and raw score s[r]: rank = 1 + ahead[r] - (the
-    user's excluded items exactly ahead), 0 where the item is excluded -> (rank int64 [P],
-    vals fp32 [P]); vals = s, or with Z [P] and p_col [n_items] the pairs' R (the excluded
-    items are then compared by R).  The exclusion CSR (over n_users users, int32) holds each
-    id at most once per row; entries < 0 or past the table are skipped.  Scores are bitwise
-    edge_mlp's."""
-    _dev(users, "users", torch.int64)
-    _dev(items, "items", torch.int64)
-    _dev(s, "s", torch.float32)
-    _dev(ahead, "ahead", torch.int32)
-    ops = _dense_mlp_operands(P, Q, W2, b2, w3, b3)
-    if Z is not None:
-        _dev(Z, "Z", torch.float32)
-    if p_col is not None:
-        _dev(p_col, "p_col", torch.float32)
-    if out is None:
-        out = torch.empty(users.numel(), dtype=torch.int64, device=users.device)
-    if vals is None:
-        vals = torch.empty(users.numel(), dtype=torch.float32, device=users.device)
-    _T().rank_resolve_mlp_f32(users, items, s, ahead, int(n_users), *ops, Z, p_col,
-                              exclude_indptr, exclude_indices, out, vals)
-    return out, vals
-
-
-# ---- the list forms: one scored row per user (csrc/heads.hip, DESIGN.md §26) ----
+# ---- f1f for the MLP head: one scored row per user (csrc/heads.hip) ----
 def rank_list_slots() -> int:
-    """List entries a row of the list count pass holds at most (kDenseListSlots); a longer
-    list is split over rows that repeat the user's P row."""
+    """Entries a row of the count pass holds at most (kDenseListSlots); a longer list is split
+    over rows that repeat the user's P row."""
     return int(_T().rank_list_slots())
 
 
@@ -2281,11 +2211,13 @@ def edge_mlp_dense_count_lists(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tenso
                                b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor,
                                lptr: torch.Tensor, thr: torch.Tensor,
                                gid: torch.Tensor) -> torch.Tensor:
-    """edge_mlp_dense_count with one scored row for several entries: row r of P [R, 128] (a
-    user, or rank_list_slots() entries of a longer list) owns the slots [lptr[r], lptr[r + 1])
-    (int64 [R + 1], at most rank_list_slots() a row) of thr (the entry's own edge_mlp score)
-    and gid (its item, int32) -> ahead int32 [E], per slot the count edge_mlp_dense_count gives
-    the pair (row, gid)."""
+    """One pass of the dense MLP kernel over all item rows of Q with one scored row for several
+    entries: row r of P [R, 128] (a user, rank_list_slots() entries of a longer list, or a
+    single pair) owns the slots [lptr[r], lptr[r + 1]) (int64 [R + 1], at most
+    rank_list_slots() a row) of thr (the entry's own edge_mlp score) and gid (its held-out
+    item, int32) -> ahead int32 [E], per slot j the items v != gid[j] with score > thr[j], or
+    == thr[j] and v < gid[j].  The compared scores are bitwise edge_mlp's, so there is no band
+    and no candidate list."""
     ops = _dense_mlp_operands(P, Q, W2, b2, w3, b3)
     parts, ahead = _count_slots(Q, lptr, thr, gid)
     _T().edge_mlp_dense_count_lists_f32(*ops, lptr, thr, gid, parts, ahead)
@@ -2316,9 +2248,13 @@ def rank_resolve_mlp_lists(row_user: torch.Tensor, lptr: torch.Tensor, s: torch.
                            p_col: Optional[torch.Tensor] = None,
                            out: Optional[torch.Tensor] = None,
                            vals: Optional[torch.Tensor] = None):
-    """rank_resolve_mlp for the rows of a list count pass: row r (P row r, user row_user[r],
-    slots [lptr[r], lptr[r + 1]) of s / gid / ahead) walks its user's exclusion row once and
-    resolves every slot from the same scores -> (rank int64 [E], vals fp32 [E]); Z is per row."""
+    """Per row r of a count pass (P row r, user row_user[r], slots [lptr[r], lptr[r + 1]) of
+    s / gid / ahead): the row walks its user's exclusion row once and resolves every slot from
+    the same scores, rank = 1 + ahead[j] - (the user's excluded items exactly ahead), 0 where
+    the slot's item is excluded -> (rank int64 [E], vals fp32 [E]); vals = s, or with Z [R]
+    (per row) and p_col [n_items] the entries' R (the excluded items are then compared by R).
+    The exclusion CSR (over n_users users, int32) holds each id at most once per row; entries
+    < 0 or past the table are skipped.  Scores are bitwise edge_mlp's."""
     _dev(row_user, "row_user", torch.int64)
     _dev(lptr, "lptr", torch.int64)
     _dev(s, "s", torch.float32)

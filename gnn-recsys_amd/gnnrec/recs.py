@@ -613,29 +613,23 @@ def _ranks_exact(scorer, users, items, vals, exclude, rank, out_pos, Z=None):
         rank[out_pos[c0:c0 + step]] = out
 
 
-def _rank_items_mlp(scorer, users, items, exclude, batch_size, rank, vals):
-    """rank_items' loop for the MLP head (scorer: a _MlpHead whose Q is formed; exclude: the
-    distinct exclusion CSR or (None, None)).  Per batch of pairs: P of the pairs' users, the
-    pairs' own edge_mlp scores, one count pass over all items, one resolve launch.  No host
-    read: there is nothing to overflow."""
-    ex0, ex1 = exclude
-    n_users = scorer.h_user.shape[0]
-    for b0 in range(0, users.numel(), batch_size):
-        ub, gb = users[b0:b0 + batch_size], items[b0:b0 + batch_size]
-        cut = slice(b0, b0 + ub.numel())
-        P = scorer.P(ub)
-        s = ops.edge_mlp(torch.arange(ub.numel(), device=ub.device), gb, P, scorer.Q,
-                         *scorer.tail)
-        gid = gb.to(torch.int32)
-        if scorer.p is None:
-            Z = None
-            ahead = ops.edge_mlp_dense_count(P, scorer.Q, *scorer.tail, s, gid)
-        else:
-            Z = scorer.denominators(P)          # recommend's Z_u: the same bits in any batch
-            ahead = ops.edge_mlp_dense_count_rating(P, scorer.Q, *scorer.tail, Z, scorer.p, s,
-                                                    gid)
-        ops.rank_resolve_mlp(ub, gb, s, ahead, n_users, P, scorer.Q, *scorer.tail, ex0, ex1, Z,
-                             scorer.p, rank[cut], vals[cut])
+def _rank_rows_mlp(scorer, P, Z, row_user, lptr, row, items, exclude, rank, vals):
+    """One batch of the MLP head's full-ranking evaluation (scorer: a _MlpHead whose Q is
+    formed).  P [R, 128]: the rows' P rows; Z [R]: their denominators, or None without a
+    popularity; row_user [R]: the rows' users; lptr [R + 1]: row r's entries are the slots
+    [lptr[r], lptr[r + 1]); row / items [E]: each entry's row and its held-out item; exclude: the
+    distinct exclusion CSR or (None, None); rank / vals [E]: the output slices.  The entries'
+    own edge_mlp scores, one count pass over all items, one resolve launch.  No host read:
+    there is nothing to overflow."""
+    s = ops.edge_mlp(row, items, P, scorer.Q, *scorer.tail)
+    gid = items.to(torch.int32)
+    if Z is None:
+        ahead = ops.edge_mlp_dense_count_lists(P, scorer.Q, *scorer.tail, lptr, s, gid)
+    else:
+        ahead = ops.edge_mlp_dense_count_lists_rating(P, scorer.Q, *scorer.tail, Z, scorer.p,
+                                                      lptr, s, gid)
+    ops.rank_resolve_mlp_lists(row_user, lptr, s, gid, ahead, scorer.h_user.shape[0], P,
+                               scorer.Q, *scorer.tail, *exclude, Z, scorer.p, rank, vals)
 
 
 def rank_items(h_user, h_item, users, items, exclude=None, *, batch_size=8192, cand_cap=1024,
@@ -676,12 +670,13 @@ def rank_items(h_user, h_item, users, items, exclude=None, *, batch_size=8192, c
     and the repeats as above.  Q = h_item W1b^T is formed once per call; per
     batch of pairs P = h_user[users] W1a^T + b1, the pairs' own scores (ops.edge_mlp), one pass
     of the dense MLP kernel over all items whose epilogue counts the items exactly ahead
-    (ops.edge_mlp_dense_count), and ops.rank_resolve_mlp, which rescores the user's excluded
-    items with the same bits and subtracts those exactly ahead.  The pass compares the final
-    fp32 score — the very value the ranking is defined on — so there is no error bound, no
-    band, no overflow and no exhaustive redo: cand_cap is accepted and unused, the stats are
-    fast_path True, band_mean 0.0, band_max 0, overflow_rows 0, eps 0.0, and the id check is
-    the call's only host read.
+    (ops.edge_mlp_dense_count_lists, each pair a row with one entry: rank_lists' kernels, which
+    share a row among a user's entries), and ops.rank_resolve_mlp_lists, which rescores the
+    user's excluded items with the same bits and subtracts those exactly ahead.  The pass
+    compares the final fp32 score — the very value the ranking is defined on — so there is no
+    error bound, no band, no overflow and no exhaustive redo: cand_cap is accepted and unused,
+    the stats are fast_path True, band_mean 0.0, band_max 0, overflow_rows 0, eps 0.0, and the
+    id check is the call's only host read.
 
     popularity (with head=): a fp32 device tensor [n_items] or [n_items, 1], as for recommend.
     The ranking is by R(u, v) = expf(s(u, v)) / Z_u + popularity[v] * weight_popularity, Z_u
@@ -751,7 +746,16 @@ def rank_items(h_user, h_item, users, items, exclude=None, *, batch_size=8192, c
         ex = (None, None) if exclude is None else \
             _distinct_exclusions(exclude, served, *sizes, n_items)
         vals = torch.empty(P, dtype=torch.float32, device=dev)
-        _rank_items_mlp(scorer, users, items, ex, batch_size, rank, vals)
+        rows = torch.arange(min(batch_size, P) + 1, device=dev)     # a pair is a one-slot row
+        for b0 in range(0, P, batch_size):
+            ub = users[b0:b0 + batch_size]
+            n = ub.numel()
+            cut = slice(b0, b0 + n)
+            Pb = scorer.P(ub)
+            # recommend's Z_u: the same bits in any batch
+            Z = None if p is None else scorer.denominators(Pb)
+            _rank_rows_mlp(scorer, Pb, Z, ub, rows[:n + 1], rows[:n], items[cut], ex, rank[cut],
+                           vals[cut])
         stats['fast_path'] = True
         return (rank, vals, stats) if return_stats else (rank, vals)
     vals = ops.sddmm_cos(users, items, h_user, h_item)
@@ -909,39 +913,6 @@ def _lists_check(user_rows, gt_indptr, gt_indices, n_users, n_items, extra=()):
     return lens, served, n_pairs, got[len(head):]
 
 
-def _rank_lists_mlp(scorer, user_rows, pairs, plan, cuts, exclude, batch_size, rank, vals):
-    """rank_lists' loop for the MLP head.  pairs: (users, items, owner) of every served entry;
-    plan: _list_row_plan's (owner, lptr) over all served users; cuts: per batch boundary the
-    slots and the rows before it (host ints, read with the id check).  Per batch of users: P,
-    Z with a popularity, the entries' own scores, one list count pass, one list resolve."""
-    ex0, ex1 = exclude
-    _, items, owner = pairs
-    row_owner, lptr = plan
-    n_users = scorer.h_user.shape[0]
-    for i, u0 in enumerate(range(0, user_rows.numel(), batch_size)):
-        (e0, r0), (e1, r1) = cuts[i], cuts[i + 1]
-        if e1 == e0:
-            continue
-        ub = user_rows[u0:u0 + batch_size]
-        P = scorer.P(ub)                                   # one row per user
-        gb = items[e0:e1]
-        s = ops.edge_mlp(owner[e0:e1] - u0, gb, P, scorer.Q, *scorer.tail)
-        gid = gb.to(torch.int32)
-        ro = row_owner[r0:r1] - u0
-        lp = (lptr[r0:r1 + 1] - e0).contiguous()
-        Pr = P[ro]                                         # a long list's rows repeat the P row
-        if scorer.p is None:
-            Zr = None
-            ahead = ops.edge_mlp_dense_count_lists(Pr, scorer.Q, *scorer.tail, lp, s, gid)
-        else:
-            Zr = scorer.denominators(P)[ro].contiguous()   # recommend's Z_u, per user
-            ahead = ops.edge_mlp_dense_count_lists_rating(Pr, scorer.Q, *scorer.tail, Zr,
-                                                          scorer.p, lp, s, gid)
-        ops.rank_resolve_mlp_lists(ub[ro].contiguous(), lp, s, gid, ahead, n_users, Pr, scorer.Q,
-                                   *scorer.tail, ex0, ex1, Zr, scorer.p, rank[e0:e1],
-                                   vals[e0:e1])
-
-
 def _rank_lists(h_user, h_item, user_rows, gt_indptr, gt_indices, exclude, head, popularity,
                 weight_popularity, batch_size, cand_cap):
     """rank_lists -> (rank, vals, stats, users, items)."""
@@ -1023,7 +994,20 @@ def _rank_lists(h_user, h_item, user_rows, gt_indptr, gt_indices, exclude, head,
     plan = _list_row_plan(lens, budget, cuts[-1][1])
     rank = torch.empty(E, dtype=torch.int64, device=dev)
     vals = torch.empty(E, dtype=torch.float32, device=dev)
-    _rank_lists_mlp(scorer, user_rows, pairs, plan, cuts, ex, batch_size, rank, vals)
+    items, (row_owner, lptr) = pairs[1], plan
+    for i, u0 in enumerate(range(0, U, batch_size)):    # per batch of users: one P row each
+        (e0, r0), (e1, r1) = cuts[i], cuts[i + 1]
+        if e1 == e0:
+            continue
+        ub = user_rows[u0:u0 + batch_size]
+        Pu = scorer.P(ub)
+        ro = row_owner[r0:r1] - u0                      # a long list's rows repeat the P row
+        lp = (lptr[r0:r1 + 1] - e0).contiguous()
+        row = torch.repeat_interleave(torch.arange(r1 - r0, device=dev), lp[1:] - lp[:-1],
+                                      output_size=e1 - e0)
+        Z = None if p is None else scorer.denominators(Pu)[ro].contiguous()   # recommend's Z_u
+        _rank_rows_mlp(scorer, Pu[ro], Z, ub[ro].contiguous(), lp, row, items[e0:e1], ex,
+                       rank[e0:e1], vals[e0:e1])
     stats.update(rows=cuts[-1][1], pairs=E)
     return rank, vals, stats, pairs[0], pairs[1]
 

@@ -856,54 +856,21 @@ int gnnrec_edge_mlp_dense_filter_rating_f32(const float* P, int64_t n_users, con
                                             const float* p_col, const float* tau, int32_t* counts,
                                             int32_t* cand_items, float* cand_scores, int64_t cap,
                                             void* stream);
-/* ---- f1f for the MLP head: exact rank among all items (csrc/heads.hip, DESIGN.md §24) ----
- * Rows are pairs (u_r, g_r): P [n_rows, 128] holds the P row of u_r, gid[r] = g_r (int32),
- * thr[r] = gnnrec_edge_mlp_f32's score of the pair.  One pass over all items with the dense
- * kernel's arithmetic: ahead[r] (int32) = #{v != gid[r] : score(r, v) > thr[r] or (score(r, v)
- * == thr[r] and v < gid[r])}.  The compared value is the final fp32 score: no band, no
- * candidate list.  parts: workspace [gnnrec_cos_denominator_parts(n_items), n_rows] int32.
- * n_rows = 0 does nothing; n_items = 0 launches nothing and writes ahead = 0. */
-int gnnrec_edge_mlp_dense_count_f32(const float* P, int64_t n_rows, const float* Q,
-                                    int64_t n_items, const float* W2, const float* b2,
-                                    const float* w3, const float* b3, const float* thr,
-                                    const int32_t* gid, int32_t* parts, int32_t* ahead,
-                                    void* stream);
-/* The same count on R(r, v) = expf(score) / Z[r] + p_col[v] against the row's own
- * R = expf(s[r]) / Z[r] + p_col[gid[r]], both formed in the kernel by one inline function
- * (s[r]: the pair's raw score, Z [n_rows], p_col [n_items]). */
-int gnnrec_edge_mlp_dense_count_rating_f32(const float* P, int64_t n_rows, const float* Q,
-                                           int64_t n_items, const float* W2, const float* b2,
-                                           const float* w3, const float* b3, const float* Z,
-                                           const float* p_col, const float* s, const int32_t* gid,
-                                           int32_t* parts, int32_t* ahead, void* stream);
-/* Per pair r = (users[r], items[r]), P [n_pairs, 128] the P row of users[r] and s[r] its raw
- * score: the items of exclude_indices[exclude_indptr[u] .. exclude_indptr[u+1]) (a CSR over the
- * n_users users, int32, each id at most once per row, entries < 0 or >= n_items skipped; both
- * pointers may be NULL) are scored with gnnrec_edge_mlp_f32's bits (Z [n_pairs] and p_col given:
- * turned into R) and those exactly ahead of items[r] counted:
- * rank[r] = 1 + ahead[r] - (excluded items exactly ahead), or 0 where items[r] is excluded.
- * vals[r] = s[r], or the pair's R.  Z and p_col come together or are both NULL.  Pairs with an
- * id out of range are left unwritten. */
-int gnnrec_rank_resolve_mlp_f32(const int64_t* users, const int64_t* items, const float* s,
-                                const int32_t* ahead, int64_t n_pairs, int64_t n_users,
-                                const float* P, const float* Q, int64_t n_items, const float* W2,
-                                const float* b2, const float* w3, const float* b3, const float* Z,
-                                const float* p_col, const int64_t* exclude_indptr,
-                                const int32_t* exclude_indices, int64_t* rank, float* vals,
-                                void* stream);
-/* ---- the list forms of f1f for the MLP head (csrc/heads.hip) ----
+/* ---- f1f for the MLP head: exact rank among all items (csrc/heads.hip, DESIGN.md §24, §26) ----
  * A row is a USER (or gnnrec_rank_list_slots() entries of a longer held-out list: the caller
- * splits a long list over rows that repeat the user's P row): P [n_rows, 128], and row r's
- * entries are the slots [lptr[r], lptr[r + 1]) (lptr int64 [n_rows + 1], ascending from 0 to
- * n_slots, at most gnnrec_rank_list_slots() slots a row) of thr (the entry's own
- * gnnrec_edge_mlp_f32 score) and gid (its item, int32; an id < 0 or >= n_items is compared as
- * it is and reads nothing).  The row is scored once per item tile and every slot counted from
- * those scores: ahead[j] = gnnrec_edge_mlp_dense_count_f32's count for the pair (row of j,
- * gid[j]).  parts: workspace [gnnrec_cos_denominator_parts(n_items), n_slots] int32.  A row
- * whose bounds lie outside [0, n_slots], or that spans more than gnnrec_rank_list_slots()
- * slots, is out of contract and has no slots: nothing is read or written for it, and ahead[j]
- * of a slot that no valid row covers is undefined (lptr lives on the device: the entry cannot
- * refuse it).  n_slots = 0 does nothing; n_items = 0 launches nothing and writes ahead = 0. */
+ * splits a long list over rows that repeat the user's P row; a single pair is a row with one
+ * slot): P [n_rows, 128], and row r's entries are the slots [lptr[r], lptr[r + 1]) (lptr int64
+ * [n_rows + 1], ascending from 0 to n_slots, at most gnnrec_rank_list_slots() slots a row) of
+ * thr (the entry's own gnnrec_edge_mlp_f32 score) and gid (its item, int32; an id < 0 or
+ * >= n_items is compared as it is and reads nothing).  One pass over all items with the dense
+ * kernel's arithmetic, the row scored once per item tile and every slot counted from those
+ * scores: ahead[j] (int32) = #{v != gid[j] : score(r, v) > thr[j] or (score(r, v) == thr[j]
+ * and v < gid[j])}.  The compared value is the final fp32 score: no band, no candidate list.
+ * parts: workspace [gnnrec_cos_denominator_parts(n_items), n_slots] int32.  A row whose bounds
+ * lie outside [0, n_slots], or that spans more than gnnrec_rank_list_slots() slots, is out of
+ * contract and has no slots: nothing is read or written for it, and ahead[j] of a slot that no
+ * valid row covers is undefined (lptr lives on the device: the entry cannot refuse it).
+ * n_slots = 0 does nothing; n_items = 0 launches nothing and writes ahead = 0. */
 int64_t gnnrec_rank_list_slots(void);
 int gnnrec_edge_mlp_dense_count_lists_f32(const float* P, int64_t n_rows, const float* Q,
                                           int64_t n_items, const float* W2, const float* b2,
@@ -919,10 +886,13 @@ int gnnrec_edge_mlp_dense_count_lists_rating_f32(const float* P, int64_t n_rows,
                                                  int64_t n_slots, const float* s,
                                                  const int32_t* gid, int32_t* parts,
                                                  int32_t* ahead, void* stream);
-/* gnnrec_rank_resolve_mlp_f32 for the rows of that plan: row_user[r] (int64) names the user
- * whose exclusion row is walked — once per row, each tile of 32 entries scored once — and every
- * slot j of the row gets rank[j] = 1 + ahead[j] - (excluded items exactly ahead of slot j), or
- * 0 where gid[j] is excluded, and vals[j] = s[j] or the slot's R (Z [n_rows] and p_col given).
+/* Per row r of that plan, P [n_rows, 128] its P row and row_user[r] (int64) its user u: the
+ * items of exclude_indices[exclude_indptr[u] .. exclude_indptr[u+1]) (a CSR over the n_users
+ * users, int32, each id at most once per row, entries < 0 or >= n_items skipped; both pointers
+ * may be NULL) are scored with gnnrec_edge_mlp_f32's bits (Z [n_rows] and p_col given: turned
+ * into R) — the row walked once, each tile of 32 entries scored once — and every slot j of the
+ * row gets rank[j] = 1 + ahead[j] - (excluded items exactly ahead of slot j), or 0 where gid[j]
+ * is excluded, and vals[j] = s[j] or the slot's R.  Z and p_col come together or are both NULL.
  * Slots whose item, and rows whose user, are out of range are left unwritten. */
 int gnnrec_rank_resolve_mlp_lists_f32(const int64_t* row_user, const int64_t* lptr,
                                       int64_t n_rows, const float* s, const int32_t* gid,

@@ -273,6 +273,8 @@ def _by_user(users):
 @pytest.mark.parametrize("d", mc.DIMS)
 @pytest.mark.parametrize("kind", mc.KINDS)
 def test_rank_lists_is_the_definition_and_rank_items(kind, d):
+    """rank_items(head=) now runs the same kernels on the expanded pairs, one slot a row, so its
+    half is no longer independent evidence: the definition half carries the proof."""
     hu, hi, pl, S, excl, ip, ix, lu, lg, want_ex, want_plain = _lists_case(kind, d)
     lens = np.diff(ip)
     assert lens[rl.EMPTY_USER] == 0 and lens[rl.SINGLE_USER] == 1 and lens[rl.LONG_USER] == rl.LONG

@@ -1,7 +1,7 @@
 """GPU checks of the full-ranking evaluation for the MLP head (gnnrec.recs.rank_items(head=) /
-rank_for_graph, the counting epilogues of the dense MLP kernel and rank_resolve_mlp in
-csrc/heads.hip).  The reference for every value is ops.edge_mlp over the
-expanded pair list — the per-edge kernel, not the code under test — and for every rank the
+rank_for_graph, the counting epilogues of the dense MLP kernel and its resolve kernel in
+csrc/heads.hip with every pair a one-slot row).  The reference for
+every value is ops.edge_mlp over the expanded pair list — the per-edge kernel, not the code under test — and for every rank the
 definition of tests/rank_cases.py applied to that matrix (to ops.rating_rows_ of it for the
 popularity-weighted form).  Everything is exact: ranks are compared with assert_array_equal,
 values bit for bit.  tests/test_rank_mlp_cpu.py shows on the host that the saturated head and
@@ -114,7 +114,8 @@ def _kernel_case(saturated):
 
 
 def _count_with_guard(op, lead, s, gid, n_rows, n_items):
-    """The torch op itself, its parts a view into a guarded buffer -> (ahead, parts)."""
+    """The torch op itself with every row a single slot (lptr = 0 .. n_rows), its parts a view
+    into a guarded buffer -> ahead."""
     from gnnrec import ops
     n_part = ops.denominator_parts(n_items)
     assert n_part == (n_items + 1023) // 1024
@@ -122,7 +123,7 @@ def _count_with_guard(op, lead, s, gid, n_rows, n_items):
     buf = torch.full((n_part * n_rows + guard,), -7, dtype=torch.int32, device="cuda")
     parts = buf[:n_part * n_rows].view(n_part, n_rows)
     ahead = torch.full((n_rows,), -7, dtype=torch.int32, device="cuda")
-    op(*lead, s, gid, parts, ahead)
+    op(*lead, torch.arange(n_rows + 1, device="cuda"), s, gid, parts, ahead)
     torch.cuda.synchronize()
     assert (buf[n_part * n_rows:] == -7).all()          # nothing past the last chunk's row
     assert (parts >= 0).all()                            # every (chunk, row) slot written
@@ -148,7 +149,8 @@ def test_count_is_the_definition_without_exclusions(n_rows, saturated):
         gid = _cu(g.astype(np.int32))
         thr = S[:n_rows, :n_items][torch.arange(n_rows, device="cuda"), _cu(g)].contiguous()
         lead = (P[:n_rows].contiguous(), Q[:n_items].contiguous(), *tail)
-        ahead = _count_with_guard(T.edge_mlp_dense_count_f32, lead, thr, gid, n_rows, n_items)
+        ahead = _count_with_guard(T.edge_mlp_dense_count_lists_f32, lead, thr, gid, n_rows,
+                                  n_items)
         np.testing.assert_array_equal(ahead, rk.ranks(Sn, rows, g) - 1, err_msg=f"{n_items} items")
 
 
@@ -167,7 +169,7 @@ def test_count_rating_is_the_definition_without_exclusions(n_rows, n_items):
     R = ops.rating_rows_(S[:n_rows, :n_items].contiguous().clone(), Z, p).cpu().numpy()
     g = np.random.default_rng([7, n_rows, n_items]).integers(0, n_items, n_rows)
     s = S[:n_rows, :n_items][torch.arange(n_rows, device="cuda"), _cu(g)].contiguous()
-    ahead = _count_with_guard(T.edge_mlp_dense_count_rating_f32, (Pn, Qn, *tail, Z, p), s,
+    ahead = _count_with_guard(T.edge_mlp_dense_count_lists_rating_f32, (Pn, Qn, *tail, Z, p), s,
                               _cu(g.astype(np.int32)), n_rows, n_items)
     np.testing.assert_array_equal(ahead, rk.ranks(R, np.arange(n_rows), g) - 1)
 
@@ -177,12 +179,14 @@ def test_count_of_nothing():
     from gnnrec import ops
     pl, P, Q, _ = _kernel_case(False)
     none_f, none_i = torch.zeros(0, device="cuda"), torch.zeros(0, dtype=torch.int32, device="cuda")
-    assert ops.edge_mlp_dense_count(P[:0], Q, *_tail(pl), none_f, none_i).numel() == 0
+    lptr = torch.arange(6, device="cuda")
+    assert ops.edge_mlp_dense_count_lists(P[:0], Q, *_tail(pl), lptr[:1], none_f,
+                                          none_i).numel() == 0
     thr, gid = torch.zeros(5, device="cuda"), torch.zeros(5, dtype=torch.int32, device="cuda")
-    assert (ops.edge_mlp_dense_count(P[:5], Q[:0], *_tail(pl), thr, gid) == 0).all()
+    assert (ops.edge_mlp_dense_count_lists(P[:5], Q[:0], *_tail(pl), lptr, thr, gid) == 0).all()
     Z = torch.ones(5, device="cuda")
-    assert (ops.edge_mlp_dense_count_rating(P[:5], Q[:0], *_tail(pl), Z, none_f, thr, gid)
-            == 0).all()
+    assert (ops.edge_mlp_dense_count_lists_rating(P[:5], Q[:0], *_tail(pl), Z, none_f, lptr, thr,
+                                                  gid) == 0).all()
 
 
 # ---------------------------------------------------------------- 2. the definition

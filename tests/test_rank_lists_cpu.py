@@ -205,6 +205,9 @@ def test_meta_dense_count_lists():
     with pytest.raises(ValueError, match="parts must be a contiguous"):
         T.edge_mlp_dense_count_lists_f32(P, Q, *tail, lptr, thr, gid, _meta(5, 130, dtype=i32),
                                          ahead)
+    with pytest.raises(ValueError, match="parts must be a contiguous"):
+        T.edge_mlp_dense_count_lists_f32(P, Q, *tail, lptr, thr, gid, _meta(5 * E, dtype=i32),
+                                         ahead)
     with pytest.raises(ValueError, match="parts must be Int"):
         T.edge_mlp_dense_count_lists_f32(P, Q, *tail, lptr, thr, gid, _meta(5, E), ahead)
     with pytest.raises(ValueError, match="ahead must be Int"):
@@ -217,8 +220,16 @@ def test_meta_dense_count_lists():
     with pytest.raises(ValueError, match="gid / ahead"):
         T.edge_mlp_dense_count_lists_f32(P, Q, *tail, lptr, thr, _meta(E + 1, dtype=i32), parts,
                                          ahead)
+    with pytest.raises(ValueError, match="gid / ahead must be contiguous \\[699\\]"):   # E is thr's
+        T.edge_mlp_dense_count_lists_f32(P, Q, *tail, lptr, _meta(E - 1), gid, parts, ahead)
+    with pytest.raises(ValueError, match="gid / ahead"):
+        T.edge_mlp_dense_count_lists_f32(P, Q, *tail, lptr, thr, gid, parts,
+                                         _meta(E - 1, dtype=i32))
     with pytest.raises(ValueError, match="128/32 hidden sizes"):
         T.edge_mlp_dense_count_lists_f32(_meta(130, 64), Q, *tail, lptr, thr, gid, parts, ahead)
+    with pytest.raises(ValueError, match="128/32 hidden sizes"):
+        T.edge_mlp_dense_count_lists_f32(P, Q, _meta(32, 64), *tail[1:], lptr, thr, gid, parts,
+                                         ahead)
 
 
 def test_meta_dense_count_lists_rating():
@@ -246,6 +257,12 @@ def test_meta_dense_count_lists_rating():
                                                 _meta(6, E, dtype=i32), ahead)
     with pytest.raises(ValueError, match="gid must be Int"):
         T.edge_mlp_dense_count_lists_rating_f32(P, Q, *tail, Z, p, lptr, s, _meta(E), parts, ahead)
+    with pytest.raises(ValueError, match="gid / ahead must be contiguous \\[701\\]"):   # E is s's
+        T.edge_mlp_dense_count_lists_rating_f32(P, Q, *tail, Z, p, lptr, _meta(E + 1), gid, parts,
+                                                ahead)
+    with pytest.raises(ValueError, match="128/32 hidden sizes"):
+        T.edge_mlp_dense_count_lists_rating_f32(P, _meta(5000, 64), *tail, Z, p, lptr, s, gid,
+                                                parts, ahead)
 
 
 def test_meta_rank_resolve_mlp_lists():
@@ -291,6 +308,9 @@ def test_meta_rank_resolve_mlp_lists():
                                      None, rank, _meta(E - 1))
     with pytest.raises(ValueError, match="gid must be Int"):
         T.rank_resolve_mlp_lists_f32(ru, lptr, s, _meta(E, dtype=i64), ahead, 130, P, Q, *tail,
+                                     None, None, None, None, rank, vals)
+    with pytest.raises(ValueError, match="must be contiguous \\[77\\]"):
+        T.rank_resolve_mlp_lists_f32(ru, lptr, s, _meta(E - 1, dtype=i32), ahead, 130, P, Q, *tail,
                                      None, None, None, None, rank, vals)
     with pytest.raises(ValueError, match="row_user must be Long"):
         T.rank_resolve_mlp_lists_f32(_meta(B, dtype=i32), lptr, s, gid, ahead, 130, P, Q, *tail,

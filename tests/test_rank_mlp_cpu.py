@@ -1,6 +1,7 @@
 """Host checks for the full-ranking evaluation of the MLP head (gnnrec.recs.rank_items(head=),
-DESIGN.md §24): the argument checks of the new ops on meta tensors, the refusals that come
-before any launch, and — for the very inputs tests/test_gpu_rank_mlp.py uses — the exact ties
+DESIGN.md §24): the refusals that come before any launch (the argument checks of its ops on
+meta tensors are tests/test_rank_lists_cpu.py's: pairs run as one-slot rows of the list ops),
+and — for the very inputs tests/test_gpu_rank_mlp.py uses — the exact ties
 its tie-rule and rating cases lean on."""
 import functools
 
@@ -27,129 +28,27 @@ def _tail():
     return _meta(32, 128), _meta(32), _meta(32), _meta(1)
 
 
-# ---------------------------------------------------------------- Meta kernels
-def test_meta_dense_count():
-    T = _T()
-    i32 = torch.int32
-    P, Q, tail = _meta(130, 128), _meta(5000, 128), _tail()
-    thr, gid = _meta(130), _meta(130, dtype=i32)
-    parts, ahead = _meta(5, 130, dtype=i32), _meta(130, dtype=i32)
-    T.edge_mlp_dense_count_f32(P, Q, *tail, thr, gid, parts, ahead)
-    T.edge_mlp_dense_count_f32(_meta(0, 128), Q, *tail, _meta(0), _meta(0, dtype=i32),
-                               _meta(5, 0, dtype=i32), _meta(0, dtype=i32))
-    T.edge_mlp_dense_count_f32(P, _meta(0, 128), *tail, thr, gid, _meta(0, 130, dtype=i32), ahead)
-    with pytest.raises(ValueError, match="parts must be a contiguous \\[5, 130\\]"):
-        T.edge_mlp_dense_count_f32(P, Q, *tail, thr, gid, _meta(4, 130, dtype=i32), ahead)
-    with pytest.raises(ValueError, match="parts must be a contiguous"):
-        T.edge_mlp_dense_count_f32(P, Q, *tail, thr, gid, _meta(5, 129, dtype=i32), ahead)
-    with pytest.raises(ValueError, match="parts must be a contiguous"):
-        T.edge_mlp_dense_count_f32(P, Q, *tail, thr, gid, _meta(650, dtype=i32), ahead)
-    with pytest.raises(ValueError, match="parts must be Int"):
-        T.edge_mlp_dense_count_f32(P, Q, *tail, thr, gid, _meta(5, 130), ahead)
-    with pytest.raises(ValueError, match="ahead must be Int"):
-        T.edge_mlp_dense_count_f32(P, Q, *tail, thr, gid, parts, _meta(130, dtype=torch.int64))
-    with pytest.raises(ValueError, match="gid must be Int"):
-        T.edge_mlp_dense_count_f32(P, Q, *tail, thr, _meta(130, dtype=torch.int64), parts, ahead)
-    with pytest.raises(ValueError, match="thr must be Float"):
-        T.edge_mlp_dense_count_f32(P, Q, *tail, _meta(130, dtype=torch.float64), gid, parts, ahead)
-    with pytest.raises(ValueError, match="thr must be contiguous \\[130\\]"):
-        T.edge_mlp_dense_count_f32(P, Q, *tail, _meta(129), gid, parts, ahead)
-    with pytest.raises(ValueError, match="gid / ahead"):
-        T.edge_mlp_dense_count_f32(P, Q, *tail, thr, _meta(131, dtype=i32), parts, ahead)
-    with pytest.raises(ValueError, match="gid / ahead"):
-        T.edge_mlp_dense_count_f32(P, Q, *tail, thr, gid, parts, _meta(129, dtype=i32))
-    with pytest.raises(ValueError, match="128/32 hidden sizes"):
-        T.edge_mlp_dense_count_f32(_meta(130, 64), Q, *tail, thr, gid, parts, ahead)
-    with pytest.raises(ValueError, match="128/32 hidden sizes"):
-        T.edge_mlp_dense_count_f32(P, Q, _meta(32, 64), *tail[1:], thr, gid, parts, ahead)
-
-
-def test_meta_dense_count_rating():
-    T = _T()
-    i32 = torch.int32
-    P, Q, tail = _meta(130, 128), _meta(5000, 128), _tail()
-    Z, p, s, gid = _meta(130), _meta(5000), _meta(130), _meta(130, dtype=i32)
-    parts, ahead = _meta(5, 130, dtype=i32), _meta(130, dtype=i32)
-    T.edge_mlp_dense_count_rating_f32(P, Q, *tail, Z, p, s, gid, parts, ahead)
-    with pytest.raises(ValueError, match="Z must be contiguous \\[130\\]"):
-        T.edge_mlp_dense_count_rating_f32(P, Q, *tail, _meta(129), p, s, gid, parts, ahead)
-    with pytest.raises(ValueError, match="p_col must be contiguous \\[5000\\]"):
-        T.edge_mlp_dense_count_rating_f32(P, Q, *tail, Z, _meta(4999), s, gid, parts, ahead)
-    with pytest.raises(ValueError, match="p_col must be Float"):
-        T.edge_mlp_dense_count_rating_f32(P, Q, *tail, Z, _meta(5000, dtype=torch.float64), s, gid,
-                                          parts, ahead)
-    with pytest.raises(ValueError, match="thr must be contiguous"):
-        T.edge_mlp_dense_count_rating_f32(P, Q, *tail, Z, p, _meta(131), gid, parts, ahead)
-    with pytest.raises(ValueError, match="parts must be a contiguous \\[5, 130\\]"):
-        T.edge_mlp_dense_count_rating_f32(P, Q, *tail, Z, p, s, gid, _meta(6, 130, dtype=i32),
-                                          ahead)
-    with pytest.raises(ValueError, match="gid must be Int"):
-        T.edge_mlp_dense_count_rating_f32(P, Q, *tail, Z, p, s, _meta(130), parts, ahead)
-    with pytest.raises(ValueError, match="128/32 hidden sizes"):
-        T.edge_mlp_dense_count_rating_f32(P, _meta(5000, 64), *tail, Z, p, s, gid, parts, ahead)
-
-
-def test_meta_rank_resolve_mlp():
-    T = _T()
-    i32, i64 = torch.int32, torch.int64
-    n = 77
-    us, gs, s, ahead = _meta(n, dtype=i64), _meta(n, dtype=i64), _meta(n), _meta(n, dtype=i32)
-    P, Q, tail = _meta(n, 128), _meta(5000, 128), _tail()
-    ip, ix = _meta(131, dtype=i64), _meta(900, dtype=i32)
-    Z, p = _meta(n), _meta(5000)
-    rank, vals = _meta(n, dtype=i64), _meta(n)
-    T.rank_resolve_mlp_f32(us, gs, s, ahead, 130, P, Q, *tail, None, None, None, None, rank, vals)
-    T.rank_resolve_mlp_f32(us, gs, s, ahead, 130, P, Q, *tail, Z, p, ip, ix, rank, vals)
-    with pytest.raises(ValueError, match="exclude_indptr and exclude_indices come together"):
-        T.rank_resolve_mlp_f32(us, gs, s, ahead, 130, P, Q, *tail, None, None, ip, None, rank, vals)
-    with pytest.raises(ValueError, match="Z and p_col come together"):
-        T.rank_resolve_mlp_f32(us, gs, s, ahead, 130, P, Q, *tail, Z, None, None, None, rank, vals)
-    with pytest.raises(ValueError, match="n_users \\+ 1"):
-        T.rank_resolve_mlp_f32(us, gs, s, ahead, 131, P, Q, *tail, None, None, ip, ix, rank, vals)
-    with pytest.raises(ValueError, match="one row per pair"):
-        T.rank_resolve_mlp_f32(us, gs, s, ahead, 130, _meta(130, 128), Q, *tail, None, None, None,
-                               None, rank, vals)
-    with pytest.raises(ValueError, match="Z must be contiguous \\[77\\]"):
-        T.rank_resolve_mlp_f32(us, gs, s, ahead, 130, P, Q, *tail, _meta(130), p, None, None, rank,
-                               vals)
-    with pytest.raises(ValueError, match="rank must be Long"):
-        T.rank_resolve_mlp_f32(us, gs, s, ahead, 130, P, Q, *tail, None, None, None, None,
-                               _meta(n, dtype=i32), vals)
-    with pytest.raises(ValueError, match="vals must be contiguous \\[77\\]"):
-        T.rank_resolve_mlp_f32(us, gs, s, ahead, 130, P, Q, *tail, None, None, None, None, rank,
-                               _meta(n - 1))
-    with pytest.raises(ValueError, match="must be contiguous \\[77\\]"):
-        T.rank_resolve_mlp_f32(us, _meta(n - 1, dtype=i64), s, ahead, 130, P, Q, *tail, None, None,
-                               None, None, rank, vals)
-    with pytest.raises(ValueError, match="users must be Long"):
-        T.rank_resolve_mlp_f32(_meta(n, dtype=i32), gs, s, ahead, 130, P, Q, *tail, None, None,
-                               None, None, rank, vals)
-    with pytest.raises(ValueError, match="pairs need users and items"):
-        T.rank_resolve_mlp_f32(us, gs, s, ahead, 130, P, _meta(0, 128), *tail, None, None, None,
-                               None, rank, vals)
-    with pytest.raises(ValueError, match="128/32 hidden sizes"):
-        T.rank_resolve_mlp_f32(us, gs, s, ahead, 130, _meta(n, 64), Q, *tail, None, None, None,
-                               None, rank, vals)
-
-
 # ---------------------------------------------------------------- refusals
 def test_wrappers_refuse_cpu_tensors():
+    """The ops rank_items(head=) runs on: pairs as one-slot rows of the list ops."""
     from gnnrec import ops
     i32, i64 = torch.int32, torch.int64
     P, Q = torch.zeros(4, 128), torch.zeros(9, 128)
     tail = (torch.zeros(32, 128), torch.zeros(32), torch.zeros(32), torch.zeros(1))
+    lptr = torch.arange(5)
     with pytest.raises(ValueError, match="HIP device tensor"):
-        ops.edge_mlp_dense_count(P, Q, *tail, torch.zeros(4), torch.zeros(4, dtype=i32))
+        ops.edge_mlp_dense_count_lists(P, Q, *tail, lptr, torch.zeros(4), torch.zeros(4, dtype=i32))
     with pytest.raises(ValueError, match="HIP device tensor"):
-        ops.edge_mlp_dense_count_rating(P, Q, *tail, torch.zeros(4), torch.zeros(9), torch.zeros(4),
-                                        torch.zeros(4, dtype=i32))
+        ops.edge_mlp_dense_count_lists_rating(P, Q, *tail, torch.zeros(4), torch.zeros(9), lptr,
+                                              torch.zeros(4), torch.zeros(4, dtype=i32))
     with pytest.raises(ValueError, match="HIP device tensor"):
-        ops.rank_resolve_mlp(torch.zeros(4, dtype=i64), torch.zeros(4, dtype=i64), torch.zeros(4),
-                             torch.zeros(4, dtype=i32), 6, P, Q, *tail)
+        ops.rank_resolve_mlp_lists(torch.zeros(4, dtype=i64), lptr, torch.zeros(4),
+                                   torch.zeros(4, dtype=i32), torch.zeros(4, dtype=i32), 6, P, Q,
+                                   *tail)
     # a device table does not excuse a host operand after it
     with pytest.raises(ValueError, match="gid must be"):
-        ops.edge_mlp_dense_count(_meta(4, 128), _meta(9, 128), *_tail(), _meta(4),
-                                 _meta(4, dtype=i64))
+        ops.edge_mlp_dense_count_lists(_meta(4, 128), _meta(9, 128), *_tail(),
+                                       _meta(5, dtype=i64), _meta(4), _meta(4, dtype=i64))
 
 
 def test_popularity_without_a_head_is_not_implemented():

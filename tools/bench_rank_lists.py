@@ -1,8 +1,9 @@
 """Full-ranking evaluation of held-out LISTS for the MLP head, one scored row per user
-(gnnrec.recs.rank_lists(head=...)), against the per-pair path it leaves as it
-is: recs.rank_items(head=...) on recs.list_pairs of the same lists, plain and
-popularity-weighted, both timed end to end in alternation in one process, their results
-compared after every run.  Beside them the list count pass alone
+(gnnrec.recs.rank_lists(head=...)), against recs.rank_items(head=...) on
+recs.list_pairs of the same lists — the same kernels on the expanded pairs, every pair a row
+with one entry, so the column shows what sharing a scored row saves and is no independent
+check of the results — plain and popularity-weighted, both timed end to end in alternation in
+one process, their results compared after every run.  Beside them the list count pass alone
 (ops.edge_mlp_dense_count_lists / _lists_rating) and ops.edge_mlp_dense_denominators over the
 same rows in the same run — the same loop over the items with another epilogue, so the ratio
 shows what the slot loop adds to the MFMA work.
@@ -215,8 +216,10 @@ def main():
             f.write("## Measured (written by tools/bench_rank_lists.py)\n\n")
             f.write(f"{shape['device']}; {n_i:,} items, d = {d}, {a.bought} bought items per "
                     f"user, batch_size {bs}, at most {budget} list entries per row of the pass; "
-                    f"ms, median (min – max) of {a.reps} alternating rounds.  The two paths' "
-                    f"ranks and value bits were compared after every round, both forms.\n\n")
+                    f"ms, median (min – max) of {a.reps} alternating rounds.  `rank_items(head=)` "
+                    f"runs the same kernels on the expanded pairs, every pair a row with one "
+                    f"entry.  The two calls' ranks and value bits were compared after every "
+                    f"round, both forms.\n\n")
             f.write("| | " + " | ".join(keys) + " |\n|---|" + "---|" * len(keys) + "\n")
             for name, get in rows_md:
                 f.write(f"| {name} | " + " | ".join(get(res[k]) for k in keys) + " |\n")

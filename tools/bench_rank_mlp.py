@@ -1,6 +1,7 @@
 """Exact full-ranking positions for the MLP head without a score matrix
 (gnnrec.recs.rank_items(head=...)), plain and popularity-weighted, against
-  * the count pass alone (ops.edge_mlp_dense_count / _count_rating),
+  * the count pass alone (ops.edge_mlp_dense_count_lists / _lists_rating, every pair a row with
+    one entry, as rank_items runs it),
   * ops.edge_mlp_dense_denominators of the same shape in the same run — the same loop over the
     items with another epilogue, the count pass's yardstick — and
   * the exact path that existed before it: exhaustive _MlpHead.score_rows chunks plus the
@@ -91,6 +92,7 @@ def main():
         sb = [ops.edge_mlp(torch.arange(pb.shape[0], device=dev), items[b:b + bs], pb, plain.Q,
                            *plain.tail) for pb, b in zip(Pb, range(0, P, bs))]
         Zb = [plain.denominators(pb) for pb in Pb]
+        lptr = torch.arange(min(bs, P) + 1, device=dev)     # a pair is a one-slot row
         EX, EX_R = (f"exhaustive: score_rows + the definition, first {n_x} pairs",
                     f"exhaustive with ratings (denominators included), first {n_x} pairs")
 
@@ -104,12 +106,14 @@ def main():
                                           weight_popularity=a.weight)
 
         def count():
-            st["ahead"] = [ops.edge_mlp_dense_count(pb, plain.Q, *plain.tail, s, gid[b:b + bs])
+            st["ahead"] = [ops.edge_mlp_dense_count_lists(pb, plain.Q, *plain.tail,
+                                                          lptr[:pb.shape[0] + 1], s, gid[b:b + bs])
                            for pb, s, b in zip(Pb, sb, range(0, P, bs))]
 
         def count_r():
-            st["ahead_r"] = [ops.edge_mlp_dense_count_rating(pb, plain.Q, *plain.tail, z, p, s,
-                                                             gid[b:b + bs])
+            st["ahead_r"] = [ops.edge_mlp_dense_count_lists_rating(pb, plain.Q, *plain.tail, z, p,
+                                                                   lptr[:pb.shape[0] + 1], s,
+                                                                   gid[b:b + bs])
                              for pb, s, z, b in zip(Pb, sb, Zb, range(0, P, bs))]
 
         def denominators():
