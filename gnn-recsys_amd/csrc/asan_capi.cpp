@@ -561,6 +561,69 @@ static void validation() {
             err_has("null CSR"),
         "remove_edges null indices with a CSR asked for");
 #undef RM_EDGES
+  // node removal (csr_remove_nodes.hip): the node table and the relation entry refuse before
+  // their first memset or launch
+  CHECK(gnnrec_node_rank_table_workspace_bytes(0) > 0 &&
+            gnnrec_node_rank_table_workspace_bytes(-5) == gnnrec_node_rank_table_workspace_bytes(0),
+        "node_rank_table empty workspace");
+  CHECK(gnnrec_node_rank_table_workspace_bytes(1000000) < 1000000,
+        "node_rank_table workspace below a byte per node");
+  const size_t nws = gnnrec_node_rank_table_workspace_bytes(70);
+  uint32_t* u16 = reinterpret_cast<uint32_t*>(i16);
+  CHECK(gnnrec_node_rank_table(l16, -1, 70, p16, nws, u16, l16, l16, l16, nullptr) ==
+                GNNREC_EINVAL && err_has("negative"),
+        "node_rank_table negative list");
+  CHECK(gnnrec_node_rank_table(l16, 1, (int64_t)1 << 31, p16, nws, u16, l16, l16, l16, nullptr) ==
+                GNNREC_EINVAL && err_has("int32"),
+        "node_rank_table N range");
+  CHECK(gnnrec_node_rank_table(l16, 1, 70, p16, nws, u16, l16, l16, nullptr, nullptr) ==
+                GNNREC_EINVAL && err_has("status"),
+        "node_rank_table null status");
+  CHECK(gnnrec_node_rank_table(nullptr, 2, 70, p16, nws, u16, l16, l16, l16, nullptr) ==
+                GNNREC_EINVAL && err_has("id list"),
+        "node_rank_table null list");
+  CHECK(gnnrec_node_rank_table(l16, 1, 70, p16, nws, u16, l16, nullptr, l16, nullptr) ==
+                GNNREC_EINVAL && err_has("null output"),
+        "node_rank_table null kept");
+  CHECK(gnnrec_node_rank_table(l16, 1, 70, p16, nws - 1, u16, l16, l16, l16, nullptr) ==
+                GNNREC_EINVAL && err_has("workspace"),
+        "node_rank_table short workspace");
+  CHECK(gnnrec_csr_remove_nodes_workspace_bytes(0, 0) > 0 &&
+            gnnrec_csr_remove_nodes_workspace_bytes(-5, 3) ==
+                gnnrec_csr_remove_nodes_workspace_bytes(0, 3),
+        "remove_nodes empty workspace");
+  CHECK(gnnrec_csr_remove_nodes_workspace_bytes((int64_t)500000000, 1000000) < 500000000,
+        "remove_nodes workspace below a byte per edge");
+  const size_t vws = gnnrec_csr_remove_nodes_workspace_bytes(100, 7);
+#define RM_NODES(E, n_src, n_dst, st, dt, n_new, ws, wsb, iout, status)                         \
+  gnnrec_csr_remove_nodes(l16, l16, l16, i16, l16, E, n_src, n_dst, st, dt, n_new, ws, wsb, l16, \
+                          l16, l16, iout, i16, l16, status, nullptr)
+  CHECK(RM_NODES(-1, 9, 7, l16, l16, 5, p16, vws, l16, l16) == GNNREC_EINVAL && err_has("negative"),
+        "remove_nodes negative E");
+  CHECK(RM_NODES((int64_t)1 << 31, 9, 7, l16, l16, 5, p16, vws, l16, l16) == GNNREC_EINVAL &&
+            err_has("int32"),
+        "remove_nodes E range");
+  CHECK(RM_NODES(100, 9, 7, l16, nullptr, 5, p16, vws, l16, l16) == GNNREC_EINVAL &&
+            err_has("new rows"),
+        "remove_nodes fewer rows without a destination table");
+  CHECK(RM_NODES(100, 9, 7, l16, l16, 8, p16, vws, l16, l16) == GNNREC_EINVAL &&
+            err_has("new rows"),
+        "remove_nodes more rows than before");
+  CHECK(RM_NODES(100, 9, 7, l16, l16, 5, p16, vws, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("status"),
+        "remove_nodes null status");
+  CHECK(RM_NODES(100, 9, 7, l16, l16, 5, p16, vws - 1, l16, l16) == GNNREC_EINVAL &&
+            err_has("workspace"),
+        "remove_nodes short workspace");
+  CHECK(gnnrec_csr_remove_nodes(l16, nullptr, l16, i16, l16, 100, 9, 7, l16, l16, 5, p16, vws, l16,
+                                l16, l16, l16, i16, l16, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("null pointer"),
+        "remove_nodes null dst");
+  CHECK(gnnrec_csr_remove_nodes(l16, l16, l16, nullptr, l16, 100, 9, 7, l16, l16, 5, p16, vws, l16,
+                                l16, l16, l16, i16, l16, l16, nullptr) == GNNREC_EINVAL &&
+            err_has("null CSR"),
+        "remove_nodes null indices with a CSR asked for");
+#undef RM_NODES
   // edge insertion (csr_merge.hip): every refusal comes before the first memset or launch; the
   // empty call (no old edges, no batch) still writes the status and indptr', so its host side
   // is the workspace query, which must give room whatever it is asked

@@ -1682,6 +1682,100 @@ void csr_remove_edges(const Tensor& src, const Tensor& dst, const Tensor& indptr
      "gnnrec_csr_remove_edges");
 }
 
+// remove_nodes, part 1: one node type's rank table (csr_remove_nodes.hip)
+void node_rank_table(const Tensor& nids, int64_t n_nodes, Tensor& ws, Tensor& removed,
+                     Tensor& table, Tensor& kept, Tensor& status) {
+  const OneDevice one_device_;
+  dev(nids, "nids", at::kLong);
+  dev(ws, "workspace", at::kByte);
+  dev(removed, "removed", at::kInt);
+  dev(table, "table", at::kLong);
+  dev(kept, "kept", at::kLong);
+  dev(status, "status", at::kLong);
+  TORCH_CHECK_VALUE(n_nodes >= 0, "node_rank_table: negative node count");
+  TORCH_CHECK_VALUE(nids.dim() == 1 && nids.is_contiguous(),
+                    "node_rank_table: nids must be a contiguous 1-D tensor");
+  const int64_t W = (n_nodes + 31) / 32;
+  TORCH_CHECK_VALUE(removed.numel() == W && table.numel() == W + 1 && kept.numel() == n_nodes &&
+                        status.numel() == 2 && removed.is_contiguous() &&
+                        table.is_contiguous() && kept.is_contiguous() && status.is_contiguous(),
+                    "node_rank_table: output sizes (removed [ceil(N/32)], table [ceil(N/32)+1], "
+                    "kept [N], status [2])");
+  if (meta(nids)) return;
+  const c10::DeviceGuard g(nids.device());
+  ck(gnnrec_node_rank_table(p<int64_t>(nids), nids.numel(), n_nodes, ws.data_ptr(), ws.nbytes(),
+                            reinterpret_cast<uint32_t*>(p<int32_t>(removed)), p<int64_t>(table),
+                            p<int64_t>(kept), p<int64_t>(status), stream_of(nids)),
+     "gnnrec_node_rank_table");
+}
+
+// remove_nodes, part 2: one relation under its types' rank tables (csr_remove_nodes.hip)
+void csr_remove_nodes(const Tensor& src, const Tensor& dst, const Tensor& indptr,
+                      const Tensor& indices, const Tensor& eids,
+                      const optional<Tensor>& src_table, const optional<Tensor>& dst_table,
+                      int64_t n_src, int64_t n_dst, int64_t n_dst_new, Tensor& ws,
+                      Tensor& src_out, Tensor& dst_out, Tensor& kept_eids, Tensor& indptr_out,
+                      Tensor& indices_out, Tensor& eids_out, Tensor& status) {
+  const OneDevice one_device_;
+  dev(src, "src", at::kLong);
+  dev(dst, "dst", at::kLong);
+  dev(indptr, "indptr", at::kLong);
+  dev(indices, "indices", at::kInt);
+  dev(eids, "eids", at::kLong);
+  dev(src_table, "src_table", at::kLong);
+  dev(dst_table, "dst_table", at::kLong);
+  dev(ws, "workspace", at::kByte);
+  dev(src_out, "src_out", at::kLong);
+  dev(dst_out, "dst_out", at::kLong);
+  dev(kept_eids, "kept_eids", at::kLong);
+  dev(indptr_out, "indptr_out", at::kLong);
+  dev(indices_out, "indices_out", at::kInt);
+  dev(eids_out, "eids_out", at::kLong);
+  dev(status, "status", at::kLong);
+  // an EMPTY indptr (a CSR has at least one entry): the relation's CSR is not built, the COO
+  // alone is compacted and every CSR operand must be empty
+  const bool csr = indptr.numel() > 0;
+  const int64_t E = dst.numel(), Ec = csr ? E : 0;
+  TORCH_CHECK_VALUE(n_src >= 0 && n_dst >= 0 && n_dst_new >= 0,
+                    "csr_remove_nodes: negative node count");
+  TORCH_CHECK_VALUE(src.dim() == 1 && dst.dim() == 1 && src.numel() == E &&
+                        src.is_contiguous() && dst.is_contiguous(),
+                    "csr_remove_nodes: src and dst must be contiguous 1-D tensors of one length");
+  TORCH_CHECK_VALUE((!csr || indptr.numel() == n_dst + 1) && indices.numel() == Ec &&
+                        eids.numel() == Ec && indptr.is_contiguous() &&
+                        indices.is_contiguous() && eids.is_contiguous(),
+                    "csr_remove_nodes: the CSR must be indptr [n_dst+1], indices [E], eids [E], "
+                    "contiguous (or all empty)");
+  TORCH_CHECK_VALUE(has(src_table) || has(dst_table),
+                    "csr_remove_nodes: a source table, a destination table or both");
+  TORCH_CHECK_VALUE((!has(src_table) || (src_table->dim() == 1 && src_table->is_contiguous() &&
+                                         src_table->numel() == (n_src + 31) / 32 + 1)) &&
+                        (!has(dst_table) ||
+                         (dst_table->dim() == 1 && dst_table->is_contiguous() &&
+                          dst_table->numel() == (n_dst + 31) / 32 + 1)),
+                    "csr_remove_nodes: a rank table must be a contiguous [ceil(N/32)+1] tensor");
+  TORCH_CHECK_VALUE(has(dst_table) ? n_dst_new <= n_dst : n_dst_new == n_dst,
+                    "csr_remove_nodes: n_dst_new must be the destination type's new node count");
+  TORCH_CHECK_VALUE(src_out.numel() == E && dst_out.numel() == E && kept_eids.numel() == E &&
+                        indptr_out.numel() == (csr ? n_dst_new + 1 : 0) &&
+                        indices_out.numel() == Ec && eids_out.numel() == Ec &&
+                        status.numel() == 2 && src_out.is_contiguous() &&
+                        dst_out.is_contiguous() && kept_eids.is_contiguous() &&
+                        indptr_out.is_contiguous() && indices_out.is_contiguous() &&
+                        eids_out.is_contiguous() && status.is_contiguous(),
+                    "csr_remove_nodes: output sizes");
+  if (meta(dst)) return;
+  const c10::DeviceGuard g(dst.device());
+  ck(gnnrec_csr_remove_nodes(p<int64_t>(src), p<int64_t>(dst), csr ? p<int64_t>(indptr) : nullptr,
+                             p<int32_t>(indices), p<int64_t>(eids), E, n_src, n_dst,
+                             p<int64_t>(src_table), p<int64_t>(dst_table), n_dst_new,
+                             ws.data_ptr(), ws.nbytes(), p<int64_t>(src_out), p<int64_t>(dst_out),
+                             p<int64_t>(kept_eids), csr ? p<int64_t>(indptr_out) : nullptr,
+                             p<int32_t>(indices_out), p<int64_t>(eids_out), p<int64_t>(status),
+                             stream_of(dst)),
+     "gnnrec_csr_remove_nodes");
+}
+
 // add_edges of one relation: the batch merged into the cached CSR (csr_merge.hip)
 void csr_add_edges(const Tensor& indptr, const Tensor& indices, const Tensor& eids,
                    const Tensor& src_new, const Tensor& dst_new, int64_t n_src, int64_t n_dst,
@@ -2534,6 +2628,12 @@ int64_t rank_list_slots() { return gnnrec_rank_list_slots(); }
 int64_t csr_remove_edges_workspace_bytes(int64_t E, int64_t n_dst) {
   return (int64_t)gnnrec_csr_remove_edges_workspace_bytes(E, n_dst);
 }
+int64_t node_rank_table_workspace_bytes(int64_t n_nodes) {
+  return (int64_t)gnnrec_node_rank_table_workspace_bytes(n_nodes);
+}
+int64_t csr_remove_nodes_workspace_bytes(int64_t E, int64_t n_dst) {
+  return (int64_t)gnnrec_csr_remove_nodes_workspace_bytes(E, n_dst);
+}
 int64_t csr_add_edges_workspace_bytes(int64_t n_new, int64_t n_dst) {
   return (int64_t)gnnrec_csr_add_edges_workspace_bytes(n_new, n_dst);
 }
@@ -2687,6 +2787,13 @@ TORCH_LIBRARY(gnnrec, m) {
         "Tensor rm, Tensor(a!) workspace, Tensor(b!) src_out, Tensor(c!) dst_out, "
         "Tensor(d!) kept_eids, Tensor(e!) indptr_out, Tensor(f!) indices_out, "
         "Tensor(g!) eids_out, Tensor(h!) status) -> ()");
+  m.def("node_rank_table(Tensor nids, int n_nodes, Tensor(a!) workspace, Tensor(b!) removed, "
+        "Tensor(c!) table, Tensor(d!) kept, Tensor(e!) status) -> ()");
+  m.def("csr_remove_nodes(Tensor src, Tensor dst, Tensor indptr, Tensor indices, Tensor eids, "
+        "Tensor? src_table, Tensor? dst_table, int n_src, int n_dst, int n_dst_new, "
+        "Tensor(a!) workspace, Tensor(b!) src_out, Tensor(c!) dst_out, Tensor(d!) kept_eids, "
+        "Tensor(e!) indptr_out, Tensor(f!) indices_out, Tensor(g!) eids_out, "
+        "Tensor(h!) status) -> ()");
   m.def("csr_add_edges(Tensor indptr, Tensor indices, Tensor eids, Tensor src_new, "
         "Tensor dst_new, int n_src, int n_dst, Tensor(a!) workspace, Tensor(b!) indptr_out, "
         "Tensor(c!) indices_out, Tensor(d!) eids_out, Tensor(e!) status) -> ()");
@@ -2759,6 +2866,9 @@ TORCH_LIBRARY(gnnrec, m) {
   m.def("rank_list_slots() -> int", &rank_list_slots);
   m.def("csr_remove_edges_workspace_bytes(int n_edges, int n_dst) -> int",
         &csr_remove_edges_workspace_bytes);
+  m.def("node_rank_table_workspace_bytes(int n_nodes) -> int", &node_rank_table_workspace_bytes);
+  m.def("csr_remove_nodes_workspace_bytes(int n_edges, int n_dst) -> int",
+        &csr_remove_nodes_workspace_bytes);
   m.def("csr_add_edges_workspace_bytes(int n_new, int n_dst) -> int",
         &csr_add_edges_workspace_bytes);
   m.def("frontier_mark_workspace_bytes(int n_rows) -> int", &frontier_mark_workspace_bytes);
@@ -2824,6 +2934,8 @@ TORCH_LIBRARY(gnnrec, m) {
   m.impl("csr_from_keys", &csr_from_keys);               \
   m.impl("csr_build", &csr_build);                       \
   m.impl("csr_remove_edges", &csr_remove_edges);         \
+  m.impl("node_rank_table", &node_rank_table);           \
+  m.impl("csr_remove_nodes", &csr_remove_nodes);         \
   m.impl("csr_add_edges", &csr_add_edges);               \
   m.impl("frontier_mark", &frontier_mark);               \
   m.impl("add_", &add_);                                 \

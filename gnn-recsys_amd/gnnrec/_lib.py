@@ -147,6 +147,14 @@ SIGNATURES = {
     # (src, dst, indptr, indices, eids, E, n_dst, rm, R, ws, ws_bytes, 6 outputs, status, stream)
     "gnnrec_csr_remove_edges": (_INT, [_P, _P, _P, _P, _P, _I64, _I64, _P, _I64, _P, _U64,
                                        _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gnnrec_node_rank_table_workspace_bytes": (_U64, [_I64]),
+    # (nids, n_ids, n_nodes, ws, ws_bytes, removed, table, kept, status, stream)
+    "gnnrec_node_rank_table": (_INT, [_P, _I64, _I64, _P, _U64, _P, _P, _P, _P, _P]),
+    "gnnrec_csr_remove_nodes_workspace_bytes": (_U64, [_I64, _I64]),
+    # (src, dst, indptr, indices, eids, E, n_src, n_dst, src_table, dst_table, n_dst_new, ws,
+    #  ws_bytes, 6 outputs, status, stream)
+    "gnnrec_csr_remove_nodes": (_INT, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _P,
+                                       _U64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gnnrec_csr_add_edges_workspace_bytes": (_U64, [_I64, _I64]),
     # (indptr, indices, eids, E, n_src, n_dst, src_new, dst_new, n, ws, ws_bytes, 3 outputs,
     #  status, stream)

@@ -668,6 +668,128 @@ class HeteroGraph:
             if ntype in (ce[0], ce[2]):
                 self._csr_edata.pop(("_member",) + ce, None)
 
+    def remove_nodes(self, nids, ntype=None) -> None:
+        """DGL's remove_nodes, in place: the nodes `nids` (any order, duplicates allowed) leave
+        type `ntype` (needed on a graph with several types; an unknown type raises
+        ValueError).  The surviving nodes keep their order and are renumbered 0..N'-1, and
+        every node-data tensor of the type is compacted alike.  Every relation with the type
+        at either end loses the edges incident to a removed node: its surviving edges keep
+        their order and are renumbered 0..E'-1, their endpoints of the type take the new node
+        ids, and its edge data is compacted alike.  Relations that do not touch the type keep
+        the very same tensors.  An empty list is a no-op; an id outside [0, N) raises
+        ValueError and leaves the graph as it was.  DGL itself is not available to test against
+        here, so parity with its remove_nodes beyond what this text states is not pinned.
+
+        On a HIP device one rank table of the type (gnnrec_node_rank_table) serves every
+        relation, and each relation's COO — and its in-CSR when it is cached — is compacted and
+        relabelled by gnnrec_csr_remove_nodes (no sort; the new CSR is bitwise what build_csr
+        gives on the filtered, relabelled COO with the new row count); a CSR that is not cached
+        is built on first use as before.  The host reads the device twice: the node table's
+        status (N' and the bad-id flag, before anything is replaced) and one transfer with
+        every relation's E'.  A graph in host memory does the same with host tensor ops.  The
+        touched relations' edge data in CSR order, packed edge records, membership CSRs and
+        source-major CSRs are dropped and rebuilt on next use.  Tensors are replaced, never
+        written: a clone taken before is unaffected.
+
+        Loaders and samplers built on this graph BEFORE the call hold node ids, edge ids and
+        per-edge scratch of the old numbering: build them after the last removal."""
+        self._remove_nodes(nids, ntype)
+
+    def _remove_nodes(self, nids, ntype=None):
+        """remove_nodes; -> the ascending old ids of the surviving nodes (None: a no-op)."""
+        if ntype is None:
+            if len(self.ntypes) != 1:
+                raise ValueError("remove_nodes: ntype is needed on a graph with several node "
+                                 "types")
+            ntype = self.ntypes[0]
+        if ntype not in self._num_nodes:
+            raise ValueError(f"remove_nodes: no node type {ntype!r}")
+        N = self._num_nodes[ntype]
+        on_device = torch.device(self.device).type == 'cuda'
+        rm = torch.as_tensor(nids, dtype=torch.int64,
+                             device=self.device if on_device else None).reshape(-1)
+        if rm.numel() == 0:
+            return None
+        touched = [ce for ce in self.canonical_etypes if ntype in (ce[0], ce[2])]
+        new = {}  # ce -> (src', dst', kept_eids, csr' or None)
+        if on_device:
+            try:
+                _bits, table, kept = ops.node_rank_table(rm.contiguous(), N)
+            except ValueError:
+                raise ValueError(f"remove_nodes: a node id lies outside [0, {N})") from None
+            N2 = int(kept.numel())
+            pending = []
+            for ce in touched:
+                s, d = self._coo[ce]
+                n_src, n_dst = self._num_nodes[ce[0]], self._num_nodes[ce[2]]
+                pending.append(ops.csr_remove_nodes(
+                    s, d, self._csr.get(ce), table if ce[0] == ntype else None,
+                    table if ce[2] == ntype else None, n_src, n_dst,
+                    N2 if ce[2] == ntype else n_dst, sync=False))
+            words = torch.stack([st for _p, st in pending]).tolist() if pending else []
+            for ce, (p, _st), (n_new, bad) in zip(touched, pending, words):
+                new[ce] = ops.csr_remove_nodes_finish(p, n_new, bad)
+            ndata = {k: ops.gather_rows(v, kept) for k, v in self._ndata[ntype].items()}
+            edata = {ce: {k: ops.gather_rows(v, new[ce][2]) for k, v in self._edata[ce].items()}
+                     for ce in touched}
+        else:
+            if int(rm.min()) < 0 or int(rm.max()) >= N:
+                raise ValueError(f"remove_nodes: a node id lies outside [0, {N})")
+            keep_n = torch.ones(N, dtype=torch.bool)
+            keep_n[rm] = False
+            kept = torch.nonzero(keep_n).reshape(-1)
+            N2 = int(kept.numel())
+            new_nid = torch.cumsum(keep_n, 0) - 1
+            for ce in touched:
+                s, d = self._coo[ce]
+                E = int(s.numel())
+                keep = torch.ones(E, dtype=torch.bool)
+                if ce[0] == ntype:
+                    keep &= keep_n[s]
+                if ce[2] == ntype:
+                    keep &= keep_n[d]
+                kept_e = torch.nonzero(keep).reshape(-1)
+                s2, d2 = s[kept_e], d[kept_e]
+                if ce[0] == ntype:
+                    s2 = new_nid[s2]
+                if ce[2] == ntype:
+                    d2 = new_nid[d2]
+                csr2, csr = None, self._csr.get(ce)
+                if csr is not None:  # the same compaction: kept slots and rows, renumbered ids
+                    indptr, indices, ids = csr
+                    slot = keep[ids]
+                    new_eid = torch.cumsum(keep, 0) - 1
+                    before = torch.zeros(E + 1, dtype=torch.int64)
+                    torch.cumsum(slot, 0, out=before[1:])
+                    indptr2 = before[indptr]
+                    if ce[2] == ntype:
+                        indptr2 = torch.cat([indptr2[:-1][keep_n], indptr2[-1:]])
+                    indices2 = indices[slot]
+                    if ce[0] == ntype:
+                        indices2 = new_nid[indices2.to(torch.int64)].to(torch.int32)
+                    csr2 = (indptr2, indices2, new_eid[ids[slot]])
+                new[ce] = (s2, d2, kept_e, csr2)
+            ndata = {k: v[kept] for k, v in self._ndata[ntype].items()}
+            edata = {ce: {k: v[new[ce][2]] for k, v in self._edata[ce].items()}
+                     for ce in touched}
+        self._num_nodes[ntype] = N2
+        for k, v in ndata.items():
+            self._ndata[ntype][k] = v
+        for ce in touched:
+            s2, d2, _kept_e, csr2 = new[ce]
+            self._coo[ce] = (s2, d2)
+            for k, v in edata[ce].items():
+                self._edata[ce][k] = v
+            if csr2 is not None:
+                self._csr[ce] = csr2
+            else:
+                self._csr.pop(ce, None)
+            self._out_csr.pop(ce, None)
+            self._csr_edata.pop(ce, None)
+            self._csr_edata.pop(("_member",) + ce, None)
+            self._edge_rec.pop(ce, None)
+        return kept
+
     def to(self, device):
         g = HeteroGraph({ce: (s.to(device), d.to(device)) for ce, (s, d) in self._coo.items()},
                         self._num_nodes, device=device)

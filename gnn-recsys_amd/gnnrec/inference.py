@@ -143,7 +143,10 @@ class IncrementalEmbeddings:
     themselves without an embedding layer), h = layers[-1].  After refresh() every table is
     torch.equal to the same layer of a full pass over a freshly built graph with the same
     edges.  refresh() writes the tables IN PLACE, so a consumer holding inc.h['user'] sees the
-    new rows; only add_nodes replaces the tables of its type (one concatenation each).
+    new rows; two calls replace the tables of their type: add_nodes (one concatenation each)
+    and remove_nodes (one gather of the kept rows each).  `numbering` counts the calls that
+    renumbered a type (remove_nodes): a consumer whose state is indexed by node id rebuilds it
+    when the value changes.
     `generation` counts the refreshes that wrote anything (a consumer that keeps state derived
     from the tables compares it with the value it last saw), and each one reports the rows of
     the last layer it rewrote in RefreshStats.final_dirty.
@@ -201,6 +204,7 @@ class IncrementalEmbeddings:
         self._huge: Dict[tuple, torch.Tensor] = {}
         self.phase_ms: Optional[dict] = None
         self.generation = 0
+        self.numbering = 0
         self.refresh()
 
     @property
@@ -273,6 +277,49 @@ class IncrementalEmbeddings:
             store[nt] = torch.cat([store[nt], store[nt].new_zeros(num)])
         self._prefix[nt] = torch.cat([self._prefix[nt], self._prefix[nt].new_full((num,), -1)])
         self._record(self._S, nt, torch.arange(N, N + num, dtype=torch.int64, device=dev))
+
+    def remove_nodes(self, nids, ntype=None) -> None:
+        """HeteroGraph.remove_nodes.  Before the removal the destinations of the removed
+        nodes' out-edges are recorded in E (frontier_mark over the source-major CSR of every
+        relation that starts in the type; a relation that only ends in it marks nothing, and a
+        removed row needs no mark of its own).  After it the type's cached tables, its (own)
+        feature table and its marks — those just recorded included, when a relation leads from
+        the type to itself — are compacted to the kept rows: one gather each, the second call
+        that REPLACES tables.  `numbering` is incremented."""
+        g = self.g
+        if ntype is None:
+            if len(g.ntypes) != 1:
+                raise ValueError("remove_nodes: ntype is needed on a graph with several node "
+                                 "types")
+            ntype = g.ntypes[0]
+        if ntype not in g.ntypes:
+            raise ValueError(f"remove_nodes: no node type {ntype!r}")
+        N = g.num_nodes(ntype)
+        rm = torch.as_tensor(nids, dtype=torch.int64, device=g.device).reshape(-1)
+        if rm.numel() == 0:
+            return
+        if int(rm.min()) < 0 or int(rm.max()) >= N:
+            raise ValueError(f"remove_nodes: a node id lies outside [0, {N})")
+        rows = torch.unique(rm)  # ascending, distinct: what frontier_mark reads
+        for ce in g.canonical_etypes:
+            if ce[0] == ntype and g.num_edges(ce):
+                oip, oix, _ = g.out_csr(ce)
+                ops.frontier_mark(rows, oip, oix, self._E[ce[2]], check=False)
+        kept = g._remove_nodes(rm, ntype)
+        if self._own_feats:
+            if ntype in self._feats:
+                self._feats[ntype] = ops.gather_rows(self._feats[ntype], kept)
+        else:
+            self._feats = g.ndata['features']
+        for tables in self.layers[1 if not self.embedding_layer else 0:]:
+            if ntype in tables:
+                tables[ntype] = ops.gather_rows(tables[ntype], kept)
+        if not self.embedding_layer and self.layers:
+            self.layers[0] = dict(self._feats)
+        for store in (self._S, self._E, self._prefix):
+            store[ntype] = ops.gather_rows(store[ntype], kept)
+        self.numbering += 1
+        self._dirty = True
 
     def set_features(self, ntype: str, ids, rows) -> None:
         """feats[ntype][ids] = rows (distinct ids), recorded as changed inputs."""

@@ -355,6 +355,113 @@ def csr_remove_edges(src: torch.Tensor, dst: torch.Tensor, rm: torch.Tensor, csr
     return fit(src_o), fit(dst_o), fit(kept), new_csr
 
 
+def node_rank_table(nids: torch.Tensor, n_nodes: int):
+    """DGL's remove_nodes, part 1 (gnnrec_node_rank_table): the rank table of one node type,
+    shared by every relation that touches it.  nids int64 node ids in any order (duplicates
+    allowed).  -> (removed int32 [ceil(N/32)], one bit per old id; table int64 [ceil(N/32)+1],
+    rank << 32 | word per 32 ids, so new_id(v) is one probe; kept int64 [N'], the ascending old
+    ids of the survivors).  An id outside [0, N) raises ValueError (the one readback of the
+    call: two status words)."""
+    T = _T()
+    _dev(nids, "nids", torch.int64)
+    n_nodes = int(n_nodes)
+    if n_nodes < 0:
+        raise ValueError(f"node_rank_table: {n_nodes} nodes")
+    dev, W = nids.device, (n_nodes + 31) // 32
+    nids = nids.reshape(-1).contiguous()
+    removed = torch.empty(W, dtype=torch.int32, device=dev)
+    table = torch.empty(W + 1, dtype=torch.int64, device=dev)
+    kept = torch.empty(n_nodes, dtype=torch.int64, device=dev)
+    status = torch.empty(2, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(int(T.node_rank_table_workspace_bytes(n_nodes)), 1), dtype=torch.uint8,
+                     device=dev)
+    T.node_rank_table(nids, n_nodes, ws, removed, table, kept, status)
+    n_new = n_nodes
+    if dev.type != "meta":
+        n_new, bad = status.tolist()
+        if bad:
+            raise ValueError(f"node_rank_table: a node id lies outside [0, {n_nodes})")
+    return removed, table, kept[:n_new]
+
+
+def csr_remove_nodes(src: torch.Tensor, dst: torch.Tensor, csr, src_table, dst_table,
+                     n_src: int, n_dst: int, n_dst_new: int, sync: bool = True):
+    """DGL's remove_nodes, part 2, on one relation, COO and dst-major CSR together
+    (gnnrec_csr_remove_nodes: a stream compaction, no sort).  (src, dst) the COO in edge-id
+    order, csr = (indptr, indices, eids) its csr_build (None: the COO alone); src_table /
+    dst_table the node_rank_table of the source / destination type (None for a side that keeps
+    its numbering; both for a relation from the type to itself); n_src, n_dst the old node
+    counts and n_dst_new the destination type's new one.  -> (src', dst', kept_eids, csr'): the
+    COO of the edges with no removed endpoint, relabelled, the old id of every new edge, and
+    (indptr' [n_dst_new+1], indices', eids') — bit for bit csr_build(src', dst', n_dst_new) —
+    or None.  An endpoint outside its type raises ValueError (the one readback of the call:
+    two status words).  sync=False: no readback — -> (pending, status), for
+    csr_remove_nodes_finish(pending, n_new, bad) once the caller has read the status words
+    (of several relations in one transfer)."""
+    T = _T()
+    dev, E = dst.device, dst.numel()
+    n_src, n_dst, n_dst_new = int(n_src), int(n_dst), int(n_dst_new)
+    if csr is None:
+        csr = (torch.empty(0, dtype=torch.int64, device=dev),
+               torch.empty(0, dtype=torch.int32, device=dev),
+               torch.empty(0, dtype=torch.int64, device=dev))
+        Ec = 0
+    else:
+        Ec = E
+        if csr[0].numel() != n_dst + 1:
+            raise ValueError("csr_remove_nodes: indptr must have n_dst + 1 entries")
+    indptr, indices, eids = csr
+    for t, n, dt in ((src, "src", torch.int64), (dst, "dst", torch.int64),
+                     (indptr, "indptr", torch.int64), (indices, "indices", torch.int32),
+                     (eids, "eids", torch.int64)):
+        _dev(t, n, dt)
+    if src_table is None and dst_table is None:
+        raise ValueError("csr_remove_nodes: a source table, a destination table or both")
+    for t, n, cnt in ((src_table, "src_table", n_src), (dst_table, "dst_table", n_dst)):
+        if t is not None:
+            _dev(t, n, torch.int64)
+            if t.dim() != 1 or t.numel() != (cnt + 31) // 32 + 1:
+                raise ValueError(f"csr_remove_nodes: {n} is not the rank table of {cnt} nodes")
+    if src.shape != dst.shape or src.dim() != 1:
+        raise ValueError("csr_remove_nodes: src and dst must be 1-D tensors of one length")
+    if indices.numel() != Ec or eids.numel() != Ec:
+        raise ValueError("csr_remove_nodes: the CSR does not match the COO's edge count")
+    if not (0 <= n_dst_new <= n_dst) or (dst_table is None and n_dst_new != n_dst):
+        raise ValueError(f"csr_remove_nodes: {n_dst_new} new rows from {n_dst}")
+    src, dst = src.contiguous(), dst.contiguous()
+    indptr, indices, eids = indptr.contiguous(), indices.contiguous(), eids.contiguous()
+    src_o, dst_o, kept = (torch.empty(E, dtype=torch.int64, device=dev) for _ in range(3))
+    indptr_o = torch.empty(n_dst_new + 1 if indptr.numel() else 0, dtype=torch.int64, device=dev)
+    indices_o, eids_o = torch.empty_like(indices), torch.empty_like(eids)
+    status = torch.empty(2, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(int(T.csr_remove_nodes_workspace_bytes(E, n_dst)), 1), dtype=torch.uint8,
+                     device=dev)
+    T.csr_remove_nodes(src, dst, indptr, indices, eids,
+                       None if src_table is None else src_table.contiguous(),
+                       None if dst_table is None else dst_table.contiguous(), n_src, n_dst,
+                       n_dst_new, ws, src_o, dst_o, kept, indptr_o, indices_o, eids_o, status)
+    pending = (E, n_src, n_dst, src_o, dst_o, kept, indptr_o, indices_o, eids_o)
+    if not sync:
+        return pending, status
+    n_new, bad = (E, 0) if dev.type == "meta" else status.tolist()
+    return csr_remove_nodes_finish(pending, n_new, bad)
+
+
+def csr_remove_nodes_finish(pending, n_new: int, bad: int):
+    """The result of a csr_remove_nodes(..., sync=False) call from its two status words."""
+    E, n_src, n_dst, src_o, dst_o, kept, indptr_o, indices_o, eids_o = pending
+    if bad:
+        raise ValueError(f"csr_remove_nodes: an endpoint lies outside [0, {n_src}) x "
+                         f"[0, {n_dst})")
+    def fit(t):  # the valid prefix; copied out when most of the old-size buffer would idle
+        return t[:n_new].clone() if 2 * n_new < E else t[:n_new]
+    new_csr = None
+    if indptr_o.numel():
+        indptr_o._gnnrec_nnz = n_new
+        new_csr = (indptr_o, fit(indices_o), fit(eids_o))
+    return fit(src_o), fit(dst_o), fit(kept), new_csr
+
+
 def csr_add_edges(csr, src_new: torch.Tensor, dst_new: torch.Tensor, n_src: int, n_dst: int):
     """DGL's add_edges on one relation's dst-major CSR (gnnrec_csr_add_edges: the batch's own
     CSR merged into the cached one; the old edges are not sorted again).  csr = (indptr,

@@ -1361,7 +1361,10 @@ class LiveRecommendations:
         refresh_stats, update_stats = live.refresh()   # inc.refresh() + update_recommendations
 
     idx / vals [n_users, k] stay valid and are updated in place; they are replaced (by grown
-    tensors, the new rows re-ranked as dirty users) only when users were added.  The items each
+    tensors, the new rows re-ranked as dirty users) when users were added, and by new tensors
+    with every user re-ranked (stats['full']) when a type was renumbered (inc.remove_nodes;
+    inc.numbering shows it): the cached lists hold item ids of the old numbering and are not
+    remapped.  The items each
     user has an `etype` edge from are excluded, as in recommend_for_graph.  A refresh of `inc`
     that did not go through this object (inc.generation shows it) makes the next refresh()
     re-rank every user.  kw (batch_size, sample, cand_cap) goes to recommend; head= and
@@ -1378,7 +1381,7 @@ class LiveRecommendations:
         self.max_dirty_frac, self.kw = max_dirty_frac, dict(kw)
         self.phase_ms = None
         self.idx, self.vals = recommend_for_graph(inc.g, inc.h, self.k, None, etype, **self.kw)
-        self._generation = inc.generation
+        self._generation, self._numbering = inc.generation, inc.numbering
 
     def refresh(self):
         """inc.refresh(), then the lists of every user brought up to date ->
@@ -1389,6 +1392,10 @@ class LiveRecommendations:
             rstats = inc.refresh()
         h = inc.h
         dev, n_users, n_items = h['item'].device, h['user'].shape[0], h['item'].shape[0]
+        if inc.numbering != self._numbering:   # a type was renumbered: no list survives
+            self.idx = self.idx.new_full((n_users, self.k), -1)
+            self.vals = self.vals.new_full((n_users, self.k), float('-inf'))
+            skipped = True
         grown = n_users - self.idx.shape[0]
         if grown > 0:    # users were added: their rows are dirty users, re-ranked below
             self.idx = torch.cat([self.idx, self.idx.new_full((grown, self.k), -1)])
@@ -1404,7 +1411,7 @@ class LiveRecommendations:
                                         (ex_ptr.to(dev), ex_idx.to(dev)),
                                         max_dirty_frac=self.max_dirty_frac, return_stats=True,
                                         phase_ms=self.phase_ms, **self.kw)
-        self._generation = inc.generation
+        self._generation, self._numbering = inc.generation, inc.numbering
         return rstats, ustats
 
 

@@ -1052,6 +1052,49 @@ int gnnrec_csr_add_edges(const int64_t* indptr, const int32_t* indices, const in
                          size_t workspace_bytes, int64_t* indptr_out, int32_t* indices_out,
                          int64_t* eids_out, int64_t* status, void* stream);
 
+/* DGLGraph.remove_nodes, part 1: the rank table of one node type, built once per call and
+ * shared by every relation that touches the type.  nids [n_ids]: the node ids to remove, in
+ * any order, duplicates allowed.  Outputs: removed [ceil(n_nodes/32)] — bit (v & 31) of word
+ * v >> 5 is set when node v goes; table [ceil(n_nodes/32) + 1] — entry w holds
+ * (kept nodes before 32 w) << 32 | removed[w], the packed entries gnnrec_csr_remove_edges uses
+ * for edge ids, so new_id(v) = (x >> 32) + popc(~word & lowmask(v & 31)) is one 8-byte probe
+ * x = table[v >> 5]; table[last] = N'; kept [n_nodes], valid prefix N': the ascending old ids
+ * of the surviving nodes (kept[new_id(v)] = v).  status[2] (device): {N', bad}; bad != 0 when
+ * some nids[i] lies outside [0, n_nodes) — then status[0] = n_nodes and no other output is
+ * written.  The status is the call's only readback, and the caller's.  n_nodes < 2^31.
+ * Workspace from gnnrec_node_rank_table_workspace_bytes (about 0.8 B per node). */
+size_t gnnrec_node_rank_table_workspace_bytes(int64_t n_nodes);
+int gnnrec_node_rank_table(const int64_t* nids, int64_t n_ids, int64_t n_nodes, void* workspace,
+                           size_t workspace_bytes, uint32_t* removed, int64_t* table,
+                           int64_t* kept, int64_t* status, void* stream);
+
+/* DGLGraph.remove_nodes, part 2: ONE relation under the rank tables of its source type
+ * (src_table), of its destination type (dst_table) or of both (a relation from the removed
+ * type to itself); a side whose type keeps its numbering passes NULL.  An edge survives iff
+ * neither endpoint is removed; the surviving edges keep their order and are renumbered
+ * 0..E'-1, their endpoints on a relabelled side become new_id(endpoint), and the rows of the
+ * removed destination nodes leave the CSR.  Inputs: the relation's COO (src, dst [n_edges])
+ * and its dst-major CSR as gnnrec_csr_build gives it (indptr [n_dst+1], indices, eids
+ * [n_edges]); n_src, n_dst the OLD node counts, n_dst_new the destination type's N' (= n_dst
+ * without a destination table).  Outputs, each allocated at the OLD edge count with a valid
+ * prefix of E' entries: src_out, dst_out, kept_eids (the old id of new edge i), indices_out,
+ * eids_out; indptr_out [n_dst_new + 1] — bit for bit gnnrec_csr_build of the filtered,
+ * relabelled COO with n_dst_new rows, by stream compaction: no sort, no host plan.  The edge
+ * bitmap comes from wave ballots of the endpoint probes (no atomics).  status[2] (device):
+ * {E', bad}; bad != 0 when an endpoint lies outside [0, n_src) x [0, n_dst) — such an id is
+ * never probed; then status[0] = n_edges and no other output is written.  The status is the
+ * call's only readback, and the caller's.  indptr_out == NULL: the COO alone (the CSR
+ * operands are ignored).  n_edges, n_src, n_dst < 2^31.  Workspace from
+ * gnnrec_csr_remove_nodes_workspace_bytes (about 0.8 B per edge). */
+size_t gnnrec_csr_remove_nodes_workspace_bytes(int64_t n_edges, int64_t n_dst);
+int gnnrec_csr_remove_nodes(const int64_t* src, const int64_t* dst, const int64_t* indptr,
+                            const int32_t* indices, const int64_t* eids, int64_t n_edges,
+                            int64_t n_src, int64_t n_dst, const int64_t* src_table,
+                            const int64_t* dst_table, int64_t n_dst_new, void* workspace,
+                            size_t workspace_bytes, int64_t* src_out, int64_t* dst_out,
+                            int64_t* kept_eids, int64_t* indptr_out, int32_t* indices_out,
+                            int64_t* eids_out, int64_t* status, void* stream);
+
 /* The dirty-set frontier of an incremental embedding refresh: mark[indices[p]] = 1 for every
  * slot p of the listed rows of one relation's SOURCE-major CSR (indptr [n_src+1], indices
  * [n_edges], the destinations) — the destinations of the out-edges of a set of source rows,
