@@ -996,7 +996,11 @@ extern "C" int gnnrec_spmm_csr_planned_dropout_live_f32(
 // reference src/train/run.py:136-138).  sum/mean: grad_X[src_e] += w_e/deg·g[v];
 // max: the gradient of column c goes to the FIRST edge (CSR order) whose message
 // equals the forward maximum (DGL's arg-max convention).  Float atomics into
-// grad_X (no reproducibility requirement on training gradients).
+// grad_X: adds from several dst rows into one source row meet in launch order, so the
+// result is repeatable only when they cannot meet.  Training uses the transposed gather for
+// sum/mean (transpose.hip) and calls the max form with every edge as its own source row
+// (ops._spmm_max_backward), where each (row, column) is written at most once; the
+// scatter into shared source rows is left to GNNREC_SPMM_BWD=atomic.
 namespace gnnrec {
 namespace {
 

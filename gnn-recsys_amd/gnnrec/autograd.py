@@ -2,8 +2,9 @@
 
 Forward values always come from the HIP kernels (the same launches as the
 inference path, so train/eval numerics agree).  Backward, all HIP:
-  * aggregation: the transposed scatter (gnnrec_spmm_backward_f32, first-arg-max
-    routing for max, as DGL's gSpMM backward);
+  * aggregation: sum / mean gather over the transposed block; max routes each column to
+    the first arg-max edge (gnnrec_spmm_backward_f32, as DGL's gSpMM backward) per edge and
+    sums per source row over the source-major CSR (ops.spmm_backward): bitwise repeatable;
   * projections: the pre-activation is recomputed by gnnrec_gemm_f32, the
     ReLU/zero-guarded-norm epilogue is differentiated by gnnrec_act_backward_f32,
     input gradients are gnnrec_gemm_f32 against the transposed weights and weight

@@ -627,13 +627,55 @@ def l2_normalize_rows(y: torch.Tensor, out: Optional[torch.Tensor] = None) -> to
 
 def spmm_backward(indptr, indices, grad_out, reduce, edge_weight=None, X=None, out=None,
                   grad_X=None, n_src=None):
-    """Gradient of spmm w.r.t. its source rows (accumulated into grad_X, created if None)."""
+    """Gradient of spmm w.r.t. its source rows (accumulated into grad_X, created if None).
+    sum / mean: the float-atomic scatter (autograd uses the transposed gather instead);
+    max: bitwise repeatable (_spmm_max_backward), unless GNNREC_SPMM_BWD=atomic asks for the
+    scatter as it does for sum / mean in autograd.SpmmFn (faster, not repeatable)."""
     _dev(grad_out, "grad_out", torch.float32)
     n_dst, d = grad_out.shape
+    if reduce == "max" and os.environ.get("GNNREC_SPMM_BWD") != "atomic":
+        return _spmm_max_backward(indptr, indices, grad_out.contiguous(), edge_weight, X, out,
+                                  grad_X, n_src)
     if grad_X is None:
         grad_X = torch.zeros((n_src, d), dtype=torch.float32, device=grad_out.device)
     grad_out = grad_out.contiguous()
     _T().spmm_backward(indptr, indices, edge_weight, grad_out, X, out, REDUCE[reduce], grad_X)
+    return grad_X
+
+
+def _spmm_max_backward(indptr, indices, grad_out, edge_weight, X, out, grad_X, n_src):
+    """The max reducer's gradient, bitwise repeatable.  gnnrec_spmm_backward_f32 routes column
+    c of destination v to the FIRST edge of v whose message equals the forward maximum and
+    adds it into that edge's source row with a float atomic: a source row that several
+    destinations route to was summed in launch order.  Here the same kernel runs over the
+    edges as their own sources (source e = row e of the gathered messages), so every (edge,
+    column) is written at most once and no two adds meet; the per-edge gradients are then
+    summed per source row by the sum gather over the source-major CSR (stable sort of the
+    source ids: ascending edge order inside a row), as the sum / mean backward does.  Costs
+    two [E, d] tables for the duration of the call and about twice the scatter's time (5.7
+    against 2.7 ms on 7.3M edges at d = 128, tools/bench_spmm_bwd.py).  A cheaper form would
+    record the arg-max edge per (destination, column) in the forward or in one pass and gather
+    over the source-major CSR, without the gathered messages and the [E, d] zero fill."""
+    if X is None or out is None:
+        raise ValueError("spmm_backward: max needs the forward input X and output out")
+    _dev(indices, "indices", torch.int32)
+    E, d = indices.numel(), grad_out.shape[1]
+    rows = grad_X.shape[0] if grad_X is not None else int(n_src)
+    dev = grad_out.device
+    if E == 0:
+        return grad_X if grad_X is not None else torch.zeros((rows, d), dtype=torch.float32,
+                                                             device=dev)
+    msgs = gather_rows(X, indices.to(torch.int64))  # [E, d]: row e = the message of edge e
+    g_edge = torch.zeros((E, d), dtype=torch.float32, device=dev)
+    _T().spmm_backward(indptr, torch.arange(E, dtype=torch.int32, device=dev), edge_weight,
+                       grad_out, msgs, out, REDUCE["max"], g_edge)
+    ip_t, perm = csr_from_keys(indices, rows)
+    g = spmm(ip_t, perm, g_edge, "sum")
+    if grad_X is None:
+        return g
+    if grad_X.is_contiguous():
+        return add_(grad_X, g)
+    grad_X += g
     return grad_X
 
 

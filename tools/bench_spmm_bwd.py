@@ -1,5 +1,8 @@
 """Aggregation backward (atomic scatter vs device transpose + gather) on a sampled-block shape: 730k dst rows x fanout 10
-into 1.1M source rows, d=128 (the first block of a C3 training step).
+into 1.1M source rows, d=128 (the first block of a C3 training step).  max: the atomic scatter
+against the repeatable form that autograd uses (ops.spmm_backward: per-edge gradients, then the
+sum gather over the source-major CSR).  The scatter is timed through the dispatcher op itself:
+ops.spmm_backward offers it for max only under GNNREC_SPMM_BWD=atomic.
 
     python tools/bench_spmm_bwd.py
 """
@@ -38,7 +41,7 @@ def main():
     for reduce in ("mean", "max"):
         Y = ops.spmm(indptr, idx, X, reduce)
         gX = torch.zeros(n_src, d, device=dev)
-        ms = t(lambda: ops.spmm_backward(indptr, idx, G, reduce, None, X=X, out=Y, grad_X=gX))
+        ms = t(lambda: ops._T().spmm_backward(indptr, idx, None, G, X, Y, ops.REDUCE[reduce], gX))
         E = n_dst * fan
         res[reduce] = {"atomic_ms": ms, "edges": E, "G_atomics_per_s": E * d / ms / 1e6}
         if reduce == "mean":
@@ -46,6 +49,9 @@ def main():
             ip_t, ix_t, w_t = ops.csr_transpose(indptr, idx, n_src, mean=True)
             tg = t(lambda: ops.spmm(ip_t, ix_t, G, "sum", edge_weight=w_t))
             res[reduce].update({"transpose_ms": tt, "gather_ms": tg, "transpose_gather_ms": tt + tg})
+        else:
+            res[reduce]["repeatable_ms"] = t(
+                lambda: ops.spmm_backward(indptr, idx, G, reduce, None, X=X, out=Y, n_src=n_src))
     print(json.dumps(res, indent=1))
 
 
